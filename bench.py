@@ -11,9 +11,19 @@ One step = one forward of the whole hot path (conv feature extractor -> 12-layer
 batch, plus -- for N > 1 -- the single RCCL all-gather of the [32, 1499, 768] embeddings that the
 data-parallel design performs per step, issued asynchronously so that it overlaps the next step's
 kernels; all K gathers complete inside the timed region.  Weak scaling: every rank encodes its own 32
-clips.  Rank 0 prints ONE JSON line; `value` = frames encoded by all ranks / max-over-ranks time.
+clips.  Rank 0 prints ONE JSON line; `value` = frames encoded by all ranks / max-over-ranks time, `ms_per_step` = the
+milliseconds one timed step took (max over ranks).
 
-Extra objects on the line:
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line with the headline fields only.
+--full adds the objects below; the timed region, and so `value`, is the same with and without it.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes the embeddings the last timed step returned (for N > 1: the gathered
+                [N*32, 1499, 768] tensor) as float32 .npy: DIR/last_hidden_state.npy = rows of the flattened [clips * frames, 768]
+                matrix -- all of them up to DUMP_MAX_ROWS, else a fixed sample (seed 0, ascending) -- and
+                DIR/last_hidden_state_index.npy = the flat index clip * frames + frame of each row (float64).  Inputs and weights are
+                seeded, so the same arguments give the same inputs in every run.
+
+Extra objects on the line with --full (run after the timed region and the dump):
   roofline      the dominant kernel = the profiling bucket with the largest summed launch time (the projection GEMM at
                 30 s x 32, attention at 10 min x 4; picked from the warm-up steps, whose every launch is bracketed):
                 algorithmic FLOPs / its summed launch time, measured live with HIP events on the launch stream
@@ -65,6 +75,22 @@ BUCKETS = {"gemm_f32": ("gemm_f32_kernel", "mfma", PEAK_F32_MFMA_TFLOPS, 1),
            "attention_f16x3": ("attention_f16x3_kernel", "mfma", PEAK_F16_MFMA_TFLOPS, 3),
            "pos_conv_f16x3_gemm": ("gemm_f16x3_dma_kernel (N = 48 form)", "mfma", PEAK_F16_MFMA_TFLOPS, 3)}
 PEAK_HBM_GBPS = 8000.0
+# --dump-outputs: at most 16 384 rows of 768 floats (48 MiB) plus their index, under the 64 MB a dump may take; the default
+# workload has 32 x 1 499 = 47 968 rows
+DUMP_MAX_ROWS = 16384
+
+
+def dump_outputs(out_dir, emb):
+    """--dump-outputs: rows of the flattened [clips * frames, hidden] embeddings `emb` -- all of them, or a fixed sample (seed 0,
+    ascending) when there are more than DUMP_MAX_ROWS -- to out_dir/last_hidden_state.npy (float32) and their flat indices to
+    out_dir/last_hidden_state_index.npy (float64)."""
+    flat = emb.reshape(-1, emb.shape[-1])
+    n = flat.shape[0]
+    idx = np.arange(n) if n <= DUMP_MAX_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+    rows = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "last_hidden_state.npy"), rows)
+    np.save(os.path.join(out_dir, "last_hidden_state_index.npy"), idx.astype(np.float64))
 
 
 def host_cores() -> int:
@@ -182,12 +208,19 @@ def main():
     ap.add_argument("--precision", choices=["f32", "f16x3", "f16x2"], default="f16x3",
                     help="contraction arithmetic: f16x3 = three fp16 MFMAs per fp32-class product (default; 3.5e-6 rel L2 of fp64), "
                          "f32 = exact fp32 MFMA (2.3e-6), ~2x slower")
-    ap.add_argument("--no-alt", action="store_true", help="skip the short measurement of the other precision mode")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: roofline, per-kernel table, the other "
+                         "precision modes, two streams, the packed forward at the reference's operating point, the CPU baseline with "
+                         "embed_rel_l2, and multi_gpu (N > 1 or --force-collective).  Off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the embeddings of the last timed step to DIR/*.npy (float32, a fixed sample of rows when larger than "
+                         f"{DUMP_MAX_ROWS} rows)")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the short measurement of the other precision mode")
     ap.add_argument("--no-two-streams", action="store_true",
-                    help="skip the short un-profiled run of the library's default schedule (two half-batches on two streams)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the short un-profiled run of the library's default schedule (two half-batches on two streams)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and embed_rel_l2")
     ap.add_argument("--no-packed", action="store_true",
-                    help="skip the short measurement of the reference's own operating point (batches of two 2-6 s utterances) on the packed forward")
+                    help="--full: skip the short measurement of the reference's own operating point (batches of two 2-6 s utterances) on the packed forward")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1 only: create the RCCL process group of one rank anyway and issue the per-step all_gather_into_tensor on "
                          "the device embeddings (what every rank does at N > 1), then check the gathered tensor against the local one")
@@ -197,6 +230,8 @@ def main():
                          "SURVEY.md 8d names (batch 32: ~80 s per pass, 17 GB of host memory) -- same frames/s within a few percent")
     ap.add_argument("--cpu-reps", type=int, default=3)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves
@@ -249,7 +284,8 @@ def main():
         return out
 
     # per-kernel events are on from the first warm-up step: they keep loco_forward on one stream, so every launch of the
-    # run (and of a rocprofv3 trace of it) has the shape the roofline is quoted for
+    # run (and of a rocprofv3 trace of it) has the shape the roofline is quoted for.  A plain run keeps them too: `value` is the
+    # one-stream figure with the dominant bucket's events, whether or not --full reads those events afterwards
     enc.set_profiling(True)
     enc.profile_reset()
     for _ in range(args.warmup):
@@ -278,12 +314,26 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert gathered.shape[0] == world * B
+    if args.force_collective and world == 1:  # the collective really ran (RCCL, device tensors) and returned the rank's own rows
+        assert gathered.data_ptr() != y.data_ptr() and torch.equal(gathered, y), "all_gather_into_tensor at world size 1 changed the embeddings"
+    # the default range policy ("fp32": re-run out-of-range batches on the exact-fp32 kernels) was active; a re-run inside the
+    # timed region would make `value` a mixed-precision figure -- refuse to report one
+    if enc.last_range_fallback:
+        raise SystemExit("bench.py: the synthetic batch left the f16x3 activation range and was re-run in fp32 -- not a valid f16x3 measurement")
+    rank_elapsed = elapsed
+    if world > 1:
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax.item())
+    # before any --full leg: those run more steps, which reuse the gather's output buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered)
     # ---- what the first multi-GPU run needs to explain itself: per-rank step time, how long the forward's stream
     # stood still for the collective, bytes gathered, and a check that every rank's block of the gathered tensor IS that rank's
     multi = None
-    if collective:
+    if collective and args.full:
         blocked_ms = gatherer.blocked_ms()
-        mine = torch.tensor([elapsed / args.steps * 1e3, blocked_ms / args.steps], dtype=torch.float64, device=dev)
+        mine = torch.tensor([rank_elapsed / args.steps * 1e3, blocked_ms / args.steps], dtype=torch.float64, device=dev)
         every = torch.empty((world, 2), dtype=torch.float64, device=dev)
         dist.all_gather_into_tensor(every.view(-1), mine)
         probe = y[0, 0].contiguous()  # 768 floats: row 0 of this rank's first clip, as this rank computed it
@@ -306,17 +356,11 @@ def main():
                  "every_ranks_block_matches_its_probe_row": blocks_ok}
         if rank == 0:
             assert all(blocks_ok), f"gathered blocks do not match their ranks' own rows: {blocks_ok}"
-    if args.force_collective and world == 1:  # the collective really ran (RCCL, device tensors) and returned the rank's own rows
-        assert gathered.data_ptr() != y.data_ptr() and torch.equal(gathered, y), "all_gather_into_tensor at world size 1 changed the embeddings"
-    # the default range policy ("fp32": re-run out-of-range batches on the exact-fp32 kernels) was active; a re-run inside the
-    # timed region would make `value` a mixed-precision figure -- refuse to report one
-    if enc.last_range_fallback:
-        raise SystemExit("bench.py: the synthetic batch left the f16x3 activation range and was re-run in fp32 -- not a valid f16x3 measurement")
     stats = enc.profile_read()
     enc.set_profiling_filter(None)
     # the per-kernel table: a few more steps, every launch bracketed, on the warm chip (the warm-up steps include the first, cold one)
     table_stats, table_steps = [], 0
-    if dominant:
+    if dominant and args.full:
         table_steps = max(1, min(args.steps, 5))
         enc.profile_reset()
         for _ in range(table_steps):
@@ -325,28 +369,13 @@ def main():
         torch.cuda.synchronize()
         table_stats = enc.profile_read()
     enc.set_profiling(False)
-    if world > 1:
-        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed = float(tmax.item())
 
     frames_per_step = world * B * T
     value = frames_per_step * args.steps / elapsed
 
     result = None
     if rank == 0:
-        by = {s["name"]: s for s in stats}
-        table, table_steps = (table_stats, table_steps) if dominant else (stats, args.steps)
-        kernels = {s["name"]: {"launches_per_step": s["launches"] / table_steps, "ms_per_step": s["ms"] / table_steps,
-                               "tflops": (s["flops"] / (s["ms"] * 1e-3) / 1e12) if s["ms"] > 0 and s["flops"] else None,
-                               "gbps": (s["bytes"] / (s["ms"] * 1e-3) / 1e9) if s["ms"] > 0 and s["bytes"] else None}
-                   for s in table}
         wkey = f"{args.clip_seconds:g}sx{B}" if args.clip_seconds < 60 else f"{args.clip_seconds / 60:g}minx{B}"
-        roofline = make_roofline(by, args.precision, args.steps, wkey)
-        if roofline and dominant:  # the share among ALL kernels comes from the fully bracketed warm-up steps
-            roofline["share_of_kernel_time"] = round(next(s_["ms"] for s_ in table if s_["name"] == dominant) / sum(s_["ms"] for s_ in table), 3)
-            roofline["events"] = (f"timed region: hipEvents around the {roofline['launches_per_step']:g} launches per step of this bucket only; "
-                                  f"`kernels` and share_of_kernel_time: {table_steps} further steps after it, every launch bracketed")
         whole = flops_per_clip(T) * B * world * args.steps / elapsed / 1e12
         result = {
             "metric": "audio frames/sec SpeechT5-base encoder, 30s×bs32 @1/2/4/8 GPU; embed L2 vs HF",
@@ -357,20 +386,32 @@ def main():
                       "f16x2": "f16x2 (weights rounded to fp16, activations hi+lo, 2 MFMAs per product; opt-in, ~9e-4: at the 1e-3 bar, no margin)"}[args.precision],
             "precision": args.precision, "range_policy": enc.range_policy, "data": "synthetic",
             "config": {"workload": workload_label(args.clip_seconds, B),
-                       "cpu_baseline_sample": "skipped" if (args.no_cpu_baseline or world > 1) else
+                       "cpu_baseline_sample": "skipped" if (not args.full or args.no_cpu_baseline or world > 1) else
                                               f"{max(1, min(args.cpu_sample_clips, B))} of the {B} clips, as one batch",
                        "clip_seconds": args.clip_seconds, "batch_per_gpu": B, "global_batch": B * world, "frames_per_clip": T,
                        "parallelism": f"dp{world}",
                        "collective": "all_gather(embeddings)" if world > 1 else
                                      ("all_gather(embeddings), forced in a process group of one rank and checked" if args.force_collective else "none")},
             "whole_path_tflops": round(whole, 2),
-            "roofline": roofline, "kernels": kernels,
         }
+        if args.full:
+            by = {s["name"]: s for s in stats}
+            table, table_steps = (table_stats, table_steps) if dominant else (stats, args.steps)
+            kernels = {s["name"]: {"launches_per_step": s["launches"] / table_steps, "ms_per_step": s["ms"] / table_steps,
+                                   "tflops": (s["flops"] / (s["ms"] * 1e-3) / 1e12) if s["ms"] > 0 and s["flops"] else None,
+                                   "gbps": (s["bytes"] / (s["ms"] * 1e-3) / 1e9) if s["ms"] > 0 and s["bytes"] else None}
+                       for s in table}
+            roofline = make_roofline(by, args.precision, args.steps, wkey)
+            if roofline and dominant:  # the share among ALL kernels comes from the fully bracketed further steps
+                roofline["share_of_kernel_time"] = round(next(s_["ms"] for s_ in table if s_["name"] == dominant) / sum(s_["ms"] for s_ in table), 3)
+                roofline["events"] = (f"timed region: hipEvents around the {roofline['launches_per_step']:g} launches per step of this bucket only; "
+                                      f"`kernels` and share_of_kernel_time: {table_steps} further steps after it, every launch bracketed")
+            result["roofline"], result["kernels"] = roofline, kernels
         if multi is not None:
             result["multi_gpu"] = multi
         # the other precision modes, short runs (3 steps), for reference: the exact-fp32 mode ("alt_precision") and the opt-in
         # two-term mode ("opt_in_precision": weights rounded to fp16, ~9e-4 instead of ~1e-6 -- never what `value` reports)
-        if world == 1 and not args.no_alt:
+        if args.full and world == 1 and not args.no_alt:
             for key, alt in (("alt_precision", "f32" if args.precision != "f32" else "f16x3"),
                              ("opt_in_precision", "f16x2" if args.precision != "f16x2" else "f16x3")):
                 enc.precision = alt
@@ -392,7 +433,7 @@ def main():
         # The timed region above runs with per-kernel HIP events, which keep loco_forward on ONE stream.  Without them the
         # library's default for big batches is two half-batches on two streams (bit-identical output, loco_set_streams):
         # the same workload, un-profiled, for reference.  `value` stays the single-stream figure the roofline belongs to.
-        if world == 1 and not args.no_two_streams:
+        if args.full and world == 1 and not args.no_two_streams:
             legs = {}
             default_streams = int(enc.streams)
             for ns in (1, 2):
@@ -411,7 +452,7 @@ def main():
         # The reference's own operating point -- batch_size = 2 in corpus order (…base…py:67-68), SLURP-like 2-6 s utterances -- on the
         # packed forward (loco_forward_packed: G of those batches per launch sequence, every clip keeps its own batch's padded length;
         # tools/packed_bench.py is the long form).  Reported beside the headline, never instead of it.
-        if world == 1 and not args.no_packed and abs(args.clip_seconds - CLIP_SECONDS) < 1e-9:
+        if args.full and world == 1 and not args.no_packed and abs(args.clip_seconds - CLIP_SECONDS) < 1e-9:
             npairs, G = 256, 32
             lens = la.synth.mixed_lengths(2 * npairs, 6 * 16000, min_fraction=2.0 / 6.0)
             fe = la.SpeechT5FeatureExtractorMI355X()
@@ -444,7 +485,7 @@ def main():
                 "fp32_reruns": sum(int(tk.used_fp32) for tk in tickets)}
             del tickets, packs
         # parity + CPU baseline on a bounded sample of the same workload (rank 0, N = 1 only)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import speecht5_oracle as oracle  # the checker; never on the product path
             nc = max(1, min(args.cpu_sample_clips, B))

@@ -29,7 +29,7 @@ def test_bench_with_a_real_rccl_all_gather_at_world_size_one():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--clip-seconds", "10", "--batch", "8", "--force-collective", "--no-alt", "--no-two-streams", "--no-cpu-baseline"]
+           "--clip-seconds", "10", "--batch", "8", "--force-collective", "--full", "--no-alt", "--no-two-streams", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

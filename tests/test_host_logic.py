@@ -299,6 +299,27 @@ def test_bench_starts_its_own_ranks_when_no_launcher_is_present(monkeypatch):
         bench.main()
 
 
+def test_bench_dump_outputs_writes_every_row_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 rows of the flattened embeddings plus their flat index (float64); all rows of a small output, the
+    same seeded sample of DUMP_MAX_ROWS rows of a large one in every run, and at most 64 MB either way."""
+    import bench
+    small = torch.randn(3, 5, 768)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    rows, idx = np.load(tmp_path / "small" / "last_hidden_state.npy"), np.load(tmp_path / "small" / "last_hidden_state_index.npy")
+    assert rows.dtype == np.float32 and idx.dtype == np.float64
+    np.testing.assert_array_equal(idx, np.arange(15))
+    np.testing.assert_array_equal(rows, small.reshape(15, 768).numpy())
+    big = torch.randn(32, 1499, 768)  # the default workload's shape
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    rows, idx = np.load(tmp_path / "a" / "last_hidden_state.npy"), np.load(tmp_path / "a" / "last_hidden_state_index.npy")
+    assert rows.shape == (bench.DUMP_MAX_ROWS, 768) and rows.dtype == np.float32
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 32 * 1499
+    np.testing.assert_array_equal(rows, big.reshape(-1, 768).numpy()[idx.astype(np.int64)])
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "b" / "last_hidden_state_index.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64e6
+
+
 def test_loader_threads_resample_on_the_ranks_own_gpu(monkeypatch, tmp_path):
     """fetch() runs on ThreadPoolExecutor threads, where torch.cuda.current_device() is 0 whatever the main thread
     selected -- every rank > 0 would resample on GPU 0.  The rank's device must be handed down explicitly."""
