@@ -437,6 +437,24 @@ int loco_head_forward(loco_head* head, const float* x, int32_t B, int32_t T, flo
 /* forward + backward: loss (device scalar), optional logits [B,101], grads [78 437] (device) */
 int loco_head_loss_grad(loco_head* head, const float* x, const float* target, int32_t B, int32_t T, float* loss,
                         float* logits, float* grads, void* workspace, size_t workspace_bytes, void* stream);
+/* Ragged forms: the batch is gathered on the device from a store of clips laid end to end, no padded copy.
+ *   store   f32 [rows, 768]; clip i is rows offsets[i] .. offsets[i] + lengths[i] - 1 (offsets int64, in rows: a store may
+ *           hold more than 2^31 floats)
+ *   targets f32 [n_items, 101] (loss_grad only)
+ *   idx     int32 [B] (device): batch entry b is clip idx[b]; indices may repeat and come in any order
+ * Contract, NOT checked on the device: every idx[b] is in [0, n_items) and lengths[idx[b]] <= T_pad.  The batch is pooled
+ * exactly as if pad_sequence had zero-padded every clip to T_pad frames: average divides by T_pad, max sees the zeros,
+ * attention gives each pad frame the score 0 (it adds exp(-m) to the softmax denominator), and in the attention backward
+ * pad frames add alpha_t (dp.(0 - p))(0 - p) to the query gradient.  Results are bit-identical to loco_head_forward /
+ * loco_head_loss_grad on the same batch padded on the host.  Workspace: loco_head_workspace_bytes(B, T_pad).  Null pointers
+ * (logits of loss_grad_ragged excepted), B <= 0 or T_pad <= 0 return LOCO_E_INVALID; a too-small workspace LOCO_E_WORKSPACE.
+ * Asynchronous on stream: no synchronisation, no host allocation. */
+int loco_head_forward_ragged(loco_head* head, const float* store, const int64_t* offsets, const int32_t* lengths,
+                             const int32_t* idx, int32_t B, int32_t T_pad, float* logits, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int loco_head_loss_grad_ragged(loco_head* head, const float* store, const int64_t* offsets, const int32_t* lengths,
+                               const float* targets, const int32_t* idx, int32_t B, int32_t T_pad, float* loss,
+                               float* logits, float* grads, void* workspace, size_t workspace_bytes, void* stream);
 /* torch.optim.Adam semantics (weight decay added to the gradient, bias correction); q is left untouched for
  * methods 0/1, where the reference's q.grad is None */
 int loco_head_adam_step(loco_head* head, const float* grads, float lr, float beta1, float beta2, float eps,

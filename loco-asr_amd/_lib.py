@@ -104,6 +104,8 @@ SIGNATURES = {
     "loco_head_workspace_bytes": (_sz, [_i32, _i32]),
     "loco_head_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_head_loss_grad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "loco_head_forward_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "loco_head_loss_grad_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "loco_head_adam_step": (C.c_int, [_vp, _vp, _f, _f, _f, _f, _f, _vp]),
 }
 

@@ -10,6 +10,8 @@
 // HBM-bound byte work (x is read 2-3 times, 2.4 MB per 16 x 50 frames ... 590 MB at 16 x 12k): the time axis is
 // split over a (B, splits) grid flash-style -- each block produces a partial (max, sum, weighted row sum) that a
 // tiny combine kernel merges -- so long recordings fill the chip instead of 16 CUs.
+// Ragged forms (loco_head_*_ragged): the same kernels read the batch straight from a device-resident store of clips laid end to
+// end, gathered by index; a clip's frames past its length enter the arithmetic as zero values, exactly as pad_sequence's zeros.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -40,18 +42,47 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// z[b,t] = x[b,t,:] . q  (one wavefront per frame, 12 floats per lane)
-__global__ __launch_bounds__(256) void head_scores_kernel(const float* __restrict__ x, const float* __restrict__ q,
-                                                          float* __restrict__ z, long rows) {
+// Where a clip's frames come from.  Padded: x [B, T, 768] as the reference's collate_fn builds it.  Ragged: clips laid end to end
+// in store [rows, 768], batch entry b is clip idx[b] (offsets in rows, 64-bit), and its frames t >= lengths[idx[b]] are the zeros
+// pad_sequence would have written -- fed as zero VALUES through the same arithmetic (no load), so both forms are bit-identical.
+struct PaddedSrc {
+    static constexpr bool kRagged = false;
+    const float* x;
+    int T;
+    __device__ __forceinline__ const float* clip(int b) const { return x + (long)b * T * D; }
+    __device__ __forceinline__ int len(int) const { return T; }
+};
+struct RaggedSrc {
+    static constexpr bool kRagged = true;
+    const float* store;
+    const int64_t* offsets;
+    const int32_t* lengths;
+    const int32_t* idx;
+    __device__ __forceinline__ const float* clip(int b) const { return store + offsets[idx[b]] * (int64_t)D; }
+    __device__ __forceinline__ int len(int b) const { return lengths[idx[b]]; }
+};
+
+// z[b,t] = x[b,t,:] . q  (one wavefront per frame, 12 floats per lane); T = the (padded) frames per clip
+template <class Src>
+__global__ __launch_bounds__(256) void head_scores_kernel(const Src src, const float* __restrict__ q, float* __restrict__ z, long rows,
+                                                          int T) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
+    const float4* xr;
+    bool pad = false;  // uniform within the wavefront: one frame per wave
+    if constexpr (Src::kRagged) {
+        const int b = (int)(row / T), t = (int)(row - (long)b * T);
+        pad = t >= src.len(b);
+        xr = reinterpret_cast<const float4*>(src.clip(b) + (long)t * D);
+    } else {
+        xr = reinterpret_cast<const float4*>(src.x + row * D);
+    }
     const float4* qr = reinterpret_cast<const float4*>(q);
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const float4 a = xr[lane + 64 * i], b = qr[lane + 64 * i];
+        const float4 a = pad ? make_float4(0.f, 0.f, 0.f, 0.f) : xr[lane + 64 * i], b = qr[lane + 64 * i];
         acc += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
     }
     acc = wave_sum(acc);
@@ -66,8 +97,9 @@ __global__ __launch_bounds__(256) void head_scores_kernel(const float* __restric
 // sum_t alpha_t (x_t - p_b) = 0, dalpha_t may be replaced by dalpha_t - dpooled_b . p_b = dpooled_b . (x_t - p_b):
 //     dq_b = sum_t alpha_t (dpooled_b . (x_t - p_b)) (x_t - p_b)                  = Cov_alpha(x) dpooled_b
 // -- every factor centred, nothing cancels, plain fp32 sums suffice.  The block accumulates that form (alpha from the global lse).
-template <int METHOD, bool BWD>
-__global__ __launch_bounds__(256) void head_partial_kernel(const float* __restrict__ x, const float* __restrict__ z,
+// A ragged clip's frames at and past its length are zeros, uniformly per frame t (the whole block, or the wave, walks the same t).
+template <int METHOD, bool BWD, class Src>
+__global__ __launch_bounds__(256) void head_partial_kernel(const Src src, const float* __restrict__ z,
                                                            const float* __restrict__ lse, const float* __restrict__ dpooled,
                                                            const float* __restrict__ pooled,
                                                            float* __restrict__ part_vec, Part* __restrict__ part, int T,
@@ -77,7 +109,10 @@ __global__ __launch_bounds__(256) void head_partial_kernel(const float* __restri
     const int b = blockIdx.y, s = blockIdx.x;
     const int t0 = s * kRows;
     const int nt = min(kRows, T - t0);
-    const float* xb = x + ((long)b * T + t0) * D;
+    const float* xb = src.clip(b) + (long)t0 * D;
+    // frames [n_ld, nt) of this split are padding (none in the padded form): the loops below run over [0, n_ld) with loads and
+    // then over [n_ld, nt) with zeros, in the same frame order -- two branch-free loops instead of a conditional load per frame
+    const int n_ld = Src::kRagged ? max(0, min(nt, src.len(b) - t0)) : nt;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float m_loc = 0.f, l_loc = 0.f, s_loc = 0.f;
     if (METHOD == 2) {
@@ -107,19 +142,22 @@ __global__ __launch_bounds__(256) void head_partial_kernel(const float* __restri
 #pragma unroll
             for (int i = 0; i < 3; ++i) { g4[i] = dp[lane + 64 * i]; p4[i] = pp[lane + 64 * i]; }
             float sacc = 0.f;
-            for (int t = wave; t < nt; t += 4) {
+            auto frame = [&](int t, bool pad) {
                 const float4* xr = reinterpret_cast<const float4*>(xb + (long)t * D);
                 float acc = 0.f;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    const float4 a = xr[lane + 64 * i], g = g4[i], c = p4[i];
+                    const float4 a = pad ? make_float4(0.f, 0.f, 0.f, 0.f) : xr[lane + 64 * i], g = g4[i], c = p4[i];
                     acc += ((a.x - c.x) * g.x + (a.y - c.y) * g.y) + ((a.z - c.z) * g.z + (a.w - c.w) * g.w);
                 }
                 acc = wave_sum(acc);
                 const float wa = expf(z[(long)b * T + t0 + t] - lse[b]) * acc;
                 if (lane == 0) w[t] = wa;
                 sacc += wa;
-            }
+            };
+            int t = wave;
+            for (; t < n_ld; t += 4) frame(t, false);
+            for (; t < nt; t += 4) frame(t, true);
             if (lane == 0) red[wave] = sacc;
             __syncthreads();
             s_loc = (red[0] + red[1]) + (red[2] + red[3]);
@@ -133,13 +171,15 @@ __global__ __launch_bounds__(256) void head_partial_kernel(const float* __restri
         const float* pb = pooled + (long)b * D;
         c0 = pb[tid]; c1 = pb[tid + 256]; c2 = pb[tid + 512];
     }
-    for (int t = 0; t < nt; ++t) {
+    auto accumulate = [&](int t, bool pad) {
         const float* xr = xb + (long)t * D;
-        const float v0 = xr[tid] - c0, v1 = xr[tid + 256] - c1, v2 = xr[tid + 512] - c2;
+        const float v0 = (pad ? 0.f : xr[tid]) - c0, v1 = (pad ? 0.f : xr[tid + 256]) - c1, v2 = (pad ? 0.f : xr[tid + 512]) - c2;
         if (METHOD == 0) { a0 += v0; a1 += v1; a2 += v2; }
         if (METHOD == 1) { a0 = fmaxf(a0, v0); a1 = fmaxf(a1, v1); a2 = fmaxf(a2, v2); }
         if (METHOD == 2) { const float ww = w[t]; a0 = fmaf(ww, v0, a0); a1 = fmaf(ww, v1, a1); a2 = fmaf(ww, v2, a2); }
-    }
+    };
+    for (int t = 0; t < n_ld; ++t) accumulate(t, false);
+    for (int t = n_ld; t < nt; ++t) accumulate(t, true);
     float* pv = part_vec + ((long)b * splits + s) * D;
     pv[tid] = a0; pv[tid + 256] = a1; pv[tid + 512] = a2;
     if (tid == 0) part[b * splits + s] = Part{m_loc, l_loc, s_loc};
@@ -193,12 +233,15 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
 
 // soft-label cross entropy, mean over the batch (torch CrossEntropyLoss with probability targets):
 //   loss = -1/B sum_b sum_c t_bc log_softmax(logits_b)_c ;  dlogits_bc = (softmax_bc * sum_c t_bc - t_bc) / B
+// target_idx (ragged form): the target of batch entry b is row target_idx[b] of target; null: row b
 __global__ __launch_bounds__(128) void head_ce_kernel(const float* __restrict__ logits, const float* __restrict__ target,
-                                                      float* __restrict__ dlogits, float* __restrict__ loss_b, int B) {
+                                                      const int32_t* __restrict__ target_idx, float* __restrict__ dlogits,
+                                                      float* __restrict__ loss_b, int B) {
     __shared__ float red[2];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* tr = target + (long)(target_idx ? target_idx[b] : b) * C;
     const float v = tid < C ? logits[b * C + tid] : -INFINITY;
-    const float t = tid < C ? target[b * C + tid] : 0.f;
+    const float t = tid < C ? tr[tid] : 0.f;
     float m = wave_max(v);
     if (lane == 0) red[wave] = m;
     __syncthreads();
@@ -328,25 +371,46 @@ HeadWs carve(char* base, int B, int T) {
     return w;
 }
 
-template <bool BWD>
-void launch_partial(int method, const float* x, const HeadWs& w, int B, int T, hipStream_t s) {
+template <bool BWD, class Src>
+void launch_partial(int method, const Src& x, const HeadWs& w, int B, int T, hipStream_t s) {
     dim3 grid(w.splits, B);
-    if (method == 0) hipLaunchKernelGGL((head_partial_kernel<0, false>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
-    else if (method == 1) hipLaunchKernelGGL((head_partial_kernel<1, false>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
-    else hipLaunchKernelGGL((head_partial_kernel<2, BWD>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
+    if (method == 0) hipLaunchKernelGGL((head_partial_kernel<0, false, Src>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
+    else if (method == 1) hipLaunchKernelGGL((head_partial_kernel<1, false, Src>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
+    else hipLaunchKernelGGL((head_partial_kernel<2, BWD, Src>), grid, dim3(256), 0, s, x, w.z, w.lse, w.dpooled, w.pooled, w.part_vec, w.part, T, w.splits);
 }
 
-int head_forward_impl(loco_head* h, const float* x, int B, int T, const HeadWs& w, hipStream_t s) {
+template <class Src>
+int head_forward_impl(loco_head* h, const Src& x, int B, int T, const HeadWs& w, hipStream_t s) {
     const float* q = h->params;
     const float* W = h->params + D;
     const float* bias = h->params + D + C * D;
-    if (h->method == 2) hipLaunchKernelGGL(head_scores_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s, x, q, w.z, (long)B * T);
+    if (h->method == 2) hipLaunchKernelGGL(head_scores_kernel<Src>, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s, x, q, w.z, (long)B * T, T);
     launch_partial<false>(h->method, x, w, B, T, s);
     if (h->method == 0) hipLaunchKernelGGL(head_combine_kernel<0>, dim3(B), dim3(256), 0, s, w.part_vec, w.part, w.pooled, w.lse, T, w.splits);
     else if (h->method == 1) hipLaunchKernelGGL(head_combine_kernel<1>, dim3(B), dim3(256), 0, s, w.part_vec, w.part, w.pooled, w.lse, T, w.splits);
     else hipLaunchKernelGGL(head_combine_kernel<2>, dim3(B), dim3(256), 0, s, w.part_vec, w.part, w.pooled, w.lse, T, w.splits);
     hipLaunchKernelGGL(head_logits_kernel, dim3((B * C + 3) / 4), dim3(256), 0, s, w.pooled, W, bias, w.logits, B);
     return hipGetLastError() == hipSuccess ? LOCO_OK : head_fail(LOCO_E_HIP, "intent head forward launch failed");
+}
+
+// forward + soft-label CE + backward into grads; target_idx: null (padded form) or the batch's store indices (ragged form)
+template <class Src>
+int head_loss_grad_impl(loco_head* h, const Src& x, const float* target, const int32_t* target_idx, int B, int T, float* loss,
+                        float* logits, float* grads, const HeadWs& w, hipStream_t s) {
+    int rc = head_forward_impl(h, x, B, T, w, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(head_ce_kernel, dim3(B), dim3(128), 0, s, w.logits, target, target_idx, w.dlogits, w.loss_b, B);
+    hipLaunchKernelGGL(head_param_grads_kernel, dim3(C + B + 1), dim3(256), 0, s, w.dlogits, w.pooled, h->params + D, w.loss_b, grads,
+                       w.dpooled, loss, B);
+    if (h->method == 2) {
+        launch_partial<true>(2, x, w, B, T, s);
+        hipLaunchKernelGGL(head_dq_kernel, dim3(1), dim3(256), 0, s, w.part_vec, grads, B, w.splits);
+    } else if (hipMemsetAsync(grads, 0, D * 4, s) != hipSuccess) {
+        return head_fail(LOCO_E_HIP, "memset failed");
+    }
+    if (logits && hipMemcpyAsync(logits, w.logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return head_fail(LOCO_E_HIP, "copy failed");
+    return hipGetLastError() == hipSuccess ? LOCO_OK : head_fail(LOCO_E_HIP, "intent head backward launch failed");
 }
 }  // namespace
 
@@ -401,7 +465,7 @@ int loco_head_forward(loco_head* h, const float* x, int32_t B, int32_t T, float*
     HeadWs w = carve((char*)ws, B, T);
     if (ws_bytes < w.total) return head_fail(LOCO_E_WORKSPACE, "loco_head_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    int rc = head_forward_impl(h, x, B, T, w, s);
+    int rc = head_forward_impl(h, PaddedSrc{x, T}, B, T, w, s);
     if (rc) return rc;
     if (hipMemcpyAsync(logits, w.logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return head_fail(LOCO_E_HIP, "copy failed");
     return LOCO_OK;
@@ -413,21 +477,31 @@ int loco_head_loss_grad(loco_head* h, const float* x, const float* target, int32
         return head_fail(LOCO_E_INVALID, "loco_head_loss_grad: invalid argument");
     HeadWs w = carve((char*)ws, B, T);
     if (ws_bytes < w.total) return head_fail(LOCO_E_WORKSPACE, "loco_head_loss_grad: workspace too small");
+    return head_loss_grad_impl(h, PaddedSrc{x, T}, target, nullptr, B, T, loss, logits, grads, w, (hipStream_t)stream);
+}
+
+int loco_head_forward_ragged(loco_head* h, const float* store, const int64_t* offsets, const int32_t* lengths, const int32_t* idx,
+                             int32_t B, int32_t T_pad, float* logits, void* ws, size_t ws_bytes, void* stream) {
+    if (!h || !store || !offsets || !lengths || !idx || !logits || !ws || B <= 0 || T_pad <= 0 || B > 65535)
+        return head_fail(LOCO_E_INVALID, "loco_head_forward_ragged: invalid argument");
+    HeadWs w = carve((char*)ws, B, T_pad);
+    if (ws_bytes < w.total) return head_fail(LOCO_E_WORKSPACE, "loco_head_forward_ragged: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    int rc = head_forward_impl(h, x, B, T, w, s);
+    int rc = head_forward_impl(h, RaggedSrc{store, offsets, lengths, idx}, B, T_pad, w, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(head_ce_kernel, dim3(B), dim3(128), 0, s, w.logits, target, w.dlogits, w.loss_b, B);
-    hipLaunchKernelGGL(head_param_grads_kernel, dim3(C + B + 1), dim3(256), 0, s, w.dlogits, w.pooled, h->params + D, w.loss_b, grads,
-                       w.dpooled, loss, B);
-    if (h->method == 2) {
-        launch_partial<true>(2, x, w, B, T, s);
-        hipLaunchKernelGGL(head_dq_kernel, dim3(1), dim3(256), 0, s, w.part_vec, grads, B, w.splits);
-    } else if (hipMemsetAsync(grads, 0, D * 4, s) != hipSuccess) {
-        return head_fail(LOCO_E_HIP, "memset failed");
-    }
-    if (logits && hipMemcpyAsync(logits, w.logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return head_fail(LOCO_E_HIP, "copy failed");
-    return hipGetLastError() == hipSuccess ? LOCO_OK : head_fail(LOCO_E_HIP, "intent head backward launch failed");
+    if (hipMemcpyAsync(logits, w.logits, (size_t)B * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return head_fail(LOCO_E_HIP, "copy failed");
+    return LOCO_OK;
+}
+
+int loco_head_loss_grad_ragged(loco_head* h, const float* store, const int64_t* offsets, const int32_t* lengths, const float* targets,
+                               const int32_t* idx, int32_t B, int32_t T_pad, float* loss, float* logits, float* grads, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (!h || !store || !offsets || !lengths || !targets || !idx || !loss || !grads || !ws || B <= 0 || T_pad <= 0 || B > 65535)
+        return head_fail(LOCO_E_INVALID, "loco_head_loss_grad_ragged: invalid argument");
+    HeadWs w = carve((char*)ws, B, T_pad);
+    if (ws_bytes < w.total) return head_fail(LOCO_E_WORKSPACE, "loco_head_loss_grad_ragged: workspace too small");
+    return head_loss_grad_impl(h, RaggedSrc{store, offsets, lengths, idx}, targets, idx, B, T_pad, loss, logits, grads, w,
+                               (hipStream_t)stream);
 }
 
 int loco_head_adam_step(loco_head* h, const float* grads, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {

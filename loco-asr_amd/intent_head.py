@@ -6,6 +6,7 @@ weight_decay 1e-4, :61-68), data-parallel over RCCL when a process group exists.
     head = IntentClassifierMI355X(method="attention").to("cuda")
     logits = head(x)                         # [B, 1, 101] like the reference (it squeezes dim 1 itself)
     loss = head.train_step(x, target)        # fwd + bwd (+ all-reduce of 78 437 gradients) + Adam
+    loss, logits = head.train_step_ragged(store, *store.batch(indices))   # the same on a device-resident EmbeddingStore
 
 ``state_dict()`` uses the reference's names (``q``, ``classifier.0.weight``, ``classifier.0.bias``) so its
 ``.pth`` files load unchanged (train_classifier.py:132,163,171,221-222).  No CPU path: device tensors only.
@@ -172,6 +173,10 @@ class IntentClassifierMI355X(nn.Module):
         reported loss) are averaged over ranks with one all-reduce before Adam -- data-parallel SGD on the
         global batch."""
         loss, logits, grads = self.loss_and_grads(x, target)
+        return self._reduce_and_step(loss, logits, grads, x.device, group)
+
+    def _reduce_and_step(self, loss, logits, grads, dev, group):
+        """train_step's tail: the gradient all-reduce when a process group exists, then Adam."""
         if dist.is_available() and dist.is_initialized() and not _dp._skip_collective(dist.get_world_size(group)):
             # one all-reduce of the flat gradient buffer (+ the loss); also issued in a process group of ONE rank when
             # dp.FORCE_COLLECTIVE / LOCO_FORCE_COLLECTIVE=1 asks for it (the RCCL path on a one-GPU box): sum / 1 is exact
@@ -183,9 +188,58 @@ class IntentClassifierMI355X(nn.Module):
             loss = buf[-1]
             self.allreduces_issued += 1
         hp = self.hyper
-        dev = x.device
         with torch.cuda.device(dev):
             self._check(self._lib.loco_head_adam_step(self._h, C.c_void_p(grads.data_ptr()), hp["lr"], hp["beta1"], hp["beta2"],
                                                       hp["eps"], hp["weight_decay"],
                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return loss, logits
+
+    # ---- ragged forms: batches gathered on the device from an EmbeddingStore (embedding_store.py) -----------------
+    def _ragged(self, store, idx: torch.Tensor, T_pad: int):
+        dev = store.rows.device
+        if dev.type != "cuda":
+            raise RuntimeError("IntentClassifierMI355X runs only on an AMD GPU (no CPU path): the store is on " + str(dev))
+        if idx.dtype != torch.int32 or idx.dim() != 1 or idx.device != dev or not idx.is_contiguous():
+            raise ValueError(f"idx must be a contiguous 1-d int32 tensor on {dev} (EmbeddingStore.batch), got {idx.dtype} "
+                             f"{tuple(idx.shape)} on {idx.device}")
+        if store.rows.dtype != torch.float32 or store.rows.dim() != 2 or store.rows.shape[1] != D:
+            raise ValueError(f"the store's rows must be [n_rows, 768] float32, got {store.rows.dtype} {tuple(store.rows.shape)}")
+        self._ensure(dev)
+        return dev, int(idx.numel()), int(T_pad)
+
+    @torch.no_grad()
+    def forward_ragged(self, store, idx: torch.Tensor, T_pad: int) -> torch.Tensor:
+        """forward() on the batch `idx` of `store` as if zero-padded to T_pad frames (EmbeddingStore.batch) -> [B, 1, 101]"""
+        dev, B, T = self._ragged(store, idx, T_pad)
+        ws = self._workspace(B, T, dev)
+        logits = torch.empty(B, NCLS, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            self._check(self._lib.loco_head_forward_ragged(
+                self._h, C.c_void_p(store.rows.data_ptr()), C.c_void_p(store.offsets.data_ptr()), C.c_void_p(store.lengths_dev.data_ptr()),
+                C.c_void_p(idx.data_ptr()), B, T, C.c_void_p(logits.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return logits.unsqueeze(1)
+
+    @torch.no_grad()
+    def loss_and_grads_ragged(self, store, idx: torch.Tensor, T_pad: int):
+        """loss_and_grads() on the batch `idx` of `store` (targets from store.targets) -> (loss, logits [B,101], grads)"""
+        dev, B, T = self._ragged(store, idx, T_pad)
+        ws = self._workspace(B, T, dev)
+        n = self._lib.loco_head_num_params()
+        if self._grads is None or self._grads.device != dev:
+            self._grads = torch.empty(n, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        logits = torch.empty(B, NCLS, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            self._check(self._lib.loco_head_loss_grad_ragged(
+                self._h, C.c_void_p(store.rows.data_ptr()), C.c_void_p(store.offsets.data_ptr()), C.c_void_p(store.lengths_dev.data_ptr()),
+                C.c_void_p(store.targets.data_ptr()), C.c_void_p(idx.data_ptr()), B, T, C.c_void_p(loss.data_ptr()),
+                C.c_void_p(logits.data_ptr()), C.c_void_p(self._grads.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return loss, logits, self._grads
+
+    @torch.no_grad()
+    def train_step_ragged(self, store, idx: torch.Tensor, T_pad: int, group=None):
+        """train_step() on the batch `idx` of `store`: same all-reduce and Adam tail."""
+        loss, logits, grads = self.loss_and_grads_ragged(store, idx, T_pad)
+        return self._reduce_and_step(loss, logits, grads, store.rows.device, group)

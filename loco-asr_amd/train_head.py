@@ -13,6 +13,11 @@ rank is 1/W of the epoch); gradients are all-reduced; the up to W-1 batches of a
 that the collectives line up.
 
     python loco-asr_amd/train_head.py -m audio -p attention -v base
+    python loco-asr_amd/train_head.py -m audio -p attention -v base --device-resident
+
+--device-resident loads the train and validation embeddings ONCE into a ragged store in HBM (embedding_store.py) and trains
+on batches gathered there by index (the head's ragged kernels): same batches, same results, no per-epoch file reads, no
+host padding, and the host waits on the device only at the every-200-iterations print and at the end of each epoch.
     torchrun --standalone --nproc-per-node 8 loco-asr_amd/train_head.py -m audio -p attention -v base
 """
 from __future__ import annotations
@@ -31,6 +36,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 la = importlib.import_module("loco-asr_amd")
 sink = importlib.import_module("loco-asr_amd.sink")
+EmbeddingStore = importlib.import_module("loco-asr_amd.embedding_store").EmbeddingStore
 
 
 def collate_fn(batch):
@@ -47,6 +53,23 @@ def evaluate(model, loader, device, n_items, collective=False):
         logp = torch.log_softmax(pred, dim=1)
         sums[0] += -(target.to(device).float() * logp).sum().double()
         sums[1] += (pred.argmax(1) == target.to(device).argmax(1)).double().sum()
+    if collective:
+        import torch.distributed as dist
+        dist.all_reduce(sums)
+    return float(sums[0]) / n_items, float(sums[1]) / n_items
+
+
+@torch.no_grad()
+def evaluate_resident(model, store, plan, device, n_items, collective=False):
+    """evaluate() on batches of a device-resident store: `plan` = store.batches(this rank's index lists); the same torch
+    metric ops on the same logits, so the same sums."""
+    sums = torch.zeros(2, dtype=torch.float64, device=device)
+    for idx, T_pad in plan:
+        pred = model.forward_ragged(store, idx, T_pad).squeeze(1)
+        target = store.targets[idx]
+        logp = torch.log_softmax(pred, dim=1)
+        sums[0] += -(target * logp).sum().double()
+        sums[1] += (pred.argmax(1) == target.argmax(1)).double().sum()
     if collective:
         import torch.distributed as dist
         dist.all_reduce(sums)
@@ -104,6 +127,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None,
                     help="seed of the head's initial parameters (the reference does not seed: train_classifier.py draws them from "
                          "torch's default generator); under data parallelism rank 0's parameters are broadcast either way")
+    ap.add_argument("--device-resident", action="store_true",
+                    help="load the train and validation embeddings once into a ragged store in HBM and gather every batch there by "
+                         "index (same batches and results as the default loop, no per-epoch file reads); under torchrun EVERY rank "
+                         "holds the whole train and validation store")
     args = ap.parse_args(argv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -128,6 +155,14 @@ def main(argv=None):
         sets.append(sink.EmbeddingsTargets(folder, args.modality, "train_synthetic"))
     train_set = ConcatDataset(sets)
     val_set = sink.EmbeddingsTargets(folder, args.modality, "devel")
+    train_store = val_store = None
+    if args.device_resident:
+        import time
+        t0 = time.perf_counter()
+        train_store = EmbeddingStore.from_folders(folder, args.modality, ["train"] + (["train_synthetic"] if len(sets) > 1 else []), device)
+        val_store = EmbeddingStore.from_folders(folder, args.modality, ["devel"], device)
+        assert len(train_store) == len(train_set) and len(val_store) == len(val_set)
+        print(f"Device-resident store: {train_store.nbytes + val_store.nbytes} bytes in HBM, loaded in {time.perf_counter() - t0:.1f} s")
     print(f"Train set: {len(train_set)}, Val set: {len(val_set)}")
     n_test, test_note = len(val_set), " (no test split on disk: divided by the validation size)"
     if os.path.isdir(os.path.join(folder, "test", args.modality)):
@@ -142,7 +177,14 @@ def main(argv=None):
         return ids, DataLoader(train_set, batch_sampler=mine, collate_fn=collate_fn)  # only this rank's batches are read from disk
 
     # every rank evaluates ITS share of the validation batches; the two sums meet in one all-reduce (evaluate)
-    val_loader = DataLoader(val_set, batch_sampler=strided_batches(len(val_set), batch_size, world, rank), collate_fn=collate_fn)
+    val_batches = strided_batches(len(val_set), batch_size, world, rank)
+    val_loader = DataLoader(val_set, batch_sampler=val_batches, collate_fn=collate_fn)
+    val_plan = val_store.batches(val_batches) if args.device_resident else None
+
+    def validate(m, n_items):
+        if args.device_resident:
+            return evaluate_resident(m, val_store, val_plan, device, n_items, collective)
+        return evaluate(m, val_loader, device, n_items, collective)
 
     if args.seed is not None:
         torch.manual_seed(args.seed)
@@ -161,19 +203,36 @@ def main(argv=None):
     print("Training started...")
     for epoch in range(args.epochs):
         epoch_loss, acc_train, n_batches, n_seen = 0.0, 0.0, 0, 0
-        batch_ids, train_loader = my_epoch_loader()
-        for i, (_, data, target) in zip(batch_ids, train_loader):
-            loss, pred = model.train_step(data.to(device), target.to(device))
-            epoch_loss += float(loss)
-            acc_train += float((pred.argmax(1) == target.to(device).argmax(1)).float().sum())
-            n_batches += 1
-            n_seen += data.shape[0]
-            if (i + 1) % 200 == 0 and rank == 0:
-                print(f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}")
-                text += f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}\n"
+        if args.device_resident:
+            # the same batches; loss and correct count summed on the device (fp64 adds of the same fp32 losses in the same order
+            # = the default loop's Python floats), read back once per epoch
+            batch_ids, mine = epoch_batches(len(train_set), batch_size, world, rank, g)
+            loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+            correct = torch.zeros((), dtype=torch.int64, device=device)
+            for i, (idx, T_pad) in zip(batch_ids, train_store.batches(mine)):
+                loss, pred = model.train_step_ragged(train_store, idx, T_pad)
+                loss_sum += loss.double()
+                correct += (pred.argmax(1) == train_store.targets[idx].argmax(1)).sum()
+                n_batches += 1
+                n_seen += idx.numel()
+                if (i + 1) % 200 == 0 and rank == 0:
+                    print(f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}")
+                    text += f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}\n"
+            epoch_loss, acc_train = float(loss_sum), float(correct)
+        else:
+            batch_ids, train_loader = my_epoch_loader()
+            for i, (_, data, target) in zip(batch_ids, train_loader):
+                loss, pred = model.train_step(data.to(device), target.to(device))
+                epoch_loss += float(loss)
+                acc_train += float((pred.argmax(1) == target.to(device).argmax(1)).float().sum())
+                n_batches += 1
+                n_seen += data.shape[0]
+                if (i + 1) % 200 == 0 and rank == 0:
+                    print(f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}")
+                    text += f"Epoch [{epoch+1}/{args.epochs}], Iteration [{i+1}/{n_train_batches}], Loss: {float(loss):.4f}\n"
         epoch_loss /= max(1, n_batches)
         acc_train /= max(1, n_seen)
-        val_loss, acc_val = evaluate(model, val_loader, device, len(val_set), collective)
+        val_loss, acc_val = validate(model, len(val_set))
         for k, v in (("loss", epoch_loss), ("val_loss", val_loss), ("acc", acc_train), ("val_acc", acc_val)):
             curves[k].append(v)
         line = (f"Epoch [{epoch+1}/{args.epochs}], Training Loss: {epoch_loss:.4f}, Training accuracy: {round(acc_train*100, 2)}, "
@@ -205,7 +264,7 @@ def main(argv=None):
     model.load_state_dict(torch.load(os.path.join(save_folder, f"{tag}_best.pth")))
     print("Evaluating model on test set" + test_note)
     # the reference iterates the validation loader here and divides by len(test_set) (train_classifier.py:56, 211-212)
-    tl, ta = evaluate(model, val_loader, device, n_test, collective)
+    tl, ta = validate(model, n_test)
     print(f"Test Loss: {tl:.4f}")
     print(f"Test Accuracy: {ta*100:.2f}")
     print("Evaluation done!")
