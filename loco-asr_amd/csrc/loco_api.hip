@@ -18,6 +18,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/loco_asr.h"
@@ -45,16 +46,6 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(LOCO_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-struct Tensor {
-    float* d = nullptr;
-    std::vector<int64_t> shape;
-    int64_t numel() const {
-        int64_t n = 1;
-        for (auto s : shape) n *= s;
-        return n;
-    }
-};
-
 const int kConvK[7] = {10, 3, 3, 3, 3, 2, 2};
 const int kConvS[7] = {5, 2, 2, 2, 2, 2, 2};
 
@@ -64,19 +55,31 @@ struct SplitW {  // fp16 hi/lo planes of one GEMM weight (precision mode f16x3),
     float inv_scale = 1.0f;
 };
 
+// Checkpoint tensors the forward reads as loaded (loco_encoder::raw) are bound here by loco_finalize_weights, so that no forward
+// looks a name up.  loco_set_weight reuses a key's device buffer once allocated, so a bound pointer cannot go stale.
+struct WB {  // "<prefix>weight" and "<prefix>bias": a Linear's W and b, a LayerNorm's (or the GroupNorm's) gamma and beta
+    const float *w = nullptr, *b = nullptr;
+};
 struct LayerW {
     float* wqkv = nullptr;  // [2304,768], q rows pre-scaled by 1/8
     float* bqkv = nullptr;  // [2304]
     SplitW sqkv, so, s1, s2;
+    WB out_proj, layer_norm, ffn_in, ffn_out, final_layer_norm;  // ffn_in / ffn_out: feed_forward.intermediate_dense / output_dense
+};
+struct StemW {  // the prenet's tensors (bound for a handle with the speech prenet only), the encoder's input LayerNorm and pe_k
+    WB conv0_norm, proj_norm, proj;  // feature_encoder.conv_layers.0.layer_norm, feature_projection.layer_norm / .projection
+    const float* pos_b = nullptr;    // pos_conv_embed.conv.bias
+    WB layer_norm;                   // wrapped_encoder.layer_norm
+    const float* pe_k = nullptr;     // wrapped_encoder.embed_positions.pe_k [320,64]
 };
 
 // Profiling buckets, named after the kernel that runs in them (the two precision modes have their own attention and
 // positional-conv buckets: the f16x3 positional conv IS a gemm_f16x3_dma_kernel launch, but keeps a bucket of its own because
 // its shape -- N = 48, K = 6144, halo layout -- has little in common with the projection GEMMs).
-enum KernelId { K_GEMM = 0, K_ATTN, K_LN, K_CONV0, K_POSCONV, K_FRAMES, K_COPY, K_GEMM_SPLIT, K_ATTN_SPLIT, K_POSCONV_SPLIT, K_QP, K_COUNT };
+enum KernelId { K_GEMM = 0, K_ATTN, K_LN, K_CONV0, K_POSCONV, K_FRAMES, K_COPY, K_GEMM_SPLIT, K_ATTN_SPLIT, K_POSCONV_SPLIT, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"gemm_f32",     "attention_f32", "layernorm",       "conv0_gn_gelu",
                                            "pos_conv_f32", "frame_counts",  "copy",            "gemm_f16x3",
-                                           "attention_f16x3", "pos_conv_f16x3_gemm", "qp_table_gemm_f16x3"};
+                                           "attention_f16x3", "pos_conv_f16x3_gemm"};
 
 struct ProfRec {
     hipEvent_t a, b;
@@ -114,6 +117,16 @@ struct Call {
     bool dual = false;           // inside the two half-batch schedule (GemmSplitArgs::co_scheduled)
     float* range_dev = nullptr;  // [kRangeMaxStages][kRangeShards] in the workspace, zeroed at the start of the forward
     StatusBlock* st = nullptr;
+    int nslot = 0;               // range slots taken by the (half-)batch being enqueued: each half starts again at 0
+    // range tracking: one status word (x 8 shards) per tensor that is stored as fp16 planes and whose range does not follow from
+    // the weights alone (loco_kernels.h), in launch order; the two halves of a dual-stream forward walk the same sequence and
+    // share the words (a maximum does not care who contributes)
+    float* slot(const char* name, int layer = -1) {
+        if (!range_dev || !st || nslot >= kFiniteStage) return nullptr;
+        st->names[nslot] = name;
+        st->layer[nslot] = layer;
+        return range_dev + (size_t)kRangeShards * nslot++;
+    }
 };
 
 }  // namespace
@@ -121,7 +134,7 @@ struct Call {
 struct loco_encoder {
     loco_config cfg;
     int device = 0;
-    std::map<std::string, Tensor> raw;  // as loaded, HF names
+    std::map<std::string, float*> raw;  // device copies as loaded, HF names
     std::map<std::string, std::vector<int64_t>> expected;
     bool finalized = false;
     // prepared
@@ -133,6 +146,7 @@ struct loco_encoder {
     SplitW posg_s;                 // positional conv weight as the GEMM's W: [16][48][128*48]
     int precision = 1;             // 0 = exact fp32 MFMA, 1 = fp16 x3 split MFMA (default), 2 = f16x2 (weights rounded to fp16; opt-in)
     std::vector<LayerW> layers;
+    StemW stem;
     // published with release stores (table first, then its row count), read with acquire loads: a forward on another host thread
     // that sees the new row count also sees the new, longer table (ensure_sin_rows; loco_forward_async allows concurrent callers)
     std::atomic<float*> sin_tab{nullptr};
@@ -223,7 +237,8 @@ std::string canonical_key(const char* key) {
     return k;
 }
 
-const float* W(const loco_encoder* e, const std::string& k) { return e->raw.at(k).d; }
+const float* W(const loco_encoder* e, const std::string& k) { return e->raw.at(k); }
+WB weight_bias(const loco_encoder* e, const std::string& prefix) { return {W(e, prefix + "weight"), W(e, prefix + "bias")}; }
 
 size_t align_up(size_t n) { return (n + 255) & ~size_t(255); }
 
@@ -320,14 +335,18 @@ struct Bracket {
     }
 };
 
+// algorithmic FLOPs and fp32 bytes of a (batched) GEMM, as the profiling brackets report them
+double gemm_flops(int M, int N, int K, int nb1, int nb2) { return 2.0 * M * (double)N * K * ((double)nb1 * nb2); }
+double gemm_bytes(int M, int N, int K, int nb1, int nb2, int epi) {
+    const double nb = (double)nb1 * nb2;
+    return 4.0 * (nb * ((double)M * K + (double)M * N * (epi == kEpiResidual ? 2 : 1)) + (double)N * K);
+}
+
 int run_gemm(loco_encoder* e, hipStream_t s, const float* A, long lda, const float* Wt, long ldw, const float* bias,
              const float* R, long ldr, float* C, long ldc, int M, int N, int K, int epi, int nb1 = 1, int nb2 = 1,
              long sA1 = 0, long sA2 = 0, long sC1 = 0, long sC2 = 0) {
     GemmArgs a{A, Wt, bias, R, C, M, N, K, lda, ldw, ldc, ldr, nb1, nb2, sA1, sA2, sC1, sC2, epi};
-    const double nb = (double)nb1 * nb2;
-    const double flops = 2.0 * M * (double)N * K * nb;
-    const double bytes = 4.0 * (nb * ((double)M * K + (double)M * N * (epi == kEpiResidual ? 2 : 1)) + (double)N * K);
-    Bracket br(e, s, K_GEMM, flops, bytes);
+    Bracket br(e, s, K_GEMM, gemm_flops(M, N, K, nb1, nb2), gemm_bytes(M, N, K, nb1, nb2, epi));
     HIP_TRY(launch_gemm(a, s));
     return LOCO_OK;
 }
@@ -339,30 +358,40 @@ int run_ln(loco_encoder* e, hipStream_t s, const float* x, const float* g, const
     return LOCO_OK;
 }
 
-// split-precision GEMM: A and W as fp16 hi/lo planes; output fp32 (C) or planes (Chi/Clo)
-int run_gemm_split(loco_encoder* e, const Call& c, hipStream_t s, const _Float16* Ahi, const _Float16* Alo, long lda, const SplitW& Wt, long ldw,
-                   const float* bias, const float* R, long ldr, float* C, _Float16* Chi, _Float16* Clo, long ldc, int M, int N, int K,
-                   int epi, int nb1 = 1, long sA1 = 0, long sC1 = 0, int nb2 = 1, long sA2 = 0, long sC2 = 0,
-                   const GemmSplitArgs* scatter = nullptr, const _Float16* Rhi = nullptr, const _Float16* Rlo = nullptr,
-                   float* range_slot = nullptr, int kid = K_GEMM_SPLIT, int ktaps = 1) {
-    GemmSplitArgs a{Ahi, Alo, Wt.hi, Wt.lo, bias, R, C, Chi, Clo, M, N, K, lda, ldw, ldc, ldr, nb1, nb2, sA1, sA2, sC1, sC2, epi};
-    a.Rhi = Rhi;
-    a.Rlo = Rlo;
-    a.out_scale = Wt.inv_scale;
-    a.range_slot = range_slot;
-    a.co_scheduled = c.dual;
-    a.ktaps = ktaps;
-    a.terms = (c.precision == 2 && kid != K_QP) ? 2 : 3;  // the relative-position table keeps all three terms (K = 64: it costs nothing)
-    if (scatter) {
-        a.qkv_stride = scatter->qkv_stride;
-        a.T = scatter->T;
-    }
+// Split-precision GEMM (A and W as fp16 hi/lo planes; output fp32 C or planes Chi/Clo) of one batch over dense rows (lda = ldw = K,
+// ldc = N): callers set the operands by field name, and whatever strides or batches differently.
+GemmSplitArgs split_args(int M, int N, int K, int epilogue) {
+    GemmSplitArgs a{};
+    a.M = M; a.N = N; a.K = K;
+    a.lda = a.ldw = K;
+    a.ldc = N;
+    a.epilogue = epilogue;
+    a.nb1 = a.nb2 = 1;
+    return a;
+}
+
+// The one launch path of a split GEMM of the forward: the weight planes and every field that follows from the call are set here.
+int run_gemm_split(loco_encoder* e, const Call& c, hipStream_t s, GemmSplitArgs a, const SplitW& w, int kid, double flops, double bytes) {
+    a.Whi = w.hi;
+    a.Wlo = w.lo;
+    a.out_scale = w.inv_scale;
+    a.terms = c.precision == 2 ? 2 : 3;
+    a.co_scheduled = c.dual && a.epilogue != kEpiPosConv;  // never set for the positional conv, whose launch takes no tile choice from it
     a.splitk_ws = c.splitk;
-    const double nb = (double)nb1 * nb2;
-    const double flops = 2.0 * M * (double)N * K * nb;
-    const double bytes = 4.0 * (nb * ((double)M * K + (double)M * N * (epi == kEpiResidual ? 2 : 1)) + (double)N * K);
     Bracket br(e, s, kid, flops, bytes);
     HIP_TRY(launch_gemm_split(a, s));
+    return LOCO_OK;
+}
+int run_gemm_split(loco_encoder* e, const Call& c, hipStream_t s, const GemmSplitArgs& a, const SplitW& w) {
+    return run_gemm_split(e, c, s, a, w, K_GEMM_SPLIT, gemm_flops(a.M, a.N, a.K, a.nb1, a.nb2),
+                          gemm_bytes(a.M, a.N, a.K, a.nb1, a.nb2, a.epilogue));
+}
+
+int absmax_host(loco_encoder* e, const float* src, size_t n, hipStream_t s, float& out) {
+    HIP_TRY(hipMemsetAsync(e->absmax_dev, 0, sizeof(float), s));
+    HIP_TRY(launch_absmax(src, (long)n, e->absmax_dev, s));
+    HIP_TRY(hipMemcpyAsync(&out, e->absmax_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return LOCO_OK;
 }
 
@@ -373,11 +402,8 @@ int run_gemm_split(loco_encoder* e, const Call& c, hipStream_t s, const _Float16
 int make_split(loco_encoder* e, SplitW& w, const float* src, size_t n, hipStream_t s) {
     if (!w.hi) HIP_TRY(hipMalloc(&w.hi, n * sizeof(_Float16)));
     if (!w.lo) HIP_TRY(hipMalloc(&w.lo, n * sizeof(_Float16)));
-    HIP_TRY(hipMemsetAsync(e->absmax_dev, 0, sizeof(float), s));
-    HIP_TRY(launch_absmax(src, (long)n, e->absmax_dev, s));
     float amax = 0.f;
-    HIP_TRY(hipMemcpyAsync(&amax, e->absmax_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = absmax_host(e, src, n, s, amax)) return rc;
     int k = 0;
     if (amax > 0.f && amax < INFINITY) {
         int ex = 0;
@@ -387,14 +413,6 @@ int make_split(loco_encoder* e, SplitW& w, const float* src, size_t n, hipStream
     }
     w.inv_scale = ldexpf(1.0f, -k);
     HIP_TRY(launch_split_f16(src, w.hi, w.lo, (long)n, s, ldexpf(1.0f, k)));
-    return LOCO_OK;
-}
-
-int absmax_host(loco_encoder* e, const float* src, size_t n, hipStream_t s, float& out) {
-    HIP_TRY(hipMemsetAsync(e->absmax_dev, 0, sizeof(float), s));
-    HIP_TRY(launch_absmax(src, (long)n, e->absmax_dev, s));
-    HIP_TRY(hipMemcpyAsync(&out, e->absmax_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     return LOCO_OK;
 }
 
@@ -420,8 +438,6 @@ int static_range_check(loco_encoder* e, const std::string& ln_prefix, int dim, h
     return LOCO_OK;
 }
 
-bool nl_is_zero(const loco_encoder* e) { return e->cfg.layers == 0; }
-
 // Diagnostics, off unless the environment had LOCO_DEBUG_NONFINITE=1 when the handle was created: after each stage of the f16x3
 // forward, count the non-finite elements of what it wrote (host synchronisation per stage!) and name the FIRST stage that produced
 // any on stderr.  The range words cannot see NaNs (fmaxf drops them); this can.
@@ -436,6 +452,16 @@ int dbg_check(loco_encoder* e, hipStream_t s, const char* stage, int layer, cons
         fprintf(stderr, "[loco debug] non-finite values: %llu of %zu elements written by '%s' (layer %d); first at element %llu = row %llu, column %llu\n",
                 h[0], n, stage, layer, h[1], row_len ? h[1] / row_len : 0ull, row_len ? h[1] % row_len : 0ull);
     return LOCO_OK;
+}
+// the hi, then the lo plane of one tensor of n elements; `stage` holds one %s for "hi" / "lo"
+void dbg_planes(loco_encoder* e, hipStream_t s, const char* stage, int layer, const _Float16* hi, const _Float16* lo, size_t n,
+                long row_len) {
+    if (!e->debug_nonfinite) return;
+    char name[96];
+    snprintf(name, sizeof name, stage, "hi");
+    dbg_check(e, s, name, layer, hi, n, true, row_len);
+    snprintf(name, sizeof name, stage, "lo");
+    dbg_check(e, s, name, layer, lo, n, true, row_len);
 }
 
 int run_copy(loco_encoder* e, hipStream_t s, float* dst, const float* src, size_t n) {
@@ -489,98 +515,109 @@ struct Bufs {
     const float* sin_tab = nullptr;  // the sinusoid table this forward reads (a snapshot: ensure_sin_rows)
 };
 
+// The start of every (half-)batch: its buffers at the plan's offsets in its workspace (frames_or_null, which depends on the mask,
+// is the caller's), its split-K workspace, and its walk of the range slots from slot 0.
+Bufs carve_bufs(Call& c, const Plan& p, char* ws, int32_t* out_frames) {
+    auto f32 = [ws](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    c.splitk = p.splitk ? f32(p.off_splitk) : nullptr;
+    c.nslot = 0;
+    return {out_frames ? out_frames : reinterpret_cast<int32_t*>(ws + p.off_frames), nullptr, f32(p.off_a), f32(p.off_b), f32(p.off_x0),
+            f32(p.off_x1), f32(p.off_tmp), f32(p.off_ctx), f32(p.off_qkv), f32(p.off_qp), f32(p.off_ffn),
+            reinterpret_cast<_Float16*>(ws + p.off_xs0), reinterpret_cast<_Float16*>(ws + p.off_xs1), ws + p.off_c0scratch};
+}
+
+// conv layer 0 + GroupNorm + GELU (HF :484-494) of one (half-)batch: fp32 y, or the planes yhi / ylo
+int run_conv0(loco_encoder* e, hipStream_t s, const Plan& p, const float* wav, const Bufs& bf, float* y, _Float16* yhi, _Float16* ylo,
+              float* range_slot) {
+    const double outb = 4.0 * p.B * (double)p.Tc[0] * kConvDim;
+    Bracket br(e, s, K_CONV0, 2.0 * 10 * p.B * (double)p.Tc[0] * kConvDim, outb + 8.0 * p.B * (double)p.L);
+    HIP_TRY(launch_conv0_gn_gelu(wav, p.B, p.L, e->conv_w[0], e->stem.conv0_norm.w, e->stem.conv0_norm.b, y, bf.c0scratch, e->cfg.ln_eps, s,
+                                 yhi, ylo, range_slot, bf.t0_clip));
+    return LOCO_OK;
+}
+
+// a fp32 buffer of n elements holds the two fp16 planes of n elements back to back
+void planes(float* base, size_t n, _Float16*& hi, _Float16*& lo) {
+    hi = reinterpret_cast<_Float16*>(base);
+    lo = hi + n;
+}
+
 // ---- precision 0: every contraction on the exact-fp32 MFMA ------------------------------------------------------
-// skip_prenet: x0 already holds the encoder's input hidden states (the text front end wrote them)
-int forward_f32(loco_encoder* e, const Plan& p, const float* wav, float* out, float* const* hidden_states, const Bufs& bf,
-                hipStream_t s, bool skip_prenet = false) {
+// prenet: waveform -> x0, the encoder's input hidden states
+int prenet_f32(loco_encoder* e, const Plan& p, const float* wav, const Bufs& bf, hipStream_t s) {
     const int B = p.B;
-    const long L = p.L;
-    const int T = (int)p.T;
     const long M = p.M;
+    const StemW& sw = e->stem;
     int rc;
-    float *bufA = bf.bufA, *bufB = bf.bufB, *x0 = bf.x0, *x1 = bf.x1, *tmp = bf.tmp, *ctx = bf.ctx, *qkv = bf.qkv, *qp = bf.qp,
-          *ffn = bf.ffn;
-    const int32_t* frames_or_null = bf.frames_or_null;
-    const std::string pn = "prenet.", we = "wrapped_encoder.";
-    if (!skip_prenet) {
     // ---- feature encoder (HF :484-494)
-    {
-        const double outb = 4.0 * B * (double)p.Tc[0] * kConvDim;
-        Bracket br(e, s, K_CONV0, 2.0 * 10 * B * (double)p.Tc[0] * kConvDim, outb + 8.0 * B * (double)L);
-        HIP_TRY(launch_conv0_gn_gelu(wav, B, L, e->conv_w[0], W(e, pn + "feature_encoder.conv_layers.0.layer_norm.weight"),
-                                     W(e, pn + "feature_encoder.conv_layers.0.layer_norm.bias"), bufA,
-                                     bf.c0scratch, e->cfg.ln_eps, s, nullptr, nullptr, nullptr, bf.t0_clip));
-    }
-    float* cin = bufA;
-    float* cout = bufB;
+    if ((rc = run_conv0(e, s, p, wav, bf, bf.bufA, nullptr, nullptr, nullptr))) return rc;
+    float* cin = bf.bufA;
+    float* cout = bf.bufB;
     for (int i = 1; i < 7; ++i) {
         const long Tin = p.Tc[i - 1], Tout = p.Tc[i];
         rc = run_gemm(e, s, cin, (long)kConvS[i] * kConvDim, e->conv_w[i], (long)kConvK[i] * kConvDim, nullptr, nullptr, 0,
                       cout, kConvDim, (int)Tout, kConvDim, kConvK[i] * kConvDim, kEpiGelu, B, 1, Tin * kConvDim, 0,
                       Tout * kConvDim, 0);
         if (rc) return rc;
-        float* t = cin;
-        cin = cout;
-        cout = t;
+        std::swap(cin, cout);
     }
     float* feats = cin;  // [M,512]
     if (e->tap_conv && (rc = run_copy(e, s, e->tap_conv, feats, (size_t)M * kConvDim))) return rc;
 
     // ---- feature projection (HF :498-510): LayerNorm(512) in place, then Linear(512,768)
-    if ((rc = run_ln(e, s, feats, W(e, pn + "feature_projection.layer_norm.weight"),
-                     W(e, pn + "feature_projection.layer_norm.bias"), feats, M, kConvDim)))
-        return rc;
-    if ((rc = run_gemm(e, s, feats, kConvDim, W(e, pn + "feature_projection.projection.weight"), kConvDim,
-                       W(e, pn + "feature_projection.projection.bias"), nullptr, 0, x1, kHidden, (int)M, kHidden, kConvDim,
+    if ((rc = run_ln(e, s, feats, sw.proj_norm.w, sw.proj_norm.b, feats, M, kConvDim))) return rc;
+    if ((rc = run_gemm(e, s, feats, kConvDim, sw.proj.w, kConvDim, sw.proj.b, nullptr, 0, bf.x1, kHidden, (int)M, kHidden, kConvDim,
                        kEpiNone)))
         return rc;
-    if (e->tap_proj && (rc = run_copy(e, s, e->tap_proj, x1, (size_t)M * kHidden))) return rc;
+    if (e->tap_proj && (rc = run_copy(e, s, e->tap_proj, bf.x1, (size_t)M * kHidden))) return rc;
 
     // ---- positional conv + sinusoid (HF :555-564)
     {
         Bracket br(e, s, K_POSCONV, 2.0 * M * (double)kHidden * kPosCg * kPosK, 8.0 * M * kHidden);
-        HIP_TRY(launch_pos_conv(x1, e->pos_w, W(e, pn + "pos_conv_embed.conv.bias"), bf.sin_tab, frames_or_null, x0, B, T, s, bf.rows_clip));
+        HIP_TRY(launch_pos_conv(bf.x1, e->pos_w, sw.pos_b, bf.sin_tab, bf.frames_or_null, bf.x0, B, (int)p.T, s, bf.rows_clip));
     }
-    if (e->tap_prenet && (rc = run_copy(e, s, e->tap_prenet, x0, (size_t)M * kHidden))) return rc;
-    }  // !skip_prenet
+    if (e->tap_prenet && (rc = run_copy(e, s, e->tap_prenet, bf.x0, (size_t)M * kHidden))) return rc;
+    return LOCO_OK;
+}
 
-    // ---- encoder (HF :1276-1304)
-    if ((rc = run_ln(e, s, x0, W(e, we + "layer_norm.weight"), W(e, we + "layer_norm.bias"), x0, M, kHidden))) return rc;
-    const float* pe_k = W(e, we + "embed_positions.pe_k.weight");
+// encoder (HF :1276-1304): x0 -> out, and the hidden states the caller asked for
+int encoder_f32(loco_encoder* e, const Plan& p, float* out, float* const* hidden_states, const Bufs& bf, hipStream_t s) {
+    const int B = p.B;
+    const int T = (int)p.T;
+    const long M = p.M;
+    int rc;
+    float *x0 = bf.x0, *x1 = bf.x1, *tmp = bf.tmp, *ctx = bf.ctx, *qkv = bf.qkv, *qp = bf.qp, *ffn = bf.ffn;
+    if ((rc = run_ln(e, s, x0, e->stem.layer_norm.w, e->stem.layer_norm.b, x0, M, kHidden))) return rc;
     const int nl = e->cfg.layers;
     for (int l = 0; l < nl; ++l) {
         if (hidden_states && hidden_states[l] && (rc = run_copy(e, s, hidden_states[l], x0, (size_t)M * kHidden))) return rc;
-        const std::string b = we + "layers." + std::to_string(l) + ".";
         const LayerW& lw = e->layers[l];
         // fused q|k|v projection, q pre-scaled (HF :891,911-914)
         if ((rc = run_gemm(e, s, x0, kHidden, lw.wqkv, kHidden, lw.bqkv, nullptr, 0, qkv, kQkv, (int)M, kQkv, kHidden, kEpiNone)))
             return rc;
         // Qp[b,h] = q_scaled[b,:,h,:] pe_k^T  -> [B,12,T,320]
-        if ((rc = run_gemm(e, s, qkv, kQkv, pe_k, kHeadDim, nullptr, nullptr, 0, qp, kRelN, T, kRelN, kHeadDim, kEpiNone, B,
+        if ((rc = run_gemm(e, s, qkv, kQkv, e->stem.pe_k, kHeadDim, nullptr, nullptr, 0, qp, kRelN, T, kRelN, kHeadDim, kEpiNone, B,
                            kHeads, (long)T * kQkv, kHeadDim, (long)kHeads * T * kRelN, (long)T * kRelN)))
             return rc;
         {
             const double tt = (double)T * T;
             Bracket br(e, s, K_ATTN, 4.0 * B * kHeads * tt * kHeadDim, 4.0 * (M * (double)(kQkv + kHidden) + M * (double)kHeads * kRelN));
-            HIP_TRY(launch_attention(qkv, qp, frames_or_null, ctx, B, T, s));
+            HIP_TRY(launch_attention(qkv, qp, bf.frames_or_null, ctx, B, T, s));
         }
         // out_proj + residual (HF :984,1056), LayerNorm (HF :1058)
-        if ((rc = run_gemm(e, s, ctx, kHidden, W(e, b + "attention.out_proj.weight"), kHidden, W(e, b + "attention.out_proj.bias"),
-                           x0, kHidden, tmp, kHidden, (int)M, kHidden, kHidden, kEpiResidual)))
-            return rc;
-        if ((rc = run_ln(e, s, tmp, W(e, b + "layer_norm.weight"), W(e, b + "layer_norm.bias"), x1, M, kHidden))) return rc;
-        // FFN (HF :1003-1010) + residual + final LayerNorm (HF :1059-1060)
-        if ((rc = run_gemm(e, s, x1, kHidden, W(e, b + "feed_forward.intermediate_dense.weight"), kHidden,
-                           W(e, b + "feed_forward.intermediate_dense.bias"), nullptr, 0, ffn, e->cfg.ffn, (int)M, e->cfg.ffn,
-                           kHidden, kEpiGelu)))
-            return rc;
-        if ((rc = run_gemm(e, s, ffn, e->cfg.ffn, W(e, b + "feed_forward.output_dense.weight"), e->cfg.ffn,
-                           W(e, b + "feed_forward.output_dense.bias"), x1, kHidden, tmp, kHidden, (int)M, kHidden, e->cfg.ffn,
+        if ((rc = run_gemm(e, s, ctx, kHidden, lw.out_proj.w, kHidden, lw.out_proj.b, x0, kHidden, tmp, kHidden, (int)M, kHidden, kHidden,
                            kEpiResidual)))
             return rc;
-        float* dst = (l == nl - 1) ? out : x0;
-        if ((rc = run_ln(e, s, tmp, W(e, b + "final_layer_norm.weight"), W(e, b + "final_layer_norm.bias"), dst, M, kHidden)))
+        if ((rc = run_ln(e, s, tmp, lw.layer_norm.w, lw.layer_norm.b, x1, M, kHidden))) return rc;
+        // FFN (HF :1003-1010) + residual + final LayerNorm (HF :1059-1060)
+        if ((rc = run_gemm(e, s, x1, kHidden, lw.ffn_in.w, kHidden, lw.ffn_in.b, nullptr, 0, ffn, e->cfg.ffn, (int)M, e->cfg.ffn, kHidden,
+                           kEpiGelu)))
             return rc;
+        if ((rc = run_gemm(e, s, ffn, e->cfg.ffn, lw.ffn_out.w, e->cfg.ffn, lw.ffn_out.b, x1, kHidden, tmp, kHidden, (int)M, kHidden,
+                           e->cfg.ffn, kEpiResidual)))
+            return rc;
+        float* dst = (l == nl - 1) ? out : x0;
+        if ((rc = run_ln(e, s, tmp, lw.final_layer_norm.w, lw.final_layer_norm.b, dst, M, kHidden))) return rc;
     }
     if (nl == 0 && (rc = run_copy(e, s, out, x0, (size_t)M * kHidden))) return rc;
     if (hidden_states && hidden_states[nl] && (rc = run_copy(e, s, hidden_states[nl], out, (size_t)M * kHidden))) return rc;
@@ -590,150 +627,113 @@ int forward_f32(loco_encoder* e, const Plan& p, const float* wav, float* out, fl
 // ---- precision 1: every contraction (conv layers 1-6, feature projection, positional conv, QKV / out / FFN projections, the
 // Qp table, QK^T and PV) on the fp16 x3 split MFMA; every producer writes the fp16 hi/lo planes its consumer needs, so no
 // separate conversion pass exists.  conv0 (10 taps, VALU), residuals, GroupNorm / LayerNorm statistics and softmax stay fp32.
-int forward_f16x3(loco_encoder* e, Call& c, const Plan& p, const float* wav, float* out, float* const* hidden_states, const Bufs& bf,
-                  hipStream_t s, bool skip_prenet = false) {
+int prenet_f16x3(loco_encoder* e, Call& c, const Plan& p, const float* wav, const Bufs& bf, hipStream_t s) {
     const int B = p.B;
-    const long L = p.L;
     const int T = (int)p.T;
     const long M = p.M;
+    const StemW& sw = e->stem;
     int rc;
-    float *x0 = bf.x0, *x1 = bf.x1, *tmp = bf.tmp, *qp = bf.qp;
-    const int32_t* frames_or_null = bf.frames_or_null;
-    const std::string pn = "prenet.", we = "wrapped_encoder.";
-    // q / k / v as fp16 hi|lo planes [M,768] carved from the qkv region (attention clamps the key rows of its last tile to T - 1
-    // and multiplies them by P = 0: nothing to pad or to zero)
-    _Float16* qshi = reinterpret_cast<_Float16*>(bf.qkv);
-    _Float16* qslo = qshi + (size_t)M * kHidden;
-    // planes in the order q_hi, q_lo, k_hi, k_lo, v_hi, v_lo: the k and v pairs sit 2 M 768 halves behind the pair before them
-    _Float16* const kshi = qslo + (size_t)M * kHidden;
-    _Float16* const kslo = kshi + (size_t)M * kHidden;
-    _Float16* const vshi = kslo + (size_t)M * kHidden;
-    _Float16* const vslo = vshi + (size_t)M * kHidden;
-    GemmSplitArgs scat{};
-    scat.qkv_stride = (long)2 * M * kHidden;
-    scat.T = T;
-    // a fp32 buffer of n elements holds the two fp16 planes of n elements back to back
-    auto planes = [](float* base, size_t n, _Float16*& hi, _Float16*& lo) {
-        hi = reinterpret_cast<_Float16*>(base);
-        lo = hi + n;
-    };
-    // range tracking: one status word (x 8 shards) per tensor that is stored as fp16 planes and whose range does not follow from
-    // the weights alone (loco_kernels.h), in launch order; the two halves of a dual-stream forward walk the same sequence and
-    // share the words (a maximum does not care who contributes)
-    int nslot = 0;
-    auto slot = [&](const char* name, int layer = -1) -> float* {
-        if (!c.range_dev || !c.st || nslot >= kFiniteStage) return nullptr;
-        c.st->names[nslot] = name;
-        c.st->layer[nslot] = layer;
-        return c.range_dev + (size_t)kRangeShards * nslot++;
-    };
     static const char* const kConvNames[7] = {"feature_encoder.conv_layers.0 (GroupNorm + GELU)", "feature_encoder.conv_layers.1",
                                               "feature_encoder.conv_layers.2", "feature_encoder.conv_layers.3",
                                               "feature_encoder.conv_layers.4", "feature_encoder.conv_layers.5",
                                               "feature_encoder.conv_layers.6"};
-
-    if (!skip_prenet) {
     // ---- feature encoder: conv0 writes planes, conv1-5 planes -> planes, conv6 planes -> fp32 (LayerNorm input)
     _Float16 *ihi, *ilo, *ohi, *olo;
     planes(bf.bufA, (size_t)B * p.Tc[0] * kConvDim, ihi, ilo);
-    {
-        const double outb = 4.0 * B * (double)p.Tc[0] * kConvDim;
-        Bracket br(e, s, K_CONV0, 2.0 * 10 * B * (double)p.Tc[0] * kConvDim, outb + 8.0 * B * (double)L);
-        HIP_TRY(launch_conv0_gn_gelu(wav, B, L, e->conv_w[0], W(e, pn + "feature_encoder.conv_layers.0.layer_norm.weight"),
-                                     W(e, pn + "feature_encoder.conv_layers.0.layer_norm.bias"), nullptr, bf.c0scratch,
-                                     e->cfg.ln_eps, s, ihi, ilo, slot(kConvNames[0]), bf.t0_clip));
-    }
+    if ((rc = run_conv0(e, s, p, wav, bf, nullptr, ihi, ilo, c.slot(kConvNames[0])))) return rc;
     float* cin = bf.bufA;
     float* cout = bf.bufB;
     for (int i = 1; i < 7; ++i) {
         const long Tin = p.Tc[i - 1], Tout = p.Tc[i];
         planes(cin, (size_t)B * Tin * kConvDim, ihi, ilo);
         planes(cout, (size_t)B * Tout * kConvDim, ohi, olo);
-        const bool last = i == 6;
-        rc = run_gemm_split(e, c, s, ihi, ilo, (long)kConvS[i] * kConvDim, e->conv_s[i], (long)kConvK[i] * kConvDim, nullptr, nullptr, 0,
-                            last ? cout : nullptr, last ? nullptr : ohi, last ? nullptr : olo, kConvDim, (int)Tout, kConvDim,
-                            kConvK[i] * kConvDim, kEpiGelu, B, Tin * kConvDim, Tout * kConvDim, 1, 0, 0, nullptr, nullptr, nullptr,
-                            last ? nullptr : slot(kConvNames[i]), K_GEMM_SPLIT, kConvK[i]);
-        if (rc) return rc;
-        float* t = cin;
-        cin = cout;
-        cout = t;
+        GemmSplitArgs a = split_args(Tout, kConvDim, kConvK[i] * kConvDim, kEpiGelu);
+        a.Ahi = ihi; a.Alo = ilo; a.lda = (long)kConvS[i] * kConvDim; a.ktaps = kConvK[i];
+        a.nb1 = B; a.sA1 = Tin * kConvDim; a.sC1 = Tout * kConvDim;
+        if (i == 6) {
+            a.C = cout;
+        } else {
+            a.Chi = ohi; a.Clo = olo;
+            a.range_slot = c.slot(kConvNames[i]);
+        }
+        if ((rc = run_gemm_split(e, c, s, a, e->conv_s[i]))) return rc;
+        std::swap(cin, cout);
     }
     float* feats = cin;  // [M,512] fp32
     if (e->tap_conv && (rc = run_copy(e, s, e->tap_conv, feats, (size_t)M * kConvDim))) return rc;
 
     // ---- feature projection: LayerNorm(512) -> planes (in the idle conv buffer) -> Linear(512,768) -> x1 fp32
     planes(cout, (size_t)M * kConvDim, ohi, olo);
-    if ((rc = run_ln(e, s, feats, W(e, pn + "feature_projection.layer_norm.weight"), W(e, pn + "feature_projection.layer_norm.bias"),
-                     nullptr, M, kConvDim, ohi, olo)))
-        return rc;
-    if ((rc = run_gemm_split(e, c, s, ohi, olo, kConvDim, e->proj_s, kConvDim, W(e, pn + "feature_projection.projection.bias"), nullptr, 0,
-                             x1, nullptr, nullptr, kHidden, (int)M, kHidden, kConvDim, kEpiNone)))
-        return rc;
-    if (e->tap_proj && (rc = run_copy(e, s, e->tap_proj, x1, (size_t)M * kHidden))) return rc;
+    if ((rc = run_ln(e, s, feats, sw.proj_norm.w, sw.proj_norm.b, nullptr, M, kConvDim, ohi, olo))) return rc;
+    GemmSplitArgs a = split_args(M, kHidden, kConvDim, kEpiNone);
+    a.Ahi = ohi; a.Alo = olo; a.bias = sw.proj.b; a.C = bf.x1;
+    if ((rc = run_gemm_split(e, c, s, a, e->proj_s))) return rc;
+    if (e->tap_proj && (rc = run_copy(e, s, e->tap_proj, bf.x1, (size_t)M * kHidden))) return rc;
 
     // ---- positional conv + sinusoid as ONE split GEMM per (clip, group): x1 is re-laid group-major with a 64-frame zero
     // halo, so that output frame t reads the contiguous run of 128 taps x 48 channels (lda = 48, K = 6144); the epilogue
     // fuses bias, GELU, the residual x1 and the sinusoidal-position gather (HF :389-397,555-564)
+    _Float16* ghi = reinterpret_cast<_Float16*>(bf.ffn);  // scratch: the FFN buffer is idle until the first layer
+    _Float16* glo = ghi + (size_t)B * kPosGroups * (T + kPosK) * kPosCg;
     {
-        _Float16* ghi = reinterpret_cast<_Float16*>(bf.ffn);  // scratch: the FFN buffer is idle until the first layer
-        _Float16* glo = ghi + (size_t)B * kPosGroups * (T + kPosK) * kPosCg;
-        {
-            Bracket br(e, s, K_COPY, 0.0, 8.0 * M * kHidden);
-            HIP_TRY(launch_group_major_split(x1, ghi, glo, B, T, s, slot("feature_projection (input of pos_conv_embed)"), bf.rows_clip));
-        }
-        GemmSplitArgs a{};
-        a.Ahi = ghi; a.Alo = glo; a.Whi = e->posg_s.hi; a.Wlo = e->posg_s.lo;
-        a.bias = W(e, pn + "pos_conv_embed.conv.bias");
-        a.R = x1; a.C = x0;
-        a.M = T; a.N = kPosCg; a.K = kPosK * kPosCg;
-        a.lda = kPosCg; a.ldw = (long)kPosK * kPosCg; a.ldc = kHidden; a.ldr = kHidden;
-        a.nb1 = B; a.nb2 = kPosGroups;
-        a.sA1 = (long)kPosGroups * (T + kPosK) * kPosCg; a.sA2 = (long)(T + kPosK) * kPosCg;
-        a.sC1 = (long)T * kHidden; a.sC2 = kPosCg;
-        a.sW2 = (long)kPosCg * kPosK * kPosCg; a.sBias2 = kPosCg;
-        a.epilogue = kEpiPosConv;
-        a.out_scale = e->posg_s.inv_scale;
-        a.terms = c.precision == 2 ? 2 : 3;
-        a.sin_table = bf.sin_tab; a.frames = frames_or_null; a.T = T;
-        a.splitk_ws = c.splitk;  // one or two short clips: split-K over the taps (launch_gemm_split)
-        Bracket br(e, s, K_POSCONV_SPLIT, 2.0 * M * (double)kHidden * kPosCg * kPosK, 8.0 * M * kHidden);
-        HIP_TRY(launch_gemm_split(a, s));
+        Bracket br(e, s, K_COPY, 0.0, 8.0 * M * kHidden);
+        HIP_TRY(launch_group_major_split(bf.x1, ghi, glo, B, T, s, c.slot("feature_projection (input of pos_conv_embed)"), bf.rows_clip));
     }
-    if (e->tap_prenet && (rc = run_copy(e, s, e->tap_prenet, x0, (size_t)M * kHidden))) return rc;
-    }  // !skip_prenet
+    a = split_args(T, kPosCg, kPosK * kPosCg, kEpiPosConv);
+    a.Ahi = ghi; a.Alo = glo; a.bias = sw.pos_b; a.R = bf.x1; a.C = bf.x0;
+    a.lda = kPosCg; a.ldc = kHidden; a.ldr = kHidden;
+    a.nb1 = B; a.nb2 = kPosGroups;
+    a.sA1 = (long)kPosGroups * (T + kPosK) * kPosCg; a.sA2 = (long)(T + kPosK) * kPosCg;
+    a.sC1 = (long)T * kHidden; a.sC2 = kPosCg;
+    a.sW2 = (long)kPosCg * kPosK * kPosCg; a.sBias2 = kPosCg;
+    a.sin_table = bf.sin_tab; a.frames = bf.frames_or_null; a.T = T;
+    if ((rc = run_gemm_split(e, c, s, a, e->posg_s, K_POSCONV_SPLIT, 2.0 * M * (double)kHidden * kPosCg * kPosK, 8.0 * M * kHidden)))
+        return rc;
+    if (e->tap_prenet && (rc = run_copy(e, s, e->tap_prenet, bf.x0, (size_t)M * kHidden))) return rc;
+    return LOCO_OK;
+}
 
-    // ---- encoder
-    _Float16 *x0hi = bf.xs0, *x0lo = bf.xs0 + (size_t)M * kHidden;
-    _Float16 *x1hi = bf.xs1, *x1lo = bf.xs1 + (size_t)M * kHidden;
+int encoder_f16x3(loco_encoder* e, Call& c, const Plan& p, float* out, float* const* hidden_states, const Bufs& bf, hipStream_t s) {
+    const int B = p.B;
+    const int T = (int)p.T;
+    const long M = p.M;
+    const int F = e->cfg.ffn;
+    const size_t MH = (size_t)M * kHidden;
+    int rc;
+    float *x0 = bf.x0, *tmp = bf.tmp;
+    // q / k / v as fp16 hi|lo planes [M,768] carved from the qkv region (attention clamps the key rows of its last tile to T - 1
+    // and multiplies them by P = 0: nothing to pad or to zero)
+    _Float16* qshi = reinterpret_cast<_Float16*>(bf.qkv);
+    _Float16* qslo = qshi + MH;
+    // planes in the order q_hi, q_lo, k_hi, k_lo, v_hi, v_lo: the k and v pairs sit 2 M 768 halves behind the pair before them
+    _Float16* const kshi = qslo + MH;
+    _Float16* const kslo = kshi + MH;
+    _Float16* const vshi = kslo + MH;
+    _Float16* const vslo = vshi + MH;
+    _Float16 *x0hi = bf.xs0, *x0lo = bf.xs0 + MH;
+    _Float16 *x1hi = bf.xs1, *x1lo = bf.xs1 + MH;
     _Float16 *chi, *clo, *fhi, *flo;
-    planes(bf.ctx, (size_t)M * kHidden, chi, clo);
-    planes(bf.ffn, (size_t)M * e->cfg.ffn, fhi, flo);
+    planes(bf.ctx, MH, chi, clo);
+    planes(bf.ffn, (size_t)M * F, fhi, flo);
     // Between layers the residual stream exists only as its fp16 hi/lo planes (22 bits): they are what the next GEMM reads
     // as its A operand anyway, and the residual adds reconstruct hi + lo exactly.  An fp32 copy is written only where
     // somebody reads one: hidden-state outputs, the zero-layer configuration, and the final output.
-    float* x0f = (hidden_states || nl_is_zero(e)) ? x0 : nullptr;
-    if ((rc = run_ln(e, s, x0, W(e, we + "layer_norm.weight"), W(e, we + "layer_norm.bias"), x0f, M, kHidden, x0hi, x0lo))) return rc;
     const int nl = e->cfg.layers;
+    float* x0f = (hidden_states || nl == 0) ? x0 : nullptr;
+    if ((rc = run_ln(e, s, x0, e->stem.layer_norm.w, e->stem.layer_norm.b, x0f, M, kHidden, x0hi, x0lo))) return rc;
     for (int l = 0; l < nl; ++l) {
-        if (hidden_states && hidden_states[l] && (rc = run_copy(e, s, hidden_states[l], x0, (size_t)M * kHidden))) return rc;
-        const std::string b = we + "layers." + std::to_string(l) + ".";
+        if (hidden_states && hidden_states[l] && (rc = run_copy(e, s, hidden_states[l], x0, MH))) return rc;
         const LayerW& lw = e->layers[l];
         // fused q|k|v projection -> q, k and v as fp16 hi/lo planes [M,768] (the layout attention_f16x3 reads; it transposes V itself)
-        if ((rc = run_gemm_split(e, c, s, x0hi, x0lo, kHidden, lw.sqkv, kHidden, lw.bqkv, nullptr, 0, nullptr, qshi, qslo, kHidden, (int)M,
-                                 kQkv, kHidden, kEpiQkvScatter, 1, 0, 0, 1, 0, 0, &scat, nullptr, nullptr,
-                                 slot("attention q|k|v projections", l))))
-            return rc;
-        if (e->debug_nonfinite) {
-            dbg_check(e, s, "x0 planes hi (layer input)", l, x0hi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "x0 planes lo (layer input)", l, x0lo, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "q planes hi", l, qshi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "q planes lo", l, qslo, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "k planes hi", l, kshi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "k planes lo", l, kslo, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "v planes hi", l, vshi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "v planes lo", l, vslo, (size_t)M * kHidden, true, kHidden);
-        }
+        GemmSplitArgs a = split_args(M, kQkv, kHidden, kEpiQkvScatter);
+        a.Ahi = x0hi; a.Alo = x0lo; a.bias = lw.bqkv;
+        a.Chi = qshi; a.Clo = qslo; a.ldc = kHidden; a.qkv_stride = (long)2 * M * kHidden; a.T = T;
+        a.range_slot = c.slot("attention q|k|v projections", l);
+        if ((rc = run_gemm_split(e, c, s, a, lw.sqkv))) return rc;
+        dbg_planes(e, s, "x0 planes %s (layer input)", l, x0hi, x0lo, MH, kHidden);
+        dbg_planes(e, s, "q planes %s", l, qshi, qslo, MH, kHidden);
+        dbg_planes(e, s, "k planes %s", l, kshi, kslo, MH, kHidden);
+        dbg_planes(e, s, "v planes %s", l, vshi, vslo, MH, kHidden);
         // Qp[b,h] = q_scaled[b,:,h,:] pe_k^T -> fp32 [B,12,T,320] is computed INSIDE the attention kernel (attention_f16x3.hip,
         // TABLE form): `qp` is scratch of that launch; no table GEMM runs any more.
         {
@@ -742,45 +742,44 @@ int forward_f16x3(loco_encoder* e, Call& c, const Plan& p, const float* wav, flo
             // algorithmic bytes: q|k|v in, context out -- the table is now an internal scratch of the launch, not compulsory traffic
             Bracket br(e, s, K_ATTN_SPLIT, 4.0 * B * kHeads * tt * kHeadDim + 2.0 * M * (double)kHeads * kRelN * kHeadDim,
                        4.0 * (M * (double)(kQkv + kHidden)));
-            HIP_TRY(launch_attention_f16x3(qshi, qslo, kshi, kslo, vshi, vslo, qp, frames_or_null, chi, clo, nullptr, B, T,
+            HIP_TRY(launch_attention_f16x3(qshi, qslo, kshi, kslo, vshi, vslo, bf.qp, bf.frames_or_null, chi, clo, nullptr, B, T,
                                            s, e->pe_s.hi, e->pe_s.lo, e->pe_s.inv_scale));
         }
-        if (e->debug_nonfinite) {
-            dbg_check(e, s, "attention context planes hi", l, chi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "attention context planes lo", l, clo, (size_t)M * kHidden, true, kHidden);
-        }
-        if ((rc = run_gemm_split(e, c, s, chi, clo, kHidden, lw.so, kHidden, W(e, b + "attention.out_proj.bias"), nullptr, kHidden, tmp, nullptr,
-                                 nullptr, kHidden, (int)M, kHidden, kHidden, kEpiResidual, 1, 0, 0, 1, 0, 0, nullptr, x0hi, x0lo)))
-            return rc;
-        dbg_check(e, s, "out_proj + residual (fp32)", l, tmp, (size_t)M * kHidden, false, kHidden);
-        if ((rc = run_ln(e, s, tmp, W(e, b + "layer_norm.weight"), W(e, b + "layer_norm.bias"), nullptr, M, kHidden, x1hi, x1lo))) return rc;
-        if (e->debug_nonfinite) {
-            dbg_check(e, s, "layer_norm planes hi", l, x1hi, (size_t)M * kHidden, true, kHidden);
-            dbg_check(e, s, "layer_norm planes lo", l, x1lo, (size_t)M * kHidden, true, kHidden);
-        }
-        if ((rc = run_gemm_split(e, c, s, x1hi, x1lo, kHidden, lw.s1, kHidden, W(e, b + "feed_forward.intermediate_dense.bias"), nullptr, 0,
-                                 nullptr, fhi, flo, e->cfg.ffn, (int)M, e->cfg.ffn, kHidden, kEpiGelu, 1, 0, 0, 1, 0, 0, nullptr, nullptr,
-                                 nullptr, slot("feed_forward intermediate (GELU)", l))))
-            return rc;
-        if (e->debug_nonfinite) {
-            dbg_check(e, s, "feed_forward intermediate planes hi", l, fhi, (size_t)M * e->cfg.ffn, true, e->cfg.ffn);
-            dbg_check(e, s, "feed_forward intermediate planes lo", l, flo, (size_t)M * e->cfg.ffn, true, e->cfg.ffn);
-        }
-        if ((rc = run_gemm_split(e, c, s, fhi, flo, e->cfg.ffn, lw.s2, e->cfg.ffn, W(e, b + "feed_forward.output_dense.bias"), nullptr, kHidden,
-                                 tmp, nullptr, nullptr, kHidden, (int)M, kHidden, e->cfg.ffn, kEpiResidual, 1, 0, 0, 1, 0, 0, nullptr, x1hi,
-                                 x1lo)))
-            return rc;
-        dbg_check(e, s, "feed_forward output + residual (fp32)", l, tmp, (size_t)M * kHidden, false, kHidden);
+        dbg_planes(e, s, "attention context planes %s", l, chi, clo, MH, kHidden);
+        // out_proj + residual, LayerNorm
+        a = split_args(M, kHidden, kHidden, kEpiResidual);
+        a.Ahi = chi; a.Alo = clo; a.bias = lw.out_proj.b;
+        a.Rhi = x0hi; a.Rlo = x0lo; a.ldr = kHidden; a.C = tmp;
+        if ((rc = run_gemm_split(e, c, s, a, lw.so))) return rc;
+        dbg_check(e, s, "out_proj + residual (fp32)", l, tmp, MH, false, kHidden);
+        if ((rc = run_ln(e, s, tmp, lw.layer_norm.w, lw.layer_norm.b, nullptr, M, kHidden, x1hi, x1lo))) return rc;
+        dbg_planes(e, s, "layer_norm planes %s", l, x1hi, x1lo, MH, kHidden);
+        // FFN + residual + final LayerNorm
+        a = split_args(M, F, kHidden, kEpiGelu);
+        a.Ahi = x1hi; a.Alo = x1lo; a.bias = lw.ffn_in.b;
+        a.Chi = fhi; a.Clo = flo; a.range_slot = c.slot("feed_forward intermediate (GELU)", l);
+        if ((rc = run_gemm_split(e, c, s, a, lw.s1))) return rc;
+        dbg_planes(e, s, "feed_forward intermediate planes %s", l, fhi, flo, (size_t)M * F, F);
+        a = split_args(M, kHidden, F, kEpiResidual);
+        a.Ahi = fhi; a.Alo = flo; a.bias = lw.ffn_out.b;
+        a.Rhi = x1hi; a.Rlo = x1lo; a.ldr = kHidden; a.C = tmp;
+        if ((rc = run_gemm_split(e, c, s, a, lw.s2))) return rc;
+        dbg_check(e, s, "feed_forward output + residual (fp32)", l, tmp, MH, false, kHidden);
         const bool last = l == nl - 1;
-        if ((rc = run_ln(e, s, tmp, W(e, b + "final_layer_norm.weight"), W(e, b + "final_layer_norm.bias"),
-                         last ? out : (hidden_states ? x0 : nullptr), M, kHidden, last ? nullptr : x0hi, last ? nullptr : x0lo,
+        if ((rc = run_ln(e, s, tmp, lw.final_layer_norm.w, lw.final_layer_norm.b, last ? out : (hidden_states ? x0 : nullptr), M, kHidden,
+                         last ? nullptr : x0hi, last ? nullptr : x0lo,
                          last && c.range_dev ? c.range_dev + (size_t)kRangeShards * kFiniteStage : nullptr)))
             return rc;
     }
-    if (nl == 0 && (rc = run_copy(e, s, out, x0, (size_t)M * kHidden))) return rc;
-    if (hidden_states && hidden_states[nl] && (rc = run_copy(e, s, hidden_states[nl], out, (size_t)M * kHidden))) return rc;
-    if (c.st) c.st->used = nslot;
+    if (nl == 0 && (rc = run_copy(e, s, out, x0, MH))) return rc;
+    if (hidden_states && hidden_states[nl] && (rc = run_copy(e, s, hidden_states[nl], out, MH))) return rc;
+    if (c.st) c.st->used = c.nslot;
     return LOCO_OK;
+}
+
+// the encoder stack of the call's precision family, on the x0 a prenet (speech or text) wrote
+int encoder_stack(loco_encoder* e, Call& c, const Plan& p, float* out, float* const* hidden_states, const Bufs& bf, hipStream_t s) {
+    return c.precision >= 1 ? encoder_f16x3(e, c, p, out, hidden_states, bf, s) : encoder_f32(e, p, out, hidden_states, bf, s);
 }
 
 // The status words travel to pinned host memory behind the forward, on its stream: readable once the stream has got there.
@@ -798,6 +797,63 @@ int range_end(const Call& c, hipStream_t s) {
     if (c.precision >= 1 && c.st->used > 0)  // all of them (3 KiB): the tracked stages and the reserved finite-check word
         HIP_TRY(hipMemcpyAsync(c.st->words, c.range_dev, sizeof(float) * kRangeShards * kRangeMaxStages, hipMemcpyDeviceToHost, s));
     return LOCO_OK;
+}
+
+// The enqueue of every forward around its body half(c, part, ws, stream), which enqueues one (half-)batch from its workspace
+// `ws`: part 0 is the whole batch on the caller's stream or, with `dual`, its first half; part 1 is the second half on the side
+// stream.  Here: the Call, the status block's range words, and the fork and join of the side stream.
+template <class Half>
+int enqueue(loco_encoder* e, int precision, StatusBlock* st, void* workspace, hipStream_t s, bool dual, const Half& half) {
+    Call c;
+    c.precision = precision;
+    c.st = st;
+    c.range_dev = reinterpret_cast<float*>(workspace);
+    char* ws = reinterpret_cast<char*>(workspace) + kStatusDevBytes;
+    int rc = range_begin(e, c, s);
+    if (rc) return rc;
+    if (!dual) {
+        rc = half(c, 0, ws, s);
+        return rc ? rc : range_end(c, s);
+    }
+
+    // The side stream is one per handle: forwards in flight together take turns on it (the lock covers the enqueue only).
+    std::lock_guard<std::mutex> lock(e->side_mu);
+    if (!e->side) {
+        HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+    }
+    HIP_TRY(hipEventRecord(e->ev_fork, s));  // the side stream starts after everything already queued on the caller's stream
+    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    // From here on the side stream may hold work that reads the caller's buffers and the workspace: whatever fails below, the
+    // caller's stream is joined to it before this function returns, so that "stream idle" still means "workspace free".
+    c.dual = true;
+    rc = half(c, 0, ws, s);
+    if (!rc) rc = half(c, 1, ws, e->side);  // it walks the same range slots as the first half (carve_bufs)
+    c.dual = false;
+    // a failed half has set loco_last_error; nothing below overwrites it
+    const hipError_t j1 = hipEventRecord(e->ev_join, e->side);  // ... and the caller's stream continues after both halves
+    const hipError_t j2 = j1 == hipSuccess ? hipStreamWaitEvent(s, e->ev_join, 0) : j1;
+    if (j2 != hipSuccess) {
+        // the join itself failed: block until the side stream has drained rather than hand back a workspace in use
+        (void)hipStreamSynchronize(e->side);
+        if (!rc) return fail(LOCO_E_HIP, "loco_forward: joining the second stream failed: %s", hipGetErrorString(j2));
+    }
+    return rc ? rc : range_end(c, s);
+}
+
+// What the loco_forward*_async entries share around run(mode, st): the precision and the status block are checked, and the
+// block is no valid status until the enqueue has succeeded.
+template <class Run>
+int with_status(const loco_encoder* e, const char* fn, int precision, void* status, const Run& run) {
+    if (precision != -1 && !loco_precision_name(precision))
+        return fail(LOCO_E_INVALID, "%s: precision must be -1 (the handle's mode) or one of " LOCO_PRECISION_MODES, fn);
+    if (reinterpret_cast<uintptr_t>(status) & 7) return fail(LOCO_E_INVALID, "%s: the status block must be 8-byte aligned", fn);
+    StatusBlock* st = reinterpret_cast<StatusBlock*>(status);
+    st->magic = 0;  // not a valid status until the enqueue has succeeded
+    const int rc = run(precision < 0 ? e->precision : precision, st);
+    if (rc) st->magic = 0;
+    return rc;
 }
 
 }  // namespace
@@ -869,7 +925,7 @@ loco_encoder* loco_create(const loco_config* cfg) {
 
 void loco_destroy(loco_encoder* e) {
     if (!e) return;
-    for (auto& kv : e->raw) (void)hipFree(kv.second.d);
+    for (auto& kv : e->raw) (void)hipFree(kv.second);
     for (int i = 1; i < 7; ++i) (void)hipFree(e->conv_w[i]);
     (void)hipFree(e->pos_w);
     auto free_split = [](SplitW& w) {
@@ -965,10 +1021,9 @@ int loco_set_weight(loco_encoder* e, const char* key, const float* data, const i
         for (auto s : it->second) want += std::to_string(s) + ",";
         return fail(LOCO_E_INVALID, "size mismatch for %s: got [%s] expected [%s]", key, got.c_str(), want.c_str());
     }
-    Tensor& t = e->raw[k];
-    if (!t.d) HIP_TRY(hipMalloc(&t.d, (size_t)n * sizeof(float)));
-    t.shape = shp;
-    HIP_TRY(hipMemcpy(t.d, data, (size_t)n * sizeof(float), hipMemcpyDefault));
+    float*& d = e->raw[k];
+    if (!d) HIP_TRY(hipMalloc(&d, (size_t)n * sizeof(float)));
+    HIP_TRY(hipMemcpy(d, data, (size_t)n * sizeof(float), hipMemcpyDefault));
     HIP_TRY(hipStreamSynchronize(nullptr));  // device-to-device copies may return early; the caller may free `data` now
     e->finalized = false;
     return LOCO_OK;
@@ -1017,26 +1072,38 @@ int loco_finalize_weights(loco_encoder* e, void* stream) {
         HIP_TRY(launch_relayout_conv_weight(W(e, p + "feature_encoder.conv_layers." + std::to_string(i) + ".conv.weight"),
                                             e->conv_w[i], kConvDim, kConvDim, kConvK[i], s));
     }
+    StemW& sw = e->stem;
     if (speech) {
-        e->conv_w[0] = e->raw.at(p + "feature_encoder.conv_layers.0.conv.weight").d;
+        sw.conv0_norm = weight_bias(e, p + "feature_encoder.conv_layers.0.layer_norm.");
+        sw.proj_norm = weight_bias(e, p + "feature_projection.layer_norm.");
+        sw.proj = weight_bias(e, p + "feature_projection.projection.");
+        sw.pos_b = W(e, p + "pos_conv_embed.conv.bias");
+        e->conv_w[0] = e->raw.at(p + "feature_encoder.conv_layers.0.conv.weight");
         // positional conv: fold weight-norm, lay out [group][tap][o][i]
         if (!e->pos_w) HIP_TRY(hipMalloc(&e->pos_w, (size_t)kHidden * kPosCg * kPosK * sizeof(float)));
         HIP_TRY(launch_fold_pos_conv(W(e, p + "pos_conv_embed.conv.parametrizations.weight.original0"),
                                      W(e, p + "pos_conv_embed.conv.parametrizations.weight.original1"), e->pos_w, s));
     }
     // fused QKV with the 1/8 query scaling folded in: (x Wq^T + bq)/8 == x (Wq/8)^T + bq/8 exactly (power of two)
+    sw.layer_norm = weight_bias(e, w + "layer_norm.");
+    sw.pe_k = W(e, w + "embed_positions.pe_k.weight");
     const size_t hh = (size_t)kHidden * kHidden;
     for (int l = 0; l < e->cfg.layers; ++l) {
         LayerW& lw = e->layers[l];
-        const std::string b = w + "layers." + std::to_string(l) + ".attention.";
+        const std::string b = w + "layers." + std::to_string(l) + ".", a = b + "attention.";
         if (!lw.wqkv) HIP_TRY(hipMalloc(&lw.wqkv, 3 * hh * sizeof(float)));
         if (!lw.bqkv) HIP_TRY(hipMalloc(&lw.bqkv, 3 * kHidden * sizeof(float)));
-        HIP_TRY(launch_scale_copy(W(e, b + "q_proj.weight"), lw.wqkv, hh, 0.125f, s));
-        HIP_TRY(launch_scale_copy(W(e, b + "k_proj.weight"), lw.wqkv + hh, hh, 1.0f, s));
-        HIP_TRY(launch_scale_copy(W(e, b + "v_proj.weight"), lw.wqkv + 2 * hh, hh, 1.0f, s));
-        HIP_TRY(launch_scale_copy(W(e, b + "q_proj.bias"), lw.bqkv, kHidden, 0.125f, s));
-        HIP_TRY(launch_scale_copy(W(e, b + "k_proj.bias"), lw.bqkv + kHidden, kHidden, 1.0f, s));
-        HIP_TRY(launch_scale_copy(W(e, b + "v_proj.bias"), lw.bqkv + 2 * kHidden, kHidden, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "q_proj.weight"), lw.wqkv, hh, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "k_proj.weight"), lw.wqkv + hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "v_proj.weight"), lw.wqkv + 2 * hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "q_proj.bias"), lw.bqkv, kHidden, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "k_proj.bias"), lw.bqkv + kHidden, kHidden, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, a + "v_proj.bias"), lw.bqkv + 2 * kHidden, kHidden, 1.0f, s));
+        lw.out_proj = weight_bias(e, a + "out_proj.");
+        lw.layer_norm = weight_bias(e, b + "layer_norm.");
+        lw.ffn_in = weight_bias(e, b + "feed_forward.intermediate_dense.");
+        lw.ffn_out = weight_bias(e, b + "feed_forward.output_dense.");
+        lw.final_layer_norm = weight_bias(e, b + "final_layer_norm.");
     }
     // fp16 hi/lo planes of every GEMM weight for precision mode f16x3 (378 MB; built unconditionally so that the
     // mode can be switched per forward)
@@ -1051,8 +1118,8 @@ int loco_finalize_weights(loco_encoder* e, void* stream) {
         (void)hipFree(tmpw);
         if (he != hipSuccess) return fail(LOCO_E_HIP, "permute_conv_k: %s", hipGetErrorString(he));
     }
-    if (speech && !rc) rc = make_split(e, e->proj_s, W(e, p + "feature_projection.projection.weight"), (size_t)kHidden * kConvDim, s);
-    if (!rc) rc = make_split(e, e->pe_s, W(e, w + "embed_positions.pe_k.weight"), (size_t)kRelN * kHeadDim, s);
+    if (speech && !rc) rc = make_split(e, e->proj_s, sw.proj.w, (size_t)kHidden * kConvDim, s);
+    if (!rc) rc = make_split(e, e->pe_s, sw.pe_k, (size_t)kRelN * kHeadDim, s);
     if (speech && !rc) {  // positional conv weight re-laid [g][o][tap*48+i] for the conv-as-GEMM form, then split
         float* tmpw = nullptr;
         const size_t n = (size_t)kHidden * kPosCg * kPosK;
@@ -1065,11 +1132,10 @@ int loco_finalize_weights(loco_encoder* e, void* stream) {
     }
     for (int l = 0; l < e->cfg.layers && !rc; ++l) {
         LayerW& lw = e->layers[l];
-        const std::string b = w + "layers." + std::to_string(l) + ".";
         rc = make_split(e, lw.sqkv, lw.wqkv, 3 * hh, s);
-        if (!rc) rc = make_split(e, lw.so, W(e, b + "attention.out_proj.weight"), hh, s);
-        if (!rc) rc = make_split(e, lw.s1, W(e, b + "feed_forward.intermediate_dense.weight"), (size_t)e->cfg.ffn * kHidden, s);
-        if (!rc) rc = make_split(e, lw.s2, W(e, b + "feed_forward.output_dense.weight"), (size_t)e->cfg.ffn * kHidden, s);
+        if (!rc) rc = make_split(e, lw.so, lw.out_proj.w, hh, s);
+        if (!rc) rc = make_split(e, lw.s1, lw.ffn_in.w, (size_t)e->cfg.ffn * kHidden, s);
+        if (!rc) rc = make_split(e, lw.s2, lw.ffn_out.w, (size_t)e->cfg.ffn * kHidden, s);
     }
     if (rc) return rc;
     if (speech) {
@@ -1151,31 +1217,20 @@ int loco_set_taps(loco_encoder* e, float* conv_stack, float* feature_projection,
 }
 
 namespace {
-// clip_tab: null, or (loco_forward_packed) the host table {conv0 frames [B], encoder frames [B]} of THIS (half-)batch's clips
-int forward_one(loco_encoder* e, Call& c, const Plan& p, const float* wav, const int32_t* mask, int B, long L, float* out, int32_t* out_frames,
-                float* const* hidden_states, char* ws, hipStream_t s, const int32_t* clip_t0 = nullptr, const int32_t* clip_rows = nullptr,
-                const int32_t* clip_valid = nullptr, const float* sin_tab = nullptr) {
-    int32_t* frames = out_frames ? out_frames : reinterpret_cast<int32_t*>(ws + p.off_frames);
-    float* bufA = reinterpret_cast<float*>(ws + p.off_a);
-    float* bufB = reinterpret_cast<float*>(ws + p.off_b);
-    float* x0 = reinterpret_cast<float*>(ws + p.off_x0);
-    float* x1 = reinterpret_cast<float*>(ws + p.off_x1);
-    float* tmp = reinterpret_cast<float*>(ws + p.off_tmp);
-    float* ctx = reinterpret_cast<float*>(ws + p.off_ctx);
-    float* qkv = reinterpret_cast<float*>(ws + p.off_qkv);
-    float* qp = reinterpret_cast<float*>(ws + p.off_qp);
-    float* ffn = reinterpret_cast<float*>(ws + p.off_ffn);
-
+// One (half-)batch of a speech forward: frame counts, the packed forward's clip tables, prenet and encoder stack.
+// clip_t0 / clip_rows / clip_valid: null, or (loco_forward_packed) the host tables of THIS (half-)batch's clips
+int forward_speech(loco_encoder* e, Call& c, const Plan& p, const float* wav, const int32_t* mask, float* out, int32_t* out_frames,
+                   float* const* hidden_states, char* ws, hipStream_t s, const int32_t* clip_t0, const int32_t* clip_rows,
+                   const int32_t* clip_valid, const float* sin_tab) {
+    const int B = p.B;
+    Bufs bf = carve_bufs(c, p, ws, out_frames);
     // ---- valid frame counts (HF :569-598); a packed forward that was given valid_len has them from the host (below)
     if (!clip_valid) {
-        Bracket br(e, s, K_FRAMES, 0.0, mask ? 4.0 * B * (double)L : 0.0);
-        HIP_TRY(launch_frame_counts(mask, B, L, frames, s));
+        Bracket br(e, s, K_FRAMES, 0.0, mask ? 4.0 * B * (double)p.L : 0.0);
+        HIP_TRY(launch_frame_counts(mask, B, p.L, bf.frames, s));
     }
-    const int32_t* frames_or_null = mask ? frames : nullptr;
-
-    struct Bufs bufs{frames, frames_or_null, bufA, bufB, x0, x1, tmp, ctx, qkv, qp, ffn, reinterpret_cast<_Float16*>(ws + p.off_xs0),
-                     reinterpret_cast<_Float16*>(ws + p.off_xs1), ws + p.off_c0scratch};
-    bufs.sin_tab = sin_tab;
+    bf.frames_or_null = mask ? bf.frames : nullptr;
+    bf.sin_tab = sin_tab;
     if (clip_t0) {
         // packed forward: the per-clip tables follow the stream into the workspace; without a mask every sample of a clip's own
         // reference batch counts, so its valid frames are that batch's frames (and a key mask is needed whatever the caller passed:
@@ -1183,14 +1238,14 @@ int forward_one(loco_encoder* e, Call& c, const Plan& p, const float* wav, const
         int32_t* tab = reinterpret_cast<int32_t*>(ws + p.off_clip);
         HIP_TRY(hipMemcpyAsync(tab, clip_t0, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(tab + B, clip_rows, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (clip_valid) HIP_TRY(hipMemcpyAsync(frames, clip_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        else if (!mask) HIP_TRY(hipMemcpyAsync(frames, tab + B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        bufs.frames_or_null = frames;
-        bufs.t0_clip = tab;
-        bufs.rows_clip = tab + B;
+        if (clip_valid) HIP_TRY(hipMemcpyAsync(bf.frames, clip_valid, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        else if (!mask) HIP_TRY(hipMemcpyAsync(bf.frames, tab + B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        bf.frames_or_null = bf.frames;
+        bf.t0_clip = tab;
+        bf.rows_clip = tab + B;
     }
-    c.splitk = p.splitk ? reinterpret_cast<float*>(ws + p.off_splitk) : nullptr;
-    return c.precision >= 1 ? forward_f16x3(e, c, p, wav, out, hidden_states, bufs, s) : forward_f32(e, p, wav, out, hidden_states, bufs, s);
+    const int rc = c.precision >= 1 ? prenet_f16x3(e, c, p, wav, bf, s) : prenet_f32(e, p, wav, bf, s);
+    return rc ? rc : encoder_stack(e, c, p, out, hidden_states, bf, s);
 }
 
 // One forward in arithmetic mode `precision`, its range words in the first bytes of the workspace, its status in `st`.  Nothing
@@ -1238,52 +1293,16 @@ int forward_impl(loco_encoder* e, int precision, StatusBlock* st, const float* w
         tab_rows = st->clip_tab + B;
         if (valid_len) tab_valid = st->clip_tab + 2 * B;
     }
-    Call c;
-    c.precision = precision;
-    c.st = st;
-    c.range_dev = reinterpret_cast<float*>(workspace);
-    char* ws = reinterpret_cast<char*>(workspace) + kStatusDevBytes;
-    if ((rc = range_begin(e, c, s))) return rc;
-    if (!dual) {
-        rc = forward_one(e, c, p, wav, mask, B, L, out, out_frames, hidden_states, ws, s, tab_t0, tab_rows, tab_valid, sin_tab);
-        if (rc) return rc;
-        return range_end(c, s);
-    }
-
-    // The side stream is one per handle: forwards in flight together take turns on it (the lock covers the enqueue only).
-    std::lock_guard<std::mutex> lock(e->side_mu);
-    if (!e->side) {
-        HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    }
-    const int B0 = (B + 1) / 2, B1 = B - B0;
-    HIP_TRY(hipEventRecord(e->ev_fork, s));  // the side stream starts after everything already queued on the caller's stream
-    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    // From here on the side stream may hold work that reads the caller's buffers and the workspace: whatever fails below, the
-    // caller's stream is joined to it before this function returns, so that "stream idle" still means "workspace free".
-    c.dual = true;
-    rc = forward_one(e, c, p0, wav, mask, B0, L, out, out_frames, nullptr, ws, s, tab_t0, tab_rows, tab_valid, sin_tab);
-    int rc1 = LOCO_OK;
-    std::string first_error;
-    if (rc) first_error = g_err;
-    else rc1 = forward_one(e, c, p1, wav + (size_t)B0 * L, mask ? mask + (size_t)B0 * L : nullptr, B1, L, out + (size_t)B0 * p.T * kHidden,
-                           out_frames ? out_frames + B0 : nullptr, nullptr, ws + p0.total, e->side, tab_t0 ? tab_t0 + B0 : nullptr,
-                           tab_rows ? tab_rows + B0 : nullptr, tab_valid ? tab_valid + B0 : nullptr, sin_tab);
-    c.dual = false;
-    if (!rc && rc1) first_error = g_err;
-    const hipError_t j1 = hipEventRecord(e->ev_join, e->side);  // ... and the caller's stream continues after both halves
-    const hipError_t j2 = j1 == hipSuccess ? hipStreamWaitEvent(s, e->ev_join, 0) : j1;
-    if (j2 != hipSuccess) {
-        // the join itself failed: block until the side stream has drained rather than hand back a workspace in use
-        (void)hipStreamSynchronize(e->side);
-        if (!rc && !rc1) return fail(LOCO_E_HIP, "loco_forward: joining the second stream failed: %s", hipGetErrorString(j2));
-    }
-    if (rc || rc1) {
-        g_err = first_error;
-        return rc ? rc : rc1;
-    }
-    return range_end(c, s);
+    return enqueue(e, precision, st, workspace, s, dual, [&](Call& c, int part, char* ws, hipStream_t hs) {
+        if (part == 0)
+            return forward_speech(e, c, dual ? p0 : p, wav, mask, out, out_frames, hidden_states, ws, hs, tab_t0, tab_rows, tab_valid,
+                                  sin_tab);
+        const int B0 = p0.B;  // the second half starts B0 clips into every per-clip input and output
+        auto skip = [B0](const int32_t* tab) { return tab ? tab + B0 : nullptr; };
+        return forward_speech(e, c, p1, wav + (size_t)B0 * L, mask ? mask + (size_t)B0 * L : nullptr, out + (size_t)B0 * p.T * kHidden,
+                              out_frames ? out_frames + B0 : nullptr, nullptr, ws + p0.total, hs, skip(tab_t0), skip(tab_rows),
+                              skip(tab_valid), sin_tab);
+    });
 }
 
 const StatusBlock* as_status(const void* status) {
@@ -1353,15 +1372,9 @@ int loco_forward_async(loco_encoder* e, int precision, const float* wav, const i
                        int32_t* out_frames, float* const* hidden_states, void* workspace, size_t workspace_bytes, void* stream,
                        void* status) {
     if (!e || !status) return fail(LOCO_E_INVALID, "loco_forward_async: null argument");
-    if (precision != -1 && !loco_precision_name(precision))
-        return fail(LOCO_E_INVALID, "loco_forward_async: precision must be -1 (the handle's mode) or one of " LOCO_PRECISION_MODES);
-    if (reinterpret_cast<uintptr_t>(status) & 7) return fail(LOCO_E_INVALID, "loco_forward_async: the status block must be 8-byte aligned");
-    StatusBlock* st = reinterpret_cast<StatusBlock*>(status);
-    st->magic = 0;  // not a valid status until the enqueue has succeeded
-    const int rc = forward_impl(e, precision < 0 ? e->precision : precision, st, wav, mask, B, L, out, out_frames, hidden_states, workspace,
-                                workspace_bytes, stream);
-    if (rc) st->magic = 0;
-    return rc;
+    return with_status(e, "loco_forward_async", precision, status, [&](int mode, StatusBlock* st) {
+        return forward_impl(e, mode, st, wav, mask, B, L, out, out_frames, hidden_states, workspace, workspace_bytes, stream);
+    });
 }
 
 int loco_forward_packed(loco_encoder* e, int precision, const float* wav, const int32_t* mask, const int64_t* valid_len, int32_t B, int64_t L,
@@ -1369,15 +1382,10 @@ int loco_forward_packed(loco_encoder* e, int precision, const float* wav, const 
                         size_t workspace_bytes, void* stream, void* status) {
     if (!e || !status || !pad_len) return fail(LOCO_E_INVALID, "loco_forward_packed: null argument");
     if (mask && valid_len) return fail(LOCO_E_INVALID, "loco_forward_packed: give attention_mask or valid_len, not both");
-    if (precision != -1 && !loco_precision_name(precision))
-        return fail(LOCO_E_INVALID, "loco_forward_packed: precision must be -1 (the handle's mode) or one of " LOCO_PRECISION_MODES);
-    if (reinterpret_cast<uintptr_t>(status) & 7) return fail(LOCO_E_INVALID, "loco_forward_packed: the status block must be 8-byte aligned");
-    StatusBlock* st = reinterpret_cast<StatusBlock*>(status);
-    st->magic = 0;
-    const int rc = forward_impl(e, precision < 0 ? e->precision : precision, st, wav, mask, B, L, out, out_frames, hidden_states, workspace,
-                                workspace_bytes, stream, pad_len, valid_len);
-    if (rc) st->magic = 0;
-    return rc;
+    return with_status(e, "loco_forward_packed", precision, status, [&](int mode, StatusBlock* st) {
+        return forward_impl(e, mode, st, wav, mask, B, L, out, out_frames, hidden_states, workspace, workspace_bytes, stream, pad_len,
+                            valid_len);
+    });
 }
 
 int loco_max_pack_clips(void) { return kMaxPackClips; }
@@ -1452,33 +1460,19 @@ int forward_text_impl(loco_encoder* e, int precision, StatusBlock* st, const int
     if (workspace_bytes < kStatusDevBytes + p.total)
         return fail(LOCO_E_WORKSPACE, "loco_forward_text: workspace %zu < required %zu bytes", workspace_bytes, kStatusDevBytes + p.total);
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(LOCO_E_INVALID, "loco_forward_text: workspace must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    Call c;
-    c.precision = precision;
-    c.st = st;
-    c.range_dev = reinterpret_cast<float*>(workspace);
-    char* ws = reinterpret_cast<char*>(workspace) + kStatusDevBytes;
-    int32_t* frames = out_frames ? out_frames : reinterpret_cast<int32_t*>(ws + p.off_frames);
-    float* x0 = reinterpret_cast<float*>(ws + p.off_x0);
-    int rcb = range_begin(e, c, s);
-    if (rcb) return rcb;
-    {
-        Bracket br(e, s, K_FRAMES, 0.0, attention_mask ? 4.0 * B * (double)T : 0.0);
-        HIP_TRY(launch_token_counts(attention_mask, B, T, frames, s));
-    }
-    {   // embed_tokens + alpha * pe (HF SpeechT5TextEncoderPrenet.forward)
-        Bracket br(e, s, K_COPY, 0.0, 12.0 * p.M * kHidden);
-        HIP_TRY(launch_text_prenet(input_ids, e->text_embed, e->text_vocab, e->text_alpha, e->text_pe, B, T, x0, s));
-    }
-    struct Bufs bufs{frames, attention_mask ? frames : nullptr, reinterpret_cast<float*>(ws + p.off_a), reinterpret_cast<float*>(ws + p.off_b),
-                     x0, reinterpret_cast<float*>(ws + p.off_x1), reinterpret_cast<float*>(ws + p.off_tmp),
-                     reinterpret_cast<float*>(ws + p.off_ctx), reinterpret_cast<float*>(ws + p.off_qkv),
-                     reinterpret_cast<float*>(ws + p.off_qp), reinterpret_cast<float*>(ws + p.off_ffn),
-                     reinterpret_cast<_Float16*>(ws + p.off_xs0), reinterpret_cast<_Float16*>(ws + p.off_xs1), ws + p.off_c0scratch};
-    c.splitk = p.splitk ? reinterpret_cast<float*>(ws + p.off_splitk) : nullptr;
-    const int rc = c.precision >= 1 ? forward_f16x3(e, c, p, nullptr, out, hidden_states, bufs, s, true)
-                                    : forward_f32(e, p, nullptr, out, hidden_states, bufs, s, true);
-    return rc ? rc : range_end(c, s);
+    return enqueue(e, precision, st, workspace, (hipStream_t)stream, false, [&](Call& c, int, char* ws, hipStream_t s) {
+        Bufs bf = carve_bufs(c, p, ws, out_frames);
+        {
+            Bracket br(e, s, K_FRAMES, 0.0, attention_mask ? 4.0 * B * (double)T : 0.0);
+            HIP_TRY(launch_token_counts(attention_mask, B, T, bf.frames, s));
+        }
+        {   // embed_tokens + alpha * pe (HF SpeechT5TextEncoderPrenet.forward)
+            Bracket br(e, s, K_COPY, 0.0, 12.0 * p.M * kHidden);
+            HIP_TRY(launch_text_prenet(input_ids, e->text_embed, e->text_vocab, e->text_alpha, e->text_pe, B, T, bf.x0, s));
+        }
+        bf.frames_or_null = attention_mask ? bf.frames : nullptr;
+        return encoder_stack(e, c, p, out, hidden_states, bf, s);
+    });
 }
 }  // namespace
 
@@ -1492,15 +1486,10 @@ int loco_forward_text_async(loco_encoder* e, int precision, const int32_t* input
                             float* out, int32_t* out_frames, float* const* hidden_states, void* workspace, size_t workspace_bytes,
                             void* stream, void* status) {
     if (!e || !status) return fail(LOCO_E_INVALID, "loco_forward_text_async: null argument");
-    if (precision != -1 && !loco_precision_name(precision))
-        return fail(LOCO_E_INVALID, "loco_forward_text_async: precision must be -1 (the handle's mode) or one of " LOCO_PRECISION_MODES);
-    if (reinterpret_cast<uintptr_t>(status) & 7) return fail(LOCO_E_INVALID, "loco_forward_text_async: the status block must be 8-byte aligned");
-    StatusBlock* st = reinterpret_cast<StatusBlock*>(status);
-    st->magic = 0;
-    const int rc = forward_text_impl(e, precision < 0 ? e->precision : precision, st, input_ids, attention_mask, B, T, out, out_frames, hidden_states,
-                                     workspace, workspace_bytes, stream);
-    if (rc) st->magic = 0;
-    return rc;
+    return with_status(e, "loco_forward_text_async", precision, status, [&](int mode, StatusBlock* st) {
+        return forward_text_impl(e, mode, st, input_ids, attention_mask, B, T, out, out_frames, hidden_states, workspace, workspace_bytes,
+                                 stream);
+    });
 }
 
 // ---- profiling -----------------------------------------------------------------------------------------
