@@ -312,6 +312,18 @@ int loco_set_streams(loco_encoder* enc, int n);
  * copy the conv-stack output [B,T,512], the feature projection [B,T,768] and the prenet output [B,T,768]. */
 int loco_set_taps(loco_encoder* enc, float* conv_stack, float* feature_projection, float* prenet);
 
+/* Attention probabilities (HF output_attentions=True, modeling:930-955).  probs: NULL (unbind), or a host array of n == layers
+ * device pointers, each to fp32 [B,12,T,T] for the batch of the next forward.  Like the taps, a binding stays until it is
+ * cleared: every loco_forward, loco_forward_checked and loco_forward_text of the handle fills it, layer l right after layer l's
+ * attention launch (one attention_probs kernel per layer), with
+ *   P[b,h,i,j] = softmax_j(q_i . k_j + qp[i, clip(i-j)+160]) over the valid keys j < frames[b],  P[b,h,i,j] = 0 exactly for
+ *   j >= frames[b];  padded query rows are written too (a softmax over the valid keys, as HF writes them).
+ * Memory: layers * B * 12 * T^2 * 4 bytes (12 layers of 30 s x 8: 10.3 GB).  While a binding is set, forwards take the single
+ * in-order pass (as hidden states and taps), a range fallback of loco_forward_checked overwrites the buffers with the exact-fp32
+ * re-run, and loco_forward_async, loco_forward_packed and loco_forward_text_async return LOCO_E_STATE.  n != layers:
+ * LOCO_E_INVALID.  The default path (nothing bound) launches no extra kernel. */
+int loco_set_attention_outputs(loco_encoder* enc, float* const* probs, int32_t n);
+
 /* ---- per-kernel timing (bench.py's roofline leg) --------------------------------------------------
  * With profiling on, every kernel launch inside loco_forward is bracketed by hipEvents recorded on the
  * launch stream.  loco_profile_read synchronises those events and returns per-kernel totals since the
@@ -367,6 +379,10 @@ int loco_op_pos_conv(const float* h, const float* w_folded, const float* bias, c
  * heads merged.  Flash-style: no [T,T] tensor is ever formed. */
 int loco_op_attention(const float* qkv, const float* qp, const int32_t* frames, float* ctx, int32_t B, int32_t T,
                       void* stream);
+/* The probabilities of that attention (attention_probs.hip): probs [B,12,T,T] fp32 as loco_set_attention_outputs describes,
+ * qkv / qp / frames as loco_op_attention (frames NULL: every key valid).  Exact-fp32 products. */
+int loco_op_attention_probs(const float* qkv, const float* qp, const int32_t* frames, float* probs, int32_t B, int32_t T,
+                            void* stream);
 
 /* ---- split-precision ("f16x3") operators: fp32-class accuracy at the fp16 matrix-core rate ----------------------
  * x = hi + lo with hi = fp16(x), lo = fp16(x - hi); A W^T ~= Ahi Whi^T + Alo Whi^T + Ahi Wlo^T (gemm_f16x3.hip). */
@@ -414,6 +430,12 @@ int loco_op_attention_f16x3(const void* qhi, const void* qlo, const void* khi, c
 int loco_op_attention_f16x3_pe(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
                                const void* pe_hi, const void* pe_lo, float pe_scale, float* qp_scratch, const int32_t* frames,
                                float* ctx, int32_t B, int32_t T, void* stream);
+/* loco_op_attention_probs on fp16 hi/lo planes of q (pre-scaled) and k, [B*T,768] each, as the QKV projection writes them: terms 3
+ * (Qlo Khi + Qhi Klo + Qhi Khi) or 2 (the Klo term dropped) v_mfma_f32_32x32x16_f16 per product.  qp may be the qp_scratch a
+ * loco_op_attention_f16x3_pe launch with the same frames has just filled: a valid key reads only columns that launch formed, and a
+ * masked key reads no table entry at all. */
+int loco_op_attention_probs_f16x3(const void* qhi, const void* qlo, const void* khi, const void* klo, const float* qp,
+                                  const int32_t* frames, float* probs, int32_t B, int32_t T, int32_t terms, void* stream);
 
 /* ---- intent head: the first consumer of the embeddings ("next" row f-1) --------------------------------------
  * IntentClassifier (/root/reference/speech_text/intent_classifier.py:24-49): pooling over time

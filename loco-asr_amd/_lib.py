@@ -72,6 +72,7 @@ SIGNATURES = {
     "loco_get_precision": (C.c_int, [_vp]),
     "loco_set_streams": (C.c_int, [_vp, C.c_int]),
     "loco_set_taps": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "loco_set_attention_outputs": (C.c_int, [_vp, _vp, _i32]),
     "loco_set_profiling": (C.c_int, [_vp, C.c_int]),
     "loco_set_profiling_filter": (C.c_int, [_vp, C.c_char_p]),
     "loco_profile_reset": (C.c_int, [_vp]),
@@ -84,6 +85,8 @@ SIGNATURES = {
     "loco_op_frame_counts": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "loco_op_pos_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "loco_op_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "loco_op_attention_probs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "loco_op_attention_probs_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "loco_op_split_f16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "loco_gemm_splitk_bytes": (_sz, []),
     "loco_debug_reload_gemm_knobs": (None, []),

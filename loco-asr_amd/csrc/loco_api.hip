@@ -76,10 +76,10 @@ struct StemW {  // the prenet's tensors (bound for a handle with the speech pren
 // Profiling buckets, named after the kernel that runs in them (the two precision modes have their own attention and
 // positional-conv buckets: the f16x3 positional conv IS a gemm_f16x3_dma_kernel launch, but keeps a bucket of its own because
 // its shape -- N = 48, K = 6144, halo layout -- has little in common with the projection GEMMs).
-enum KernelId { K_GEMM = 0, K_ATTN, K_LN, K_CONV0, K_POSCONV, K_FRAMES, K_COPY, K_GEMM_SPLIT, K_ATTN_SPLIT, K_POSCONV_SPLIT, K_COUNT };
+enum KernelId { K_GEMM = 0, K_ATTN, K_LN, K_CONV0, K_POSCONV, K_FRAMES, K_COPY, K_GEMM_SPLIT, K_ATTN_SPLIT, K_POSCONV_SPLIT, K_ATTN_PROBS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"gemm_f32",     "attention_f32", "layernorm",       "conv0_gn_gelu",
                                            "pos_conv_f32", "frame_counts",  "copy",            "gemm_f16x3",
-                                           "attention_f16x3", "pos_conv_f16x3_gemm"};
+                                           "attention_f16x3", "pos_conv_f16x3_gemm", "attention_probs"};
 
 struct ProfRec {
     hipEvent_t a, b;
@@ -156,6 +156,8 @@ struct loco_encoder {
     std::vector<float*> retired;  // tables replaced while forwards may still have been reading them: freed at loco_destroy
     // taps
     float *tap_conv = nullptr, *tap_proj = nullptr, *tap_prenet = nullptr;
+    // attention probabilities (loco_set_attention_outputs): one fp32 [B,12,T,T] buffer per layer, or empty
+    std::vector<float*> attn_probs;
     // text front end (SpeechT5TextEncoderPrenet): optional; a handle may carry the speech prenet, the text prenet or both
     float* text_embed = nullptr;  // [text_vocab, 768]
     int text_vocab = 0;
@@ -580,6 +582,17 @@ int prenet_f32(loco_encoder* e, const Plan& p, const float* wav, const Bufs& bf,
     return LOCO_OK;
 }
 
+// output_attentions: layer l's probabilities into the bound buffer, right after the layer's attention launch (nothing when unbound).
+// The f16 planes use all three MFMA terms in every plane mode, as the attention kernel does for its own QK^T.
+int run_attention_probs(loco_encoder* e, hipStream_t s, const float* qkv, const _Float16* qhi, const _Float16* qlo, const _Float16* khi,
+                        const _Float16* klo, const float* qp, const int32_t* frames, int l, int B, int T) {
+    if (e->attn_probs.empty()) return LOCO_OK;
+    const double tt = (double)B * kHeads * T * (double)T;
+    Bracket br(e, s, K_ATTN_PROBS, 2.0 * 2.0 * tt * kHeadDim, 4.0 * tt);
+    HIP_TRY(launch_attention_probs(qkv, qhi, qlo, khi, klo, qp, frames, e->attn_probs[l], B, T, 3, s));
+    return LOCO_OK;
+}
+
 // encoder (HF :1276-1304): x0 -> out, and the hidden states the caller asked for
 int encoder_f32(loco_encoder* e, const Plan& p, float* out, float* const* hidden_states, const Bufs& bf, hipStream_t s) {
     const int B = p.B;
@@ -604,6 +617,7 @@ int encoder_f32(loco_encoder* e, const Plan& p, float* out, float* const* hidden
             Bracket br(e, s, K_ATTN, 4.0 * B * kHeads * tt * kHeadDim, 4.0 * (M * (double)(kQkv + kHidden) + M * (double)kHeads * kRelN));
             HIP_TRY(launch_attention(qkv, qp, bf.frames_or_null, ctx, B, T, s));
         }
+        if ((rc = run_attention_probs(e, s, qkv, nullptr, nullptr, nullptr, nullptr, qp, bf.frames_or_null, l, B, T))) return rc;
         // out_proj + residual (HF :984,1056), LayerNorm (HF :1058)
         if ((rc = run_gemm(e, s, ctx, kHidden, lw.out_proj.w, kHidden, lw.out_proj.b, x0, kHidden, tmp, kHidden, (int)M, kHidden, kHidden,
                            kEpiResidual)))
@@ -745,6 +759,8 @@ int encoder_f16x3(loco_encoder* e, Call& c, const Plan& p, float* out, float* co
             HIP_TRY(launch_attention_f16x3(qshi, qslo, kshi, kslo, vshi, vslo, bf.qp, bf.frames_or_null, chi, clo, nullptr, B, T,
                                            s, e->pe_s.hi, e->pe_s.lo, e->pe_s.inv_scale));
         }
+        // the table the launch just formed in bf.qp holds every column a valid key reads (include/loco_asr.h)
+        if ((rc = run_attention_probs(e, s, nullptr, qshi, qslo, kshi, kslo, bf.qp, bf.frames_or_null, l, B, T))) return rc;
         dbg_planes(e, s, "attention context planes %s", l, chi, clo, MH, kHidden);
         // out_proj + residual, LayerNorm
         a = split_args(M, kHidden, kHidden, kEpiResidual);
@@ -1216,6 +1232,20 @@ int loco_set_taps(loco_encoder* e, float* conv_stack, float* feature_projection,
     return LOCO_OK;
 }
 
+int loco_set_attention_outputs(loco_encoder* e, float* const* probs, int32_t n) {
+    if (!e) return fail(LOCO_E_INVALID, "null encoder");
+    if (!probs) {
+        e->attn_probs.clear();
+        return LOCO_OK;
+    }
+    if (n != e->cfg.layers)
+        return fail(LOCO_E_INVALID, "loco_set_attention_outputs: %d buffers for %d layers", n, e->cfg.layers);
+    for (int i = 0; i < n; ++i)
+        if (!probs[i]) return fail(LOCO_E_INVALID, "loco_set_attention_outputs: buffer %d is null", i);
+    e->attn_probs.assign(probs, probs + n);
+    return LOCO_OK;
+}
+
 namespace {
 // One (half-)batch of a speech forward: frame counts, the packed forward's clip tables, prenet and encoder stack.
 // clip_t0 / clip_rows / clip_valid: null, or (loco_forward_packed) the host tables of THIS (half-)batch's clips
@@ -1262,8 +1292,9 @@ int forward_impl(loco_encoder* e, int precision, StatusBlock* st, const float* w
         return fail(LOCO_E_INVALID, "loco_forward: batch %d x %lld samples gives no output frame (need >= 400 samples)", B, (long long)L);
     if (B > 65535) return fail(LOCO_E_INVALID, "loco_forward: batch %d > 65535", B);
     if (p.M > 0x7fffffffL / 8) return fail(LOCO_E_INVALID, "loco_forward: B*T = %ld frames is too large", p.M);
-    // per-kernel timing, hidden-state and tap outputs keep the single in-order pass
-    const bool dual = !e->profiling && !hidden_states && !e->tap_conv && !e->tap_proj && !e->tap_prenet && split_batch(e, B, L, p0, p1);
+    // per-kernel timing, hidden-state, tap and attention outputs keep the single in-order pass
+    const bool dual = !e->profiling && !hidden_states && !e->tap_conv && !e->tap_proj && !e->tap_prenet && e->attn_probs.empty() &&
+                      split_batch(e, B, L, p0, p1);
     const size_t need = kStatusDevBytes + (dual ? p0.total + p1.total : p.total);
     if (workspace_bytes < need)
         return fail(LOCO_E_WORKSPACE, "loco_forward: workspace %zu < required %zu bytes", workspace_bytes, need);
@@ -1372,6 +1403,7 @@ int loco_forward_async(loco_encoder* e, int precision, const float* wav, const i
                        int32_t* out_frames, float* const* hidden_states, void* workspace, size_t workspace_bytes, void* stream,
                        void* status) {
     if (!e || !status) return fail(LOCO_E_INVALID, "loco_forward_async: null argument");
+    if (!e->attn_probs.empty()) return fail(LOCO_E_STATE, "loco_forward_async: attention outputs are bound (loco_set_attention_outputs)");
     return with_status(e, "loco_forward_async", precision, status, [&](int mode, StatusBlock* st) {
         return forward_impl(e, mode, st, wav, mask, B, L, out, out_frames, hidden_states, workspace, workspace_bytes, stream);
     });
@@ -1381,6 +1413,7 @@ int loco_forward_packed(loco_encoder* e, int precision, const float* wav, const 
                         const int64_t* pad_len, float* out, int32_t* out_frames, float* const* hidden_states, void* workspace,
                         size_t workspace_bytes, void* stream, void* status) {
     if (!e || !status || !pad_len) return fail(LOCO_E_INVALID, "loco_forward_packed: null argument");
+    if (!e->attn_probs.empty()) return fail(LOCO_E_STATE, "loco_forward_packed: attention outputs are bound (loco_set_attention_outputs)");
     if (mask && valid_len) return fail(LOCO_E_INVALID, "loco_forward_packed: give attention_mask or valid_len, not both");
     return with_status(e, "loco_forward_packed", precision, status, [&](int mode, StatusBlock* st) {
         return forward_impl(e, mode, st, wav, mask, B, L, out, out_frames, hidden_states, workspace, workspace_bytes, stream, pad_len,
@@ -1486,6 +1519,8 @@ int loco_forward_text_async(loco_encoder* e, int precision, const int32_t* input
                             float* out, int32_t* out_frames, float* const* hidden_states, void* workspace, size_t workspace_bytes,
                             void* stream, void* status) {
     if (!e || !status) return fail(LOCO_E_INVALID, "loco_forward_text_async: null argument");
+    if (!e->attn_probs.empty())
+        return fail(LOCO_E_STATE, "loco_forward_text_async: attention outputs are bound (loco_set_attention_outputs)");
     return with_status(e, "loco_forward_text_async", precision, status, [&](int mode, StatusBlock* st) {
         return forward_text_impl(e, mode, st, input_ids, attention_mask, B, T, out, out_frames, hidden_states, workspace, workspace_bytes,
                                  stream);
@@ -1704,6 +1739,21 @@ int loco_op_attention_f16x3_pe(const void* qhi, const void* qlo, const void* khi
     HIP_TRY(launch_attention_f16x3((const _Float16*)qhi, (const _Float16*)qlo, (const _Float16*)khi, (const _Float16*)klo,
                                    (const _Float16*)vhi, (const _Float16*)vlo, qp_scratch, frames, nullptr, nullptr, ctx, B, T,
                                    (hipStream_t)stream, (const _Float16*)pe_hi, (const _Float16*)pe_lo, pe_scale));
+    return LOCO_OK;
+}
+
+int loco_op_attention_probs(const float* qkv, const float* qp, const int32_t* frames, float* probs, int32_t B, int32_t T, void* stream) {
+    if (!qkv || !qp || !probs) return fail(LOCO_E_INVALID, "loco_op_attention_probs: null argument");
+    HIP_TRY(launch_attention_probs(qkv, nullptr, nullptr, nullptr, nullptr, qp, frames, probs, B, T, 3, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_attention_probs_f16x3(const void* qhi, const void* qlo, const void* khi, const void* klo, const float* qp, const int32_t* frames,
+                                  float* probs, int32_t B, int32_t T, int32_t terms, void* stream) {
+    if (!qhi || !qlo || !khi || !klo || !qp || !probs) return fail(LOCO_E_INVALID, "loco_op_attention_probs_f16x3: null argument");
+    if (terms != 2 && terms != 3) return fail(LOCO_E_INVALID, "loco_op_attention_probs_f16x3: terms must be 2 or 3");
+    HIP_TRY(launch_attention_probs(nullptr, (const _Float16*)qhi, (const _Float16*)qlo, (const _Float16*)khi, (const _Float16*)klo, qp,
+                                   frames, probs, B, T, terms, (hipStream_t)stream));
     return LOCO_OK;
 }
 

@@ -289,6 +289,11 @@ hipError_t launch_pos_conv(const float* h, const float* wf, const float* bias, c
                            const int32_t* frames, float* out, int B, int T, hipStream_t s, const int32_t* rows_clip = nullptr);
 hipError_t launch_attention(const float* qkv, const float* qp, const int32_t* frames, float* ctx, int B, int T,
                             hipStream_t s, void* ctx_hi = nullptr, void* ctx_lo = nullptr);
+// attention_probs.hip: P[b,h,i,j] = softmax over the valid keys of q.k + qp (output_attentions), fp32 [B,12,T,T].  Exact-fp32 operands
+// (qkv [B,T,2304], qhi == nullptr) or fp16 hi/lo planes of q and k ([B*T,768], `terms` 3 or 2 MFMA terms); qp as the layer's attention
+// launch left it (include/loco_asr.h, loco_op_attention_probs*).
+hipError_t launch_attention_probs(const float* qkv, const _Float16* qhi, const _Float16* qlo, const _Float16* khi, const _Float16* klo,
+                                  const float* qp, const int32_t* frames, float* probs, int B, int T, int terms, hipStream_t s);
 
 // weight preparation (run once in loco_finalize_weights)
 hipError_t launch_relayout_conv_weight(const float* w, float* out, int N, int C, int k, hipStream_t s);  // [N,C,k]->[N,k*C]

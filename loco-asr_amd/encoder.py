@@ -628,11 +628,13 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
     def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
                 return_dict: Optional[bool] = None, stage_taps: Optional[dict] = None, **kwargs):
+        """HF's SpeechT5Encoder call.  ``output_attentions=True`` also returns ``attentions``: one fp32 [B, 12, T, T] tensor per
+        layer (softmax over the valid keys, masked keys exactly 0; HF modeling_speecht5.py:930-955), formed by a separate kernel
+        after each layer's attention launch -- ``layers * B * 12 * T^2 * 4`` bytes on the input's device (12 layers of 30 s x 8:
+        10.3 GB).  ``return_dict=False`` returns (last_hidden_state, hidden_states, attentions) without the Nones."""
         if self.training:
             raise RuntimeError("the MI355X encoder path is inference-only (the reference calls it under "
                                "model.eval() + torch.no_grad()); call .eval()")
-        if output_attentions:
-            raise NotImplementedError("output_attentions=True: the flash-style attention kernel never forms the [T,T] weights")
         if input_values.dim() != 2:
             raise ValueError(f"input_values must be [batch, samples], got {tuple(input_values.shape)}")
         device = input_values.device
@@ -665,28 +667,42 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             if output_hidden_states:
                 hs = [torch.empty_like(out) for _ in range(self.num_layers + 1)]
                 hs_ptrs = (C.c_void_p * (self.num_layers + 1))(*[t.data_ptr() for t in hs])
-            taps = None
-            if stage_taps is not None:
-                taps = dict(conv_stack=torch.empty((B, T, CONV_DIM), dtype=torch.float32, device=device),
-                            feature_projection=torch.empty_like(out), prenet=torch.empty_like(out))
-                _lib.check(self._lib.loco_set_taps(self._handle, taps["conv_stack"].data_ptr(),
-                                                   taps["feature_projection"].data_ptr(), taps["prenet"].data_ptr()))
+            taps, attn = None, None
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             try:
+                if stage_taps is not None:
+                    taps = dict(conv_stack=torch.empty((B, T, CONV_DIM), dtype=torch.float32, device=device),
+                                feature_projection=torch.empty_like(out), prenet=torch.empty_like(out))
+                    _lib.check(self._lib.loco_set_taps(self._handle, taps["conv_stack"].data_ptr(),
+                                                       taps["feature_projection"].data_ptr(), taps["prenet"].data_ptr()))
+                if output_attentions:
+                    attn = bind_attention_outputs(self._lib, self._handle, self.num_layers, B, T, device)
                 self._forward_call((C.c_void_p(x.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, L,
                                     C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs,
                                     C.c_void_p(self._workspace.data_ptr()), self._workspace.numel()), stream)
             finally:
                 if taps is not None:
                     _lib.check(self._lib.loco_set_taps(self._handle, None, None, None))
+                if attn is not None:
+                    _lib.check(self._lib.loco_set_attention_outputs(self._handle, None, 0))
         if stage_taps is not None:
             stage_taps.update(taps)
             stage_taps["frames"] = frames
         self.last_frames = frames
         hidden = tuple(hs) if hs is not None else None
         if return_dict is False:
-            return tuple(v for v in (out, hidden) if v is not None)
-        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=None)
+            return tuple(v for v in (out, hidden, attn) if v is not None)
+        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=attn)
+
+
+def bind_attention_outputs(lib, handle, layers: int, B: int, T: int, device) -> tuple:
+    """Allocate the per-layer [B, 12, T, T] fp32 probability tensors of output_attentions=True and bind them to the handle
+    (loco_set_attention_outputs); the caller unbinds after the forward.  A zero-layer encoder binds nothing and returns ()."""
+    probs = tuple(torch.empty((B, HEADS, T, T), dtype=torch.float32, device=device) for _ in range(layers))
+    if layers:
+        ptrs = (C.c_void_p * layers)(*[t.data_ptr() for t in probs])
+        _lib.check(lib.loco_set_attention_outputs(handle, ptrs, layers), "loco_set_attention_outputs")
+    return probs
 
 
 class _SpeechT5Core(nn.Module):

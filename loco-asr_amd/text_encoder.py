@@ -19,7 +19,7 @@ from torch import nn
 
 from . import _lib
 from .encoder import (HIDDEN, LAYERS, BaseModelOutput, SpeechT5EncoderMI355X, SpeechT5EncoderWithSpeechPrenetMI355X,
-                      _Ref, _SpeechT5Core, _WeightHolder)
+                      _Ref, _SpeechT5Core, _WeightHolder, bind_attention_outputs)
 
 VOCAB_SIZE = 81           # SpeechT5Config.vocab_size
 MAX_TEXT_POSITIONS = 450  # SpeechT5Config.max_text_positions
@@ -224,10 +224,10 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
     def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
                 return_dict: Optional[bool] = None, **kwargs):
+        """HF's SpeechT5Encoder call on token ids.  ``output_attentions=True``: one fp32 [B, 12, T, T] tensor per layer, as the
+        speech encoder returns them (``layers * B * 12 * T^2 * 4`` bytes); a range fallback re-run overwrites them with its own."""
         if self.training:
             raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
-        if output_attentions:
-            raise NotImplementedError("output_attentions=True: the flash-style attention kernel never forms the [T,T] weights")
         ids = input_values
         device = ids.device
         self._ensure_handle(device)
@@ -249,6 +249,7 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
                 hs = [torch.empty_like(out) for _ in range(self.num_layers + 1)]
                 hs_ptrs = (C.c_void_p * (self.num_layers + 1))(*[t.data_ptr() for t in hs])
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            attn = bind_attention_outputs(self._lib, self._handle, self.num_layers, B, T, device) if output_attentions else None
 
             def launch():
                 _lib.check(self._lib.loco_forward_text(self._handle, C.c_void_p(ids32.data_ptr()),
@@ -257,24 +258,28 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
                                                        C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), stream),
                            "loco_forward_text")
 
-            launch()
-            # numeric range of precision "f16x3" (include/loco_asr.h): same policy as the speech encoder's
-            self.last_range_fallback = False
-            policy = self.range_policy
-            if policy != "off" and self.precision != "f32":
-                torch.cuda.current_stream(device).synchronize()
-                rc = self._lib.loco_forward_status(self._handle, None, 0)
-                if rc != 0:
-                    if policy == "raise":
-                        _lib.check(rc, "loco_forward_text")
-                    _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS["f32"]), "set_precision")
-                    launch()  # the same batch on the exact-fp32 kernels
-                    self.last_range_fallback = True
+            try:
+                launch()
+                # numeric range of precision "f16x3" (include/loco_asr.h): same policy as the speech encoder's
+                self.last_range_fallback = False
+                policy = self.range_policy
+                if policy != "off" and self.precision != "f32":
+                    torch.cuda.current_stream(device).synchronize()
+                    rc = self._lib.loco_forward_status(self._handle, None, 0)
+                    if rc != 0:
+                        if policy == "raise":
+                            _lib.check(rc, "loco_forward_text")
+                        _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS["f32"]), "set_precision")
+                        launch()  # the same batch on the exact-fp32 kernels (it rewrites the bound attention buffers too)
+                        self.last_range_fallback = True
+            finally:
+                if attn is not None:
+                    _lib.check(self._lib.loco_set_attention_outputs(self._handle, None, 0))
         self.last_frames = frames
         hidden = tuple(hs) if hs is not None else None
         if return_dict is False:
-            return tuple(v for v in (out, hidden) if v is not None)
-        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=None)
+            return tuple(v for v in (out, hidden, attn) if v is not None)
+        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=attn)
 
 
 class SpeechT5ForTextToSpeechMI355X(nn.Module):
