@@ -482,6 +482,67 @@ int loco_head_loss_grad_ragged(loco_head* head, const float* store, const int64_
 int loco_head_adam_step(loco_head* head, const float* grads, float lr, float beta1, float beta2, float eps,
                         float weight_decay, void* stream);
 
+/* ---- text decoder: SpeechT5ForSpeechToText's other half (teacher-forced logits, greedy generate) ------------------------------
+ * The reference's notebooks call `model_stt.generate(**audios, max_length=100)` and `model_stt(**audios, decoder_input_ids=ids)`.
+ * SpeechT5DecoderWithTextPrenet (HF modeling_speecht5.py: SpeechT5TextDecoderPrenet -- embed_tokens + sinusoid positions with
+ * padding_idx 1 -- and 6 post-LN SpeechT5DecoderLayer: causal self-attention, cross-attention over the encoder output, erf-GELU
+ * feed-forward) + SpeechT5TextDecoderPostnet (lm_head, no bias).  Weights go through loco_set_weight under HF's names below
+ * "speecht5.": "decoder.prenet.embed_tokens.weight" [V,768], "decoder.wrapped_decoder.layers.N.{self_attn,encoder_attn}.
+ * {q,k,v,out}_proj.{weight,bias}", "...layers.N.{self_attn_layer_norm,encoder_attn_layer_norm,final_layer_norm}.{weight,bias}",
+ * "...layers.N.feed_forward.{intermediate_dense,output_dense}.{weight,bias}", "text_decoder_postnet.lm_head.weight" [V,768]; the
+ * embedding and lm_head are tied in HF: either one suffices, both given are used as given.  Optionally
+ * "decoder.prenet.embed_positions.weights" [>= 452,768] (HF's non-persistent buffer; otherwise generated).  The layer count
+ * follows from the keys.  A handle without any decoder tensor behaves exactly as before; with some of them,
+ * loco_missing_weights names the rest.  Every decoder product is exact fp32 in every precision mode, the cross-attention
+ * k|v projection of the encoder output (M = B * T_enc, the existing fp32 MFMA GEMM) included.
+ *   enc_out      f32 [B, T_enc, 768] the encoder's last_hidden_state (device); enc_frames i32 [B] valid frames per clip (device:
+ *                loco_forward's out_frames) or NULL = all T_enc; cross-attention sees keys j < enc_frames[b]
+ *   workspace    >= loco_decoder_workspace_bytes(enc, B, T_enc, S_max) bytes (device): cross k|v cache [B, T_enc, layers, 1536], self k|v
+ *                cache [layers, B, S_max, 1536], token buffer i32 [B, S_max], per-row state, scratch.  It carries ALL state between
+ *                loco_decoder_begin and the steps, so several utterance batches may be decoded side by side.
+ * Limits: S, S_max, max_length <= 450 (max_text_positions) and, for begin / step / generate, B <= loco_decoder_max_batch() = 64
+ * rows of the weight-streaming GEMM: LOCO_E_INVALID naming the limit.  No decoder weights: LOCO_E_STATE.
+ *   loco_decoder_forward   teacher-forced: decoder_input_ids i32 [B, S] (device) -> logits f32 [B, S, V]; hidden_states NULL or a
+ *                          host array of layers + 1 device pointers f32 [B, S, 768] (inputs of every layer and the last output)
+ *   loco_decoder_begin     cross k|v projection, token buffer := <s> (2) then <pad>, row state reset
+ *   loco_decoder_step      step t (0-based): consumes token t of every row, appends token t + 1 = argmax (lowest index wins ties), <pad>
+ *                          (1) for a row that has emitted </s> (2); logits NULL or f32 [B, V] (device) receiving this step's logits.
+ *                          Asynchronous, no host read, capturable (a linear chain of launches).  Steps must be enqueued in order.
+ *   loco_decoder_read_tokens  enqueue copies of the token buffer [B, S_max] and the row lengths [B] (tokens up to and including </s>)
+ *   loco_decoder_generate  = begin + steps + stream synchronisation, greedy search as HF's generate runs it for this model: stops when
+ *                          every row has emitted </s> (the device's "rows open" word is read through pinned memory every 8 steps) or at
+ *                          max_length tokens (<s> included).  tokens_out i32 [B, max_length] HOST, *out_length = the length HF returns
+ *                          (columns beyond it hold <pad>), lengths_out i32 [B] HOST or NULL, step_logits NULL or f32
+ *                          [max_length - 1, B, V] (device).  Single caller per handle: the pinned word the poll reads belongs to the
+ *                          handle (begin / step / forward keep everything in the workspace and may run side by side).
+ *   loco_has_decoder       1 when the handle holds a COMPLETE set of decoder tensors (loco_missing_weights names what a partial set lacks)
+ *   loco_decoder_workspace_bytes  0 for a handle without a (complete) decoder */
+int loco_has_decoder(const loco_encoder* enc);
+int loco_decoder_max_batch(void);
+size_t loco_decoder_workspace_bytes(const loco_encoder* enc, int32_t B, int32_t T_enc, int32_t S_max);
+int loco_decoder_forward(loco_encoder* enc, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                         const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int loco_decoder_begin(loco_encoder* enc, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, int32_t S_max,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int loco_decoder_step(loco_encoder* enc, int32_t B, int32_t T_enc, int32_t S_max, int32_t t, float* logits, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int loco_decoder_read_tokens(const loco_encoder* enc, int32_t B, int32_t T_enc, int32_t S_max, int32_t* tokens, int32_t* lengths,
+                             const void* workspace, size_t workspace_bytes, void* stream);
+int loco_decoder_generate(loco_encoder* enc, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, int32_t max_length,
+                          int32_t* tokens_out, int32_t* lengths_out, int32_t* out_length, float* step_logits, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* The two new kernels as operators (parity tests).  loco_op_skinny_gemm: loco_op_gemm's contract (epilogues 0 / 1 / 2, dense C) for
+ * M <= 64 rows and K % 256 == 0 on the weight-streaming kernel, any N; LOCO_E_INVALID above 64 rows.  loco_op_decoder_attention:
+ * q [B,Sq,768], k / v [B,Tk,768] (12 heads x 64), out [B,Sq,768] = softmax_j(scale q.k) v over keys j < key_counts[b] (NULL: Tk) and,
+ * when causal != 0, j <= i + causal_offset; long key ranges are split over workgroups and merged in a fixed order (scratch >=
+ * loco_decoder_attention_scratch_bytes). */
+int loco_op_skinny_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* R, int64_t ldr, float* C,
+                        int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* stream);
+size_t loco_decoder_attention_scratch_bytes(int32_t B, int32_t Sq, int32_t Tk);
+int loco_op_decoder_attention(const float* q, const float* k, const float* v, const int32_t* key_counts, float* out, int32_t B, int32_t Sq,
+                              int32_t Tk, int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

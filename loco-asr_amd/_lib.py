@@ -110,6 +110,17 @@ SIGNATURES = {
     "loco_head_forward_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_head_loss_grad_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "loco_head_adam_step": (C.c_int, [_vp, _vp, _f, _f, _f, _f, _f, _vp]),
+    "loco_has_decoder": (C.c_int, [_vp]),
+    "loco_decoder_max_batch": (C.c_int, []),
+    "loco_decoder_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "loco_decoder_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "loco_decoder_begin": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "loco_decoder_step": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "loco_decoder_read_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "loco_decoder_generate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, C.POINTER(_i32), _vp, _vp, _sz, _vp]),
+    "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),
+    "loco_op_decoder_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -190,6 +190,63 @@ def load_hf_checkpoint(path: str, with_text_prenet: bool = False):
     return pre, enc
 
 
+HF_DECODER_PREFIXES = ("speecht5.decoder.", "text_decoder_postnet.")
+
+
+def load_hf_decoder(path: str):
+    """(decoder_state_dict, postnet_state_dict) of a HuggingFace SpeechT5ForSpeechToText checkpoint on disk -- keys below
+    ``speecht5.decoder.`` (``prenet.embed_tokens.weight``, ``wrapped_decoder.layers.N.*``) and ``text_decoder_postnet.``
+    (``lm_head.weight``) -- or two empty dicts for an encoder-only file.  ``tie_word_embeddings``: safetensors files carry the
+    tied tensor once; whichever of embed_tokens / lm_head is present serves for both (from_state_dicts resolves it).  HF's
+    non-persistent position buffer, when an old file carries it, is dropped (the table is regenerated)."""
+    import torch
+    dec, post = {}, {}
+
+    def take(key, get):
+        for pf, dst in zip(HF_DECODER_PREFIXES, (dec, post)):
+            if key.startswith(pf) and "embed_positions" not in key:
+                dst[key[len(pf):]] = get()
+
+    for f in _checkpoint_files(path):
+        if f.endswith(".safetensors"):
+            from safetensors import safe_open
+            with safe_open(f, framework="pt", device="cpu") as sf:
+                for key in sf.keys():
+                    take(key, lambda k_=key: sf.get_tensor(k_))
+        else:
+            sd = torch.load(f, map_location="cpu", weights_only=True)
+            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+            for key, v in sd.items():
+                take(key, lambda v_=v: v_)
+    return dec, post
+
+
+def decoder_problem(dec_sd, post_sd):
+    """None when (dec_sd, post_sd) hold a complete, well-formed text decoder -- one of the tied pair embed_tokens / lm_head as
+    [vocab, 768] and every tensor of layers 0..N in HF's shapes -- else one line naming the first thing that is missing or
+    misshapen.  from_pretrained keeps the decoder of a checkpoint only in the first case: files that carry the encoder and
+    stray decoder tensors keep loading as encoder-only models, and ``generate`` then raises with this line."""
+    import re
+    from .decoder import decoder_layer_keys
+    tied = [t for t in (dec_sd.get("prenet.embed_tokens.weight"), post_sd.get("lm_head.weight")) if t is not None]
+    if not tied:
+        return "neither speecht5.decoder.prenet.embed_tokens.weight nor text_decoder_postnet.lm_head.weight is in the file"
+    for t in tied:
+        if t.dim() != 2 or t.shape[1] != 768 or t.shape[0] < 3:
+            return f"the token embedding / lm_head has shape {tuple(t.shape)}, expected [vocab, 768]"
+    ids = [int(m_.group(1)) for m_ in (re.match(r"wrapped_decoder\.layers\.(\d+)\.", k) for k in dec_sd) if m_]
+    if not ids:
+        return "no speecht5.decoder.wrapped_decoder.layers.N.* tensors are in the file"
+    for l in range(max(ids) + 1):
+        for name, shape, _ in decoder_layer_keys(l):
+            t = dec_sd.get("wrapped_decoder." + name)
+            if t is None:
+                return f"speecht5.decoder.wrapped_decoder.{name} is missing"
+            if tuple(t.shape) != tuple(shape):
+                return f"speecht5.decoder.wrapped_decoder.{name} has shape {tuple(t.shape)}, expected {tuple(shape)}"
+    return None
+
+
 def check_hf_config(path: str):
     """config.json next to the weights, when there is one: the kernels are specialised for SpeechT5-base; say so before loading."""
     import json

@@ -73,6 +73,32 @@ struct StemW {  // the prenet's tensors (bound for a handle with the speech pren
     const float* pe_k = nullptr;     // wrapped_encoder.embed_positions.pe_k [320,64]
 };
 
+// Text decoder (SpeechT5DecoderWithTextPrenet + SpeechT5TextDecoderPostnet): optional, bound by loco_finalize_weights when the handle
+// was given decoder tensors.  Everything is fp32 in every precision mode (rows are few; the step is bandwidth-bound).
+struct DecLayerW {
+    float* wqkv = nullptr;  // self-attention [2304,768], q rows pre-scaled by 1/8
+    float* bqkv = nullptr;
+    float* wcq = nullptr;   // cross-attention q [768,768] pre-scaled by 1/8
+    float* bcq = nullptr;
+    WB self_out, self_ln, cross_out, cross_ln, ffn_in, ffn_out, final_ln;
+};
+struct DecoderW {
+    int layers = 0;         // from the keys
+    bool ready = false;
+    std::vector<DecLayerW> L;
+    float* wckv = nullptr;  // cross-attention k|v of every layer, [layers * 1536, 768]: one product per utterance
+    float* bckv = nullptr;
+    const float* embed = nullptr;
+    const float* lm_head = nullptr;
+    int vocab = 0;
+    float* pos_tab = nullptr;  // [pos_rows, 768], HF SpeechT5SinusoidalPositionalEmbedding (padding row 1 = 0)
+    int pos_rows = 0;
+    bool pos_user = false;
+    int32_t* host_state = nullptr;  // pinned: loco_decoder_generate reads the device's "rows still open" word through it
+};
+constexpr int kDecMaxPositions = 450;  // SpeechT5Config.max_text_positions; HF's table has max_text_positions + pad_token_id + 1 = 452 rows
+constexpr int kDecStartToken = 2, kDecEosToken = 2, kDecPadToken = 1;
+
 // Profiling buckets, named after the kernel that runs in them (the two precision modes have their own attention and
 // positional-conv buckets: the f16x3 positional conv IS a gemm_f16x3_dma_kernel launch, but keeps a bucket of its own because
 // its shape -- N = 48, K = 6144, halo layout -- has little in common with the projection GEMMs).
@@ -165,6 +191,8 @@ struct loco_encoder {
     float* text_pe = nullptr;     // [text_pe_rows, 768]
     int text_pe_rows = 0;
     bool speech_ready = false;    // set by loco_finalize_weights when the speech prenet weights were supplied
+    DecoderW dec;                 // text decoder (optional)
+    std::map<std::string, std::vector<int64_t>> dec_shapes;  // shapes of the decoder tensors as loaded (the vocabulary is theirs)
     // concurrency inside one forward: a batch may run as two half-batches on two streams (loco_set_streams).  The side stream and
     // its events are created on first use under side_mu; forwards in flight together serialise their second halves on it.
     int streams = 2;
@@ -227,6 +255,87 @@ void build_expected(loco_encoder* e) {
 }
 
 bool optional_key(const std::string& k) { return k == "prenet.masked_spec_embed"; }
+
+// Decoder tensors (HF names below "speecht5.", as the encoder's): the shape a key must have, or false for a key that is none.
+// The vocabulary size is taken from the tensor ([V,768], V >= 3: the special tokens 0..2 exist).
+const char* const kDecLayerLinear[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj",
+                                       "encoder_attn.q_proj", "encoder_attn.k_proj", "encoder_attn.v_proj", "encoder_attn.out_proj"};
+const char* const kDecLayerNorm[] = {"self_attn_layer_norm", "encoder_attn_layer_norm", "final_layer_norm"};
+const std::string kDecEmbedKey = "decoder.prenet.embed_tokens.weight", kDecHeadKey = "text_decoder_postnet.lm_head.weight",
+                  kDecLayerPrefix = "decoder.wrapped_decoder.layers.";
+
+std::vector<std::pair<std::string, std::vector<int64_t>>> decoder_layer_keys(int l) {
+    std::vector<std::pair<std::string, std::vector<int64_t>>> out;
+    const std::string b = kDecLayerPrefix + std::to_string(l) + ".";
+    for (const char* pr : kDecLayerLinear) {
+        out.push_back({b + pr + ".weight", {kHidden, kHidden}});
+        out.push_back({b + pr + ".bias", {kHidden}});
+    }
+    for (const char* ln : kDecLayerNorm) {
+        out.push_back({b + ln + ".weight", {kHidden}});
+        out.push_back({b + ln + ".bias", {kHidden}});
+    }
+    out.push_back({b + "feed_forward.intermediate_dense.weight", {kFfn, kHidden}});
+    out.push_back({b + "feed_forward.intermediate_dense.bias", {kFfn}});
+    out.push_back({b + "feed_forward.output_dense.weight", {kHidden, kFfn}});
+    out.push_back({b + "feed_forward.output_dense.bias", {kHidden}});
+    return out;
+}
+
+int decoder_layer_of(const std::string& k) {  // -1: not a decoder layer key
+    if (k.rfind(kDecLayerPrefix, 0) != 0) return -1;
+    size_t i = kDecLayerPrefix.size(), j = i;
+    while (j < k.size() && k[j] >= '0' && k[j] <= '9') ++j;
+    if (j == i || j - i > 2 || j >= k.size() || k[j] != '.') return -1;
+    return atoi(k.substr(i, j - i).c_str());
+}
+
+bool decoder_key_shape(const std::string& k, const std::vector<int64_t>& got, std::vector<int64_t>& want) {
+    if (k == kDecEmbedKey || k == kDecHeadKey) {
+        want = {got.size() == 2 && got[0] >= 3 ? got[0] : 81, kHidden};
+        return true;
+    }
+    const int l = decoder_layer_of(k);
+    if (l < 0) return false;
+    for (auto& kv : decoder_layer_keys(l))
+        if (kv.first == k) {
+            want = kv.second;
+            return true;
+        }
+    return false;
+}
+
+// decoder layer count of the tensors loaded so far (0: none), and whether any decoder tensor was given at all
+int decoder_layers_loaded(const loco_encoder* e, bool* any) {
+    int layers = 0;
+    bool seen = false;
+    for (auto& kv : e->raw) {
+        const int l = decoder_layer_of(kv.first);
+        if (l >= 0) layers = l + 1 > layers ? l + 1 : layers;
+        seen = seen || l >= 0 || kv.first == kDecEmbedKey || kv.first == kDecHeadKey;
+    }
+    if (any) *any = seen;
+    return layers;
+}
+
+// Decoder tensors still missing on a handle that was given SOME of them (it must then have them all; one of the tied embedding /
+// lm_head pair suffices); 0 for a handle without any decoder tensor.  Names are appended to *names, comma separated.
+int decoder_missing(const loco_encoder* e, std::string* names) {
+    bool any = false;
+    const int layers = decoder_layers_loaded(e, &any);
+    if (!any) return 0;
+    int missing = 0;
+    auto need = [&](const std::string& k) {
+        if (e->raw.count(k)) return;
+        ++missing;
+        if (names) *names += (names->empty() ? "" : ",") + k;
+    };
+    if (!e->raw.count(kDecEmbedKey) && !e->raw.count(kDecHeadKey)) need(kDecEmbedKey);
+    if (layers == 0) need(kDecLayerPrefix + "0.self_attn.q_proj.weight");
+    for (int l = 0; l < layers; ++l)
+        for (auto& kv : decoder_layer_keys(l)) need(kv.first);
+    return missing;
+}
 
 std::string canonical_key(const char* key) {
     std::string k(key);
@@ -960,6 +1069,16 @@ void loco_destroy(loco_encoder* e) {
         free_split(l.s1);
         free_split(l.s2);
     }
+    for (auto& l : e->dec.L) {
+        (void)hipFree(l.wqkv);
+        (void)hipFree(l.bqkv);
+        (void)hipFree(l.wcq);
+        (void)hipFree(l.bcq);
+    }
+    (void)hipFree(e->dec.wckv);
+    (void)hipFree(e->dec.bckv);
+    (void)hipFree(e->dec.pos_tab);
+    if (e->dec.host_state) (void)hipHostFree(e->dec.host_state);
     (void)hipFree(e->absmax_dev);
     (void)hipFree(e->debug_counter);
     if (e->own) (void)hipHostFree(e->own);
@@ -1029,15 +1148,35 @@ int loco_set_weight(loco_encoder* e, const char* key, const float* data, const i
         *slot = d;
         return LOCO_OK;
     }
+    if (k == "decoder.prenet.embed_positions.weights") {  // HF's non-persistent buffer: given, it replaces the generated table
+        if (ndim != 2 || shp[1] != kHidden || shp[0] < kDecMaxPositions + 2) return fail(LOCO_E_INVALID, "%s: expected [>= 452,768]", key);
+        float* d = nullptr;
+        HIP_TRY(hipMalloc(&d, (size_t)n * sizeof(float)));
+        HIP_TRY(hipMemcpy(d, data, (size_t)n * sizeof(float), hipMemcpyDefault));
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(e->dec.pos_tab);
+        e->dec.pos_tab = d;
+        e->dec.pos_rows = (int)shp[0];
+        e->dec.pos_user = true;
+        return LOCO_OK;
+    }
+    std::vector<int64_t> dec_shape;
+    const bool dec_key = decoder_key_shape(k, shp, dec_shape);
     auto it = e->expected.find(k);
-    if (it == e->expected.end()) return fail(LOCO_E_INVALID, "unexpected key in state_dict: %s", key);
-    if (it->second != shp) {
+    if (!dec_key && it == e->expected.end()) return fail(LOCO_E_INVALID, "unexpected key in state_dict: %s", key);
+    if ((dec_key ? dec_shape : it->second) != shp) {
         std::string got, want;
         for (auto s : shp) got += std::to_string(s) + ",";
-        for (auto s : it->second) want += std::to_string(s) + ",";
+        for (auto s : (dec_key ? dec_shape : it->second)) want += std::to_string(s) + ",";
         return fail(LOCO_E_INVALID, "size mismatch for %s: got [%s] expected [%s]", key, got.c_str(), want.c_str());
     }
     float*& d = e->raw[k];
+    // [vocab,768]: the only tensors whose size is the checkpoint's own -- a re-load with another vocabulary gets a new buffer
+    if (d && (k == kDecEmbedKey || k == kDecHeadKey) && e->dec_shapes.count(k) && e->dec_shapes[k] != shp) {
+        (void)hipFree(d);
+        d = nullptr;
+    }
+    if (dec_key) e->dec_shapes[k] = shp;
     if (!d) HIP_TRY(hipMalloc(&d, (size_t)n * sizeof(float)));
     HIP_TRY(hipMemcpy(d, data, (size_t)n * sizeof(float), hipMemcpyDefault));
     HIP_TRY(hipStreamSynchronize(nullptr));  // device-to-device copies may return early; the caller may free `data` now
@@ -1063,9 +1202,76 @@ int loco_missing_weights(const loco_encoder* e, char* buf, size_t buflen) {
         ++missing;
         names += (names.empty() ? "" : ",") + std::string("text_prenet.encode_positions.alpha");
     }
+    missing += decoder_missing(e, &names);
     if (buf && buflen) snprintf(buf, buflen, "%s", names.c_str());
     return missing;
 }
+
+namespace {
+// Decoder weights as the kernels read them: q|k|v of the self-attention fused ([2304,768], the 1/8 query scaling folded in -- exact, a
+// power of two), the cross-attention q scaled alike, the cross-attention k|v of ALL layers stacked into one [layers * 1536, 768]
+// operand (projected once per utterance by one big-M GEMM).  The tied embedding / lm_head pair: either one serves for both.
+int finalize_decoder(loco_encoder* e, hipStream_t s) {
+    DecoderW& d = e->dec;
+    bool any = false;
+    const int layers = decoder_layers_loaded(e, &any);
+    d.ready = false;
+    if (!any) return LOCO_OK;
+    const size_t hh = (size_t)kHidden * kHidden;
+    if ((int)d.L.size() != layers) {
+        for (auto& l : d.L) {
+            (void)hipFree(l.wqkv), (void)hipFree(l.bqkv), (void)hipFree(l.wcq), (void)hipFree(l.bcq);
+        }
+        d.L.assign(layers, DecLayerW());
+        (void)hipFree(d.wckv), (void)hipFree(d.bckv);
+        d.wckv = d.bckv = nullptr;
+    }
+    d.layers = layers;
+    if (!d.wckv) HIP_TRY(hipMalloc(&d.wckv, (size_t)layers * 2 * hh * sizeof(float)));
+    if (!d.bckv) HIP_TRY(hipMalloc(&d.bckv, (size_t)layers * 2 * kHidden * sizeof(float)));
+    for (int l = 0; l < layers; ++l) {
+        DecLayerW& lw = d.L[l];
+        const std::string b = "decoder.wrapped_decoder.layers." + std::to_string(l) + ".", sa = b + "self_attn.", ca = b + "encoder_attn.";
+        if (!lw.wqkv) HIP_TRY(hipMalloc(&lw.wqkv, 3 * hh * sizeof(float)));
+        if (!lw.bqkv) HIP_TRY(hipMalloc(&lw.bqkv, 3 * kHidden * sizeof(float)));
+        if (!lw.wcq) HIP_TRY(hipMalloc(&lw.wcq, hh * sizeof(float)));
+        if (!lw.bcq) HIP_TRY(hipMalloc(&lw.bcq, kHidden * sizeof(float)));
+        HIP_TRY(launch_scale_copy(W(e, sa + "q_proj.weight"), lw.wqkv, hh, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, sa + "k_proj.weight"), lw.wqkv + hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, sa + "v_proj.weight"), lw.wqkv + 2 * hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, sa + "q_proj.bias"), lw.bqkv, kHidden, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, sa + "k_proj.bias"), lw.bqkv + kHidden, kHidden, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, sa + "v_proj.bias"), lw.bqkv + 2 * kHidden, kHidden, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "q_proj.weight"), lw.wcq, hh, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "q_proj.bias"), lw.bcq, kHidden, 0.125f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "k_proj.weight"), d.wckv + (size_t)l * 2 * hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "v_proj.weight"), d.wckv + (size_t)l * 2 * hh + hh, hh, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "k_proj.bias"), d.bckv + (size_t)l * 2 * kHidden, kHidden, 1.0f, s));
+        HIP_TRY(launch_scale_copy(W(e, ca + "v_proj.bias"), d.bckv + (size_t)l * 2 * kHidden + kHidden, kHidden, 1.0f, s));
+        lw.self_out = weight_bias(e, sa + "out_proj.");
+        lw.self_ln = weight_bias(e, b + "self_attn_layer_norm.");
+        lw.cross_out = weight_bias(e, ca + "out_proj.");
+        lw.cross_ln = weight_bias(e, b + "encoder_attn_layer_norm.");
+        lw.ffn_in = weight_bias(e, b + "feed_forward.intermediate_dense.");
+        lw.ffn_out = weight_bias(e, b + "feed_forward.output_dense.");
+        lw.final_ln = weight_bias(e, b + "final_layer_norm.");
+    }
+    const bool has_embed = e->raw.count(kDecEmbedKey) != 0, has_head = e->raw.count(kDecHeadKey) != 0;
+    d.embed = W(e, has_embed ? kDecEmbedKey : kDecHeadKey);
+    d.lm_head = W(e, has_head ? kDecHeadKey : kDecEmbedKey);
+    const std::vector<int64_t>&se = e->dec_shapes.at(has_embed ? kDecEmbedKey : kDecHeadKey), &sh = e->dec_shapes.at(has_head ? kDecHeadKey : kDecEmbedKey);
+    if (se[0] != sh[0]) return fail(LOCO_E_INVALID, "decoder: embed_tokens has %lld rows, lm_head %lld", (long long)se[0], (long long)sh[0]);
+    d.vocab = (int)se[0];
+    if (!d.pos_tab) {  // C callers without HF's buffer: the library's own generator (the same torch expression, fp32 step by step)
+        d.pos_rows = kDecMaxPositions + 2;
+        HIP_TRY(hipMalloc(&d.pos_tab, (size_t)d.pos_rows * kHidden * sizeof(float)));
+        HIP_TRY(launch_sinusoid_table(d.pos_tab, d.pos_rows, s));
+    }
+    if (!d.host_state) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d.host_state), 4 * sizeof(int32_t), hipHostMallocDefault));
+    d.ready = true;
+    return LOCO_OK;
+}
+}  // namespace
 
 int loco_finalize_weights(loco_encoder* e, void* stream) {
     if (!e) return fail(LOCO_E_INVALID, "null encoder");
@@ -1170,6 +1376,8 @@ int loco_finalize_weights(loco_encoder* e, void* stream) {
         rc = static_range_check(e, b + "layer_norm.", kHidden, s);
         if (!rc && l + 1 < e->cfg.layers) rc = static_range_check(e, b + "final_layer_norm.", kHidden, s);  // the last one is written in fp32
     }
+    if (rc) return rc;
+    rc = finalize_decoder(e, s);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     e->speech_ready = speech;
@@ -1764,3 +1972,280 @@ int loco_op_attention(const float* qkv, const float* qp, const int32_t* frames, 
 }
 
 }  // extern "C"
+
+// ---- text decoder: teacher-forced logits and greedy generation ------------------------------------------------------------
+namespace {
+
+// Workspace of one utterance batch (caller-owned): state that lives from loco_decoder_begin to the last step first, scratch after.
+struct DecPlan {
+    int B, T, S, L;
+    size_t off_state, off_lengths, off_frames, off_tokens, off_nonpad, off_finished, off_cross, off_self, off_x0, off_x1, off_tmp, off_q,
+        off_ctx, off_ffn, off_logits, off_attn, total;
+};
+
+void make_dec_plan(int layers, int B, int T, int S, DecPlan& p) {
+    p.B = B, p.T = T, p.S = S, p.L = layers;
+    const size_t f = sizeof(float), rows = (size_t)B * S;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        size_t at = o;
+        o += align_up(bytes);
+        return at;
+    };
+    p.off_state = take(4 * sizeof(int32_t));  // [0] rows still open, [1] steps completed
+    p.off_lengths = take((size_t)B * sizeof(int32_t));
+    p.off_frames = take((size_t)B * sizeof(int32_t));
+    p.off_tokens = take(rows * sizeof(int32_t));
+    p.off_nonpad = take(rows * sizeof(int32_t));
+    p.off_finished = take(rows * sizeof(int32_t));
+    p.off_cross = take((size_t)B * T * p.L * 2 * kHidden * f);  // [B * T_enc][layers][k | v]
+    p.off_self = take((size_t)p.L * rows * 2 * kHidden * f);    // [layers][B][S_max][k | v]
+    p.off_x0 = take(rows * kHidden * f);
+    p.off_x1 = take(rows * kHidden * f);
+    p.off_tmp = take(rows * kHidden * f);
+    p.off_q = take(rows * kHidden * f);
+    p.off_ctx = take(rows * kHidden * f);
+    p.off_ffn = take(rows * kFfn * f);
+    p.off_logits = take((size_t)B * 128 * f);
+    size_t attn = dec_attention_scratch_bytes(B, S, T);  // teacher-forced cross-attention
+    for (size_t v : {dec_attention_scratch_bytes(B, S, S), dec_attention_scratch_bytes(B, 1, T), dec_attention_scratch_bytes(B, 1, S)})
+        attn = v > attn ? v : attn;
+    p.off_attn = take(attn);
+    p.total = o;
+}
+
+int dec_check(const loco_encoder* e, const char* fn, int B, int T, int S, const void* ws, size_t bytes, DecPlan& p) {
+    if (!e) return fail(LOCO_E_INVALID, "%s: null encoder", fn);
+    if (!e->finalized || !e->dec.ready)
+        return fail(LOCO_E_STATE, "%s: the handle has no decoder weights (decoder.prenet.*, decoder.wrapped_decoder.*, text_decoder_postnet.*) or "
+                                  "loco_finalize_weights has not run", fn);
+    if (B <= 0 || T <= 0 || S <= 0) return fail(LOCO_E_INVALID, "%s: B, T_enc and the sequence length must be positive", fn);
+    if (S > kDecMaxPositions) return fail(LOCO_E_INVALID, "%s: %d positions exceed max_text_positions = %d", fn, S, kDecMaxPositions);
+    if (!ws) return fail(LOCO_E_INVALID, "%s: null workspace", fn);
+    make_dec_plan(e->dec.layers, B, T, S, p);
+    if (bytes < p.total) return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, bytes, p.total);
+    return LOCO_OK;
+}
+
+int run_skinny(hipStream_t s, const float* A, const WB& w, const float* R, float* C, int M, int N, int K, int epi) {
+    HIP_TRY(launch_skinny_gemm(A, K, w.w, K, w.b, R, N, C, N, nullptr, 0, N, M, N, K, epi, s));
+    return LOCO_OK;
+}
+
+// cross-attention k|v of every layer from the encoder output: M = B * T_enc rows through the exact-fp32 GEMM (14 MFLOP per frame
+// against the encoder's 339)
+int dec_cross_kv(loco_encoder* e, const DecPlan& p, char* ws, const float* enc_out, hipStream_t s) {
+    const int N = p.L * 2 * kHidden;
+    return run_gemm(e, s, enc_out, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0, reinterpret_cast<float*>(ws + p.off_cross), N,
+                    p.B * p.T, N, kHidden, kEpiNone);
+}
+
+int dec_attention(hipStream_t s, const float* q, long ldq, long sq, const float* kv, long ldk, long sk, const int32_t* kcount, float* out,
+                  int B, int Sq, int Tk, int causal, float* scratch) {
+    HIP_TRY(launch_dec_attention(q, ldq, sq, kv, ldk, sk, kv + kHidden, ldk, sk, kcount, out, kHidden, (long)Sq * kHidden, B, Sq, Tk, causal, 0,
+                                 1.0f, scratch, s));
+    return LOCO_OK;
+}
+
+#define DEC_TRY(expr)           \
+    do {                        \
+        const int rc_ = (expr); \
+        if (rc_) return rc_;    \
+    } while (0)
+
+// one decode step: token t of every row in, token t + 1 out; B rows through the weight-streaming GEMM
+int dec_step(loco_encoder* e, const DecPlan& p, char* ws, int t, float* logits_out, hipStream_t s) {
+    const DecoderW& d = e->dec;
+    const int B = p.B;
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    float *x0 = F(p.off_x0), *x1 = F(p.off_x1), *tmp = F(p.off_tmp), *q = F(p.off_q), *ctx = F(p.off_ctx), *ffn = F(p.off_ffn), *scr = F(p.off_attn);
+    float* logits = logits_out ? logits_out : F(p.off_logits);
+    const long ld_cross = (long)p.L * 2 * kHidden, ld_self = 2 * kHidden;
+    HIP_TRY(launch_dec_embed_step(I(p.off_tokens), p.S, t, d.embed, d.vocab, d.pos_tab, d.pos_rows, I(p.off_nonpad), x0, B, s));
+    for (int l = 0; l < p.L; ++l) {
+        const DecLayerW& lw = d.L[l];
+        float* cache = F(p.off_self) + (size_t)l * B * p.S * ld_self;
+        // q -> row buffer, k|v -> row t of the cache
+        HIP_TRY(launch_skinny_gemm(x0, kHidden, lw.wqkv, kHidden, lw.bqkv, nullptr, 0, q, kHidden, cache + (size_t)t * ld_self, (long)p.S * ld_self,
+                                   kHidden, B, kQkv, kHidden, kEpiNone, s));
+        DEC_TRY(dec_attention(s, q, kHidden, kHidden, cache, ld_self, (long)p.S * ld_self, nullptr, ctx, B, 1, t + 1, 0, scr));
+        DEC_TRY(run_skinny(s, ctx, lw.self_out, x0, tmp, B, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.self_ln.w, lw.self_ln.b, x1, B, kHidden));
+        DEC_TRY(run_skinny(s, x1, WB{lw.wcq, lw.bcq}, nullptr, q, B, kHidden, kHidden, kEpiNone));
+        DEC_TRY(dec_attention(s, q, kHidden, kHidden, F(p.off_cross) + (size_t)l * 2 * kHidden, ld_cross, (long)p.T * ld_cross, I(p.off_frames), ctx, B,
+                              1, p.T, 0, scr));
+        DEC_TRY(run_skinny(s, ctx, lw.cross_out, x1, tmp, B, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.cross_ln.w, lw.cross_ln.b, x0, B, kHidden));
+        DEC_TRY(run_skinny(s, x0, lw.ffn_in, nullptr, ffn, B, kFfn, kHidden, kEpiGelu));
+        DEC_TRY(run_skinny(s, ffn, lw.ffn_out, x0, tmp, B, kHidden, kFfn, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.final_ln.w, lw.final_ln.b, x0, B, kHidden));
+    }
+    DEC_TRY(run_skinny(s, x0, WB{d.lm_head, nullptr}, nullptr, logits, B, d.vocab, kHidden, kEpiNone));
+    HIP_TRY(launch_dec_select(logits, d.vocab, B, I(p.off_tokens), p.S, t, I(p.off_finished), I(p.off_lengths), I(p.off_state), kDecEosToken,
+                              kDecPadToken, s));
+    return LOCO_OK;
+}
+
+int dec_begin(loco_encoder* e, const DecPlan& p, char* ws, const float* enc_out, const int32_t* enc_frames, hipStream_t s) {
+    auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    if (enc_frames)
+        HIP_TRY(hipMemcpyAsync(I(p.off_frames), enc_frames, (size_t)p.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    else  // no frame counts: every encoder row is a key
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(I(p.off_frames)), p.T, (size_t)p.B, s));
+    HIP_TRY(launch_dec_begin(I(p.off_tokens), p.B, p.S, kDecStartToken, kDecPadToken, I(p.off_lengths), I(p.off_state), s));
+    return dec_cross_kv(e, p, ws, enc_out, s);
+}
+
+}  // namespace
+
+int loco_has_decoder(const loco_encoder* e) {
+    if (!e) return 0;
+    bool any = false;
+    (void)decoder_layers_loaded(e, &any);
+    return any && decoder_missing(e, nullptr) == 0 ? 1 : 0;  // a complete set of decoder tensors, not a part of one
+}
+
+int loco_decoder_max_batch(void) { return kSkinnyMaxM; }
+
+size_t loco_decoder_workspace_bytes(const loco_encoder* e, int32_t B, int32_t T_enc, int32_t S_max) {
+    if (!e || B <= 0 || T_enc <= 0 || S_max <= 0) return 0;
+    if (!loco_has_decoder(e)) return 0;  // nothing to decode with
+    DecPlan p;
+    make_dec_plan(decoder_layers_loaded(e, nullptr), B, T_enc, S_max, p);  // the layers the loaded keys name
+    return p.total;
+}
+
+int loco_decoder_forward(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                         const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, "loco_decoder_forward", B, T_enc, S, workspace, workspace_bytes, p));
+    if (!enc_out || !decoder_input_ids || !logits) return fail(LOCO_E_INVALID, "loco_decoder_forward: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const DecoderW& d = e->dec;
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    float *x0 = F(p.off_x0), *x1 = F(p.off_x1), *tmp = F(p.off_tmp), *q = F(p.off_q), *ctx = F(p.off_ctx), *ffn = F(p.off_ffn), *scr = F(p.off_attn);
+    const int M = B * S;
+    const long ld_cross = (long)p.L * 2 * kHidden, ld_self = 2 * kHidden;
+    if (enc_frames)
+        HIP_TRY(hipMemcpyAsync(I(p.off_frames), enc_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    else  // no frame counts: every encoder row is a key
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(I(p.off_frames)), T_enc, (size_t)B, s));
+    DEC_TRY(dec_cross_kv(e, p, ws, enc_out, s));
+    HIP_TRY(launch_dec_embed(decoder_input_ids, S, d.embed, d.vocab, d.pos_tab, d.pos_rows, x0, B, S, nullptr, s));
+    for (int l = 0; l < p.L; ++l) {
+        const DecLayerW& lw = d.L[l];
+        if (hidden_states) DEC_TRY(run_copy(e, s, hidden_states[l], x0, (size_t)M * kHidden));
+        // the self-attention k|v land in the layout the step reads ([layers][B][S][k | v] with S rows per clip here)
+        float* cache = F(p.off_self) + (size_t)l * M * ld_self;
+        DEC_TRY(run_gemm(e, s, x0, kHidden, lw.wqkv, kHidden, lw.bqkv, nullptr, 0, q, kHidden, M, kHidden, kHidden, kEpiNone));
+        DEC_TRY(run_gemm(e, s, x0, kHidden, lw.wqkv + (size_t)kHidden * kHidden, kHidden, lw.bqkv + kHidden, nullptr, 0, cache, ld_self, M, 2 * kHidden,
+                         kHidden, kEpiNone));
+        DEC_TRY(dec_attention(s, q, kHidden, (long)S * kHidden, cache, ld_self, (long)S * ld_self, nullptr, ctx, B, S, S, 1, scr));
+        DEC_TRY(run_gemm(e, s, ctx, kHidden, lw.self_out.w, kHidden, lw.self_out.b, x0, kHidden, tmp, kHidden, M, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.self_ln.w, lw.self_ln.b, x1, M, kHidden));
+        DEC_TRY(run_gemm(e, s, x1, kHidden, lw.wcq, kHidden, lw.bcq, nullptr, 0, q, kHidden, M, kHidden, kHidden, kEpiNone));
+        DEC_TRY(dec_attention(s, q, kHidden, (long)S * kHidden, F(p.off_cross) + (size_t)l * 2 * kHidden, ld_cross, (long)T_enc * ld_cross,
+                              I(p.off_frames), ctx, B, S, T_enc, 0, scr));
+        DEC_TRY(run_gemm(e, s, ctx, kHidden, lw.cross_out.w, kHidden, lw.cross_out.b, x1, kHidden, tmp, kHidden, M, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.cross_ln.w, lw.cross_ln.b, x0, M, kHidden));
+        DEC_TRY(run_gemm(e, s, x0, kHidden, lw.ffn_in.w, kHidden, lw.ffn_in.b, nullptr, 0, ffn, kFfn, M, kFfn, kHidden, kEpiGelu));
+        DEC_TRY(run_gemm(e, s, ffn, kFfn, lw.ffn_out.w, kFfn, lw.ffn_out.b, x0, kHidden, tmp, kHidden, M, kHidden, kFfn, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.final_ln.w, lw.final_ln.b, x0, M, kHidden));
+    }
+    if (hidden_states) DEC_TRY(run_copy(e, s, hidden_states[p.L], x0, (size_t)M * kHidden));
+    // lm_head: N = vocab (81) is no multiple of the MFMA GEMM's 4-column epilogue; the weight-streaming kernel takes any N, 64 rows per grid row
+    return run_skinny(s, x0, WB{d.lm_head, nullptr}, nullptr, logits, M, d.vocab, kHidden, kEpiNone);
+}
+
+int loco_decoder_begin(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, int32_t S_max,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, "loco_decoder_begin", B, T_enc, S_max, workspace, workspace_bytes, p));
+    if (B > kSkinnyMaxM) return fail(LOCO_E_INVALID, "loco_decoder_begin: %d clips exceed the decode step's limit of %d rows", B, kSkinnyMaxM);
+    if (!enc_out) return fail(LOCO_E_INVALID, "loco_decoder_begin: null encoder output");
+    return dec_begin(e, p, static_cast<char*>(workspace), enc_out, enc_frames, (hipStream_t)stream);
+}
+
+int loco_decoder_step(loco_encoder* e, int32_t B, int32_t T_enc, int32_t S_max, int32_t t, float* logits, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, "loco_decoder_step", B, T_enc, S_max, workspace, workspace_bytes, p));
+    if (B > kSkinnyMaxM) return fail(LOCO_E_INVALID, "loco_decoder_step: %d clips exceed the decode step's limit of %d rows", B, kSkinnyMaxM);
+    if (t < 0 || t + 1 >= S_max) return fail(LOCO_E_INVALID, "loco_decoder_step: step %d writes token %d of a buffer of %d", t, t + 1, S_max);
+    return dec_step(e, p, static_cast<char*>(workspace), t, logits, (hipStream_t)stream);
+}
+
+int loco_decoder_read_tokens(const loco_encoder* e, int32_t B, int32_t T_enc, int32_t S_max, int32_t* tokens, int32_t* lengths, const void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, "loco_decoder_read_tokens", B, T_enc, S_max, workspace, workspace_bytes, p));
+    const char* ws = static_cast<const char*>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    if (tokens) HIP_TRY(hipMemcpyAsync(tokens, ws + p.off_tokens, (size_t)B * S_max * sizeof(int32_t), hipMemcpyDefault, s));
+    if (lengths) HIP_TRY(hipMemcpyAsync(lengths, ws + p.off_lengths, (size_t)B * sizeof(int32_t), hipMemcpyDefault, s));
+    return LOCO_OK;
+}
+
+// How often generate looks at the device's "rows still open" word.  A look is a 16-byte copy to pinned memory plus a stream
+// synchronisation (~20 us of an idle queue); a step is 69 dependent launches (>= 100 us).  Every 8 steps keeps the queue fed for 8 steps
+// at a time and wastes at most 7 steps of pad tokens after the last row has finished.
+constexpr int kDecPollSteps = 8;
+
+int loco_decoder_generate(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, int32_t max_length,
+                          int32_t* tokens_out, int32_t* lengths_out, int32_t* out_length, float* step_logits, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, "loco_decoder_generate", B, T_enc, max_length, workspace, workspace_bytes, p));
+    if (B > kSkinnyMaxM) return fail(LOCO_E_INVALID, "loco_decoder_generate: %d clips exceed the decode step's limit of %d rows", B, kSkinnyMaxM);
+    if (!enc_out || !tokens_out) return fail(LOCO_E_INVALID, "loco_decoder_generate: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    DEC_TRY(dec_begin(e, p, ws, enc_out, enc_frames, s));
+    int32_t* host = e->dec.host_state;
+    for (int t = 0; t + 1 < max_length; ++t) {
+        DEC_TRY(dec_step(e, p, ws, t, step_logits ? step_logits + (size_t)t * B * e->dec.vocab : nullptr, s));
+        if ((t + 1) % kDecPollSteps == 0 && t + 2 < max_length) {
+            HIP_TRY(hipMemcpyAsync(host, ws + p.off_state, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (host[0] == 0) break;
+        }
+    }
+    std::vector<int32_t> lens(B);
+    HIP_TRY(hipMemcpyAsync(tokens_out, ws + p.off_tokens, (size_t)B * max_length * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(lens.data(), ws + p.off_lengths, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int longest = 1;
+    for (int b = 0; b < B; ++b) longest = lens[b] > longest ? lens[b] : longest;
+    // HF stops after the step in which the last open row emits <eos>: the sequences are as long as the longest row; rows that finished
+    // earlier hold <pad> from there on (steps enqueued beyond that point only wrote <pad>)
+    if (lengths_out) memcpy(lengths_out, lens.data(), (size_t)B * sizeof(int32_t));
+    if (out_length) *out_length = longest;
+    return LOCO_OK;
+}
+
+int loco_op_skinny_gemm(const float* A, int64_t lda, const float* Wt, int64_t ldw, const float* bias, const float* R, int64_t ldr, float* C,
+                        int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* stream) {
+    if (!A || !Wt || !C) return fail(LOCO_E_INVALID, "loco_op_skinny_gemm: null argument");
+    if (M > kSkinnyMaxM) return fail(LOCO_E_INVALID, "loco_op_skinny_gemm: M = %d exceeds the limit of %d rows (use loco_op_gemm)", M, kSkinnyMaxM);
+    if (epilogue < 0 || epilogue > 2) return fail(LOCO_E_INVALID, "loco_op_skinny_gemm: epilogue must be 0, 1 or 2");
+    HIP_TRY(launch_skinny_gemm(A, lda, Wt, ldw, bias, R, ldr, C, ldc, nullptr, 0, N, M, N, K, epilogue, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+size_t loco_decoder_attention_scratch_bytes(int32_t B, int32_t Sq, int32_t Tk) {
+    return B > 0 && Sq > 0 && Tk > 0 ? dec_attention_scratch_bytes(B, Sq, Tk) : 0;
+}
+
+int loco_op_decoder_attention(const float* q, const float* k, const float* v, const int32_t* key_counts, float* out, int32_t B, int32_t Sq,
+                              int32_t Tk, int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!q || !k || !v || !out || B <= 0 || Sq <= 0 || Tk <= 0) return fail(LOCO_E_INVALID, "loco_op_decoder_attention: null / non-positive argument");
+    if (scratch_bytes < dec_attention_scratch_bytes(B, Sq, Tk))
+        return fail(LOCO_E_WORKSPACE, "loco_op_decoder_attention: scratch %zu < %zu bytes", scratch_bytes, dec_attention_scratch_bytes(B, Sq, Tk));
+    HIP_TRY(launch_dec_attention(q, kHidden, (long)Sq * kHidden, k, kHidden, (long)Tk * kHidden, v, kHidden, (long)Tk * kHidden, key_counts, out, kHidden,
+                                 (long)Sq * kHidden, B, Sq, Tk, causal, causal_offset, scale, static_cast<float*>(scratch), (hipStream_t)stream));
+    return LOCO_OK;
+}

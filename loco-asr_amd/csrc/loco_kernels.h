@@ -308,6 +308,29 @@ int resample_design(int sr_in, int sr_out, int* L_out, int* M_out, int* K_out, f
 hipError_t launch_resample(const float* x, int B, long n_in, long x_stride, const float* taps, int L, int M, int K, float* y, long n_out,
                            long y_stride, hipStream_t s);
 
+// text decoder (decoder.hip)
+constexpr int kSkinnyMaxM = 64;        // rows of the weight-streaming GEMM (and clips of one decode step)
+constexpr int kDecAttnMaxSplit = 64;   // key splits of one decoder attention launch
+// C[m,n] = epi(sum_k A[m,k] W[n,k] + bias[n]) (+ R[m,n]); K % 256 == 0, lda / ldw % 4 == 0; columns n >= nsplit go to
+// C2[m, n - nsplit] when C2 is given (the step's q | k|v product: q to a row buffer, k|v into the cache)
+hipError_t launch_skinny_gemm(const float* A, long lda, const float* W, long ldw, const float* bias, const float* R, long ldr, float* C,
+                              long ldc, float* C2, long ldc2, int nsplit, int M, int N, int K, int epilogue, hipStream_t s);
+int skinny_gemm_slices(int N, int K);
+int dec_attention_splits(int B, int Sq, int Tk);
+size_t dec_attention_scratch_bytes(int B, int Sq, int Tk);
+// out[b,i,h,:] = softmax_j(scale q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:] over keys j < kcount[b] (null: Tk) and, when causal,
+// j <= i + causal_offset; ld* = row strides, s* = clip strides in floats; scratch >= dec_attention_scratch_bytes
+hipError_t launch_dec_attention(const float* q, long ldq, long sq, const float* k, long ldk, long sk, const float* v, long ldv, long sv,
+                                const int32_t* kcount, float* out, long ldo, long so, int B, int Sq, int Tk, int causal, int causal_offset,
+                                float scale, float* scratch, hipStream_t s);
+hipError_t launch_dec_embed(const int32_t* ids, long ld_ids, const float* embed, int vocab, const float* table, int table_rows, float* x,
+                            int B, int S, int32_t* positions, hipStream_t s);
+hipError_t launch_dec_embed_step(const int32_t* tokens, int S_max, int t, const float* embed, int vocab, const float* table, int table_rows,
+                                 int32_t* nonpad, float* x, int B, hipStream_t s);
+hipError_t launch_dec_select(const float* logits, int vocab, int B, int32_t* tokens, int S_max, int t, int32_t* finished, int32_t* lengths,
+                             int32_t* state, int eos, int pad, hipStream_t s);
+hipError_t launch_dec_begin(int32_t* tokens, int B, int S_max, int start, int pad, int32_t* lengths, int32_t* state, hipStream_t s);
+
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
 }  // namespace loco

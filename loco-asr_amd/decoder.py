@@ -1,0 +1,200 @@
+"""The decoder half of ``SpeechT5ForSpeechToTextMI355X``: weight holders with HuggingFace's parameter names and the host side of
+the C ABI's ``loco_decoder_*`` entry points (include/loco_asr.h).
+
+    predicted_ids = model_stt.generate(**audios, max_length=100)
+    out_stt       = model_stt(**audios, decoder_input_ids=predicted_ids)
+
+``SpeechT5DecoderWithTextPrenetMI355X`` (``.prenet``, ``.wrapped_decoder``) and ``SpeechT5TextDecoderPostnetMI355X`` only own
+parameters, so that ``load_state_dict`` of HF's dicts works; every FLOP runs in the HIP kernels of csrc/decoder.hip (the decode step)
+and the library's exact-fp32 GEMM / LayerNorm (the teacher-forced pass).  Greedy search only: beam search, sampling, prefixes and a
+decoder attention mask raise by name.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib
+from .synth import DECODER_LAYERS, FFN, HIDDEN, MAX_TEXT_POSITIONS, TEXT_VOCAB
+
+DECODER_START_TOKEN_ID = 2
+EOS_TOKEN_ID = 2
+PAD_TOKEN_ID = 1
+DEFAULT_MAX_LENGTH = 21  # what HF 5.x generate resolves for a default SpeechT5Config: max_new_tokens = 20 after the start token (pinned by g13 a_default_ids)
+
+_UNSUPPORTED_GENERATE = ("num_beams", "do_sample", "decoder_input_ids", "decoder_attention_mask", "temperature", "top_k", "top_p",
+                         "num_return_sequences", "repetition_penalty", "length_penalty", "no_repeat_ngram_size", "min_length",
+                         "min_new_tokens", "forced_eos_token_id", "logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn",
+                         "past_key_values", "generation_config", "assistant_model", "streamer")
+
+
+@dataclass
+class Seq2SeqLMOutput:
+    """Field-compatible stand-in for the part of transformers' Seq2SeqLMOutput this model fills."""
+    logits: torch.Tensor = None
+    encoder_last_hidden_state: torch.Tensor = None
+    decoder_hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
+
+
+def _holder_base():
+    from .encoder import _WeightHolder
+    return _WeightHolder
+
+
+def _register(root, dotted, shape, init=0.0):
+    from .encoder import _register as reg
+    reg(root, dotted, shape, init)
+
+
+def decoder_layer_keys(layer: int):
+    """(name below ``wrapped_decoder.``, shape, init) of one SpeechT5DecoderLayer (HF modeling_speecht5.py:1070-1100)."""
+    b = f"layers.{layer}."
+    for attn in ("self_attn", "encoder_attn"):
+        for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            yield f"{b}{attn}.{proj}.weight", (HIDDEN, HIDDEN), 0.0
+            yield f"{b}{attn}.{proj}.bias", (HIDDEN,), 0.0
+    for ln in ("self_attn_layer_norm", "encoder_attn_layer_norm", "final_layer_norm"):
+        yield f"{b}{ln}.weight", (HIDDEN,), 1.0
+        yield f"{b}{ln}.bias", (HIDDEN,), 0.0
+    yield f"{b}feed_forward.intermediate_dense.weight", (FFN, HIDDEN), 0.0
+    yield f"{b}feed_forward.intermediate_dense.bias", (FFN,), 0.0
+    yield f"{b}feed_forward.output_dense.weight", (HIDDEN, FFN), 0.0
+    yield f"{b}feed_forward.output_dense.bias", (HIDDEN,), 0.0
+
+
+def make_decoder_modules(owner_ref, layers: int = DECODER_LAYERS, vocab: int = TEXT_VOCAB):
+    """(SpeechT5DecoderWithTextPrenetMI355X, SpeechT5TextDecoderPostnetMI355X) whose parameter changes mark ``owner_ref()``'s
+    weights dirty (the encoder module owns the library handle)."""
+    Holder = _holder_base()
+
+    class SpeechT5DecoderWithTextPrenetMI355X(Holder):
+        """Parameter names of HF SpeechT5DecoderWithTextPrenet: ``prenet.embed_tokens.weight`` and ``wrapped_decoder.layers.N.*``
+        (``prenet.embed_positions.weights`` is a non-persistent buffer in HF: not a key; the table is regenerated)."""
+
+        def __init__(self):
+            super().__init__(owner_ref)
+            _register(self, "prenet.embed_tokens.weight", (vocab, HIDDEN))
+            self.num_layers = layers
+            for l in range(layers):
+                for name, shape, init in decoder_layer_keys(l):
+                    _register(self, "wrapped_decoder." + name, shape, init)
+
+        def _translate(self, sd):
+            sd.pop("prenet.embed_positions.weights", None)
+            return sd
+
+    class SpeechT5TextDecoderPostnetMI355X(Holder):
+        """Parameter name of HF SpeechT5TextDecoderPostnet: ``lm_head.weight`` (no bias)."""
+
+        def __init__(self):
+            super().__init__(owner_ref)
+            _register(self, "lm_head.weight", (vocab, HIDDEN))
+
+    return SpeechT5DecoderWithTextPrenetMI355X(), SpeechT5TextDecoderPostnetMI355X()
+
+
+def position_ids(input_ids: torch.Tensor, past_key_values_length: int = 0) -> torch.Tensor:
+    """HF's create_position_ids_from_input_ids with padding_idx 1 (modeling_speecht5.py:337-351) -- the rule dec_embed_kernel
+    implements: a token's position is the count of non-pad tokens up to and including it, plus 1; <pad> maps to row 1 (zeros)."""
+    mask = input_ids.ne(PAD_TOKEN_ID).int()
+    return ((torch.cumsum(mask, dim=1).type_as(mask) + past_key_values_length) * mask).long() + PAD_TOKEN_ID
+
+
+def resolve_max_length(max_length=None, max_new_tokens=None) -> int:
+    """Total length (start token included) as HF's generate resolves it: ``max_new_tokens`` counts tokens after the start token and
+    wins over ``max_length``; neither given = HF's default for a default SpeechT5Config."""
+    if max_new_tokens is not None:
+        if int(max_new_tokens) < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        n = int(max_new_tokens) + 1
+    elif max_length is not None:
+        n = int(max_length)
+    else:
+        n = DEFAULT_MAX_LENGTH
+    if n < 2:
+        raise ValueError(f"max_length must be >= 2 (the start token and one generated token), got {n}")
+    if n > MAX_TEXT_POSITIONS:
+        raise ValueError(f"max_length {n} exceeds max_text_positions = {MAX_TEXT_POSITIONS}")
+    return n
+
+
+def check_generate_kwargs(kwargs: dict):
+    """Refuse what greedy search does not cover, by name; ``num_beams=1`` / ``do_sample=False`` are what it is and pass."""
+    for k, v in kwargs.items():
+        if k == "num_beams" and v in (None, 1):
+            continue
+        if k == "do_sample" and not v:
+            continue
+        if k in _UNSUPPORTED_GENERATE:
+            raise NotImplementedError(f"generate({k}=...) is not implemented: this decoder does greedy search from the start token only")
+        raise TypeError(f"generate() got an unexpected keyword argument '{k}'")
+
+
+class DecoderRuntime:
+    """Host side of loco_decoder_*: workspace ownership and argument marshalling for one encoder module's handle.
+
+    Single caller, one stream: the model keeps ONE workspace (grown on demand) and the library one pinned poll word per handle, so
+    calls of one model must be issued from one thread on one stream -- a call that grows the workspace frees the old one behind the
+    work already enqueued on that stream (the caching allocator's ordering), which holds for the current stream only."""
+
+    def __init__(self, encoder):
+        self.enc = encoder
+        self.lib = encoder._lib
+        self._workspace = None
+
+    def max_batch(self) -> int:
+        return int(self.lib.loco_decoder_max_batch())
+
+    def workspace(self, B, T, S, device):
+        need = int(self.lib.loco_decoder_workspace_bytes(self.enc._handle, B, T, S))
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._workspace
+
+    @staticmethod
+    def _stream(device):
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    def forward(self, enc_out, frames, ids, output_hidden_states=False):
+        B, T, _ = enc_out.shape
+        S = ids.shape[1]
+        if S > MAX_TEXT_POSITIONS:
+            raise ValueError(f"decoder_input_ids of {S} tokens exceed max_text_positions = {MAX_TEXT_POSITIONS}")
+        device = enc_out.device
+        ws = self.workspace(B, T, S, device)
+        vocab = self.enc._decoder_vocab
+        logits = torch.empty((B, S, vocab), dtype=torch.float32, device=device)
+        hs, hs_ptrs = None, None
+        if output_hidden_states:
+            hs = [torch.empty((B, S, HIDDEN), dtype=torch.float32, device=device) for _ in range(self.enc._decoder_layers + 1)]
+            hs_ptrs = (C.c_void_p * len(hs))(*[t.data_ptr() for t in hs])
+        _lib.check(self.lib.loco_decoder_forward(
+            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
+            C.c_void_p(ids.data_ptr()), S, C.c_void_p(logits.data_ptr()), hs_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
+            self._stream(device)), "loco_decoder_forward")
+        return logits, (tuple(hs) if hs is not None else None)
+
+    def generate(self, enc_out, frames, max_length, return_logits=False):
+        B, T, _ = enc_out.shape
+        device = enc_out.device
+        if B > self.max_batch():
+            raise ValueError(f"generate: {B} clips exceed the decode step's limit of {self.max_batch()} rows; split the batch")
+        ws = self.workspace(B, T, max_length, device)
+        vocab = self.enc._decoder_vocab
+        tokens = torch.empty((B, max_length), dtype=torch.int32)
+        lengths = torch.empty((B,), dtype=torch.int32)
+        steps = torch.zeros((max_length - 1, B, vocab), dtype=torch.float32, device=device) if return_logits else None
+        n = C.c_int32(0)
+        _lib.check(self.lib.loco_decoder_generate(
+            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
+            max_length, C.c_void_p(tokens.data_ptr()), C.c_void_p(lengths.data_ptr()), C.byref(n), C.c_void_p(steps.data_ptr()) if steps is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), self._stream(device)), "loco_decoder_generate")
+        S = int(n.value)
+        ids = tokens[:, :S].to(torch.long).to(device)
+        self.last_lengths = lengths
+        return (ids, steps[:S - 1]) if return_logits else ids

@@ -293,6 +293,11 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
         self._workspace = None
         self._sin_rows = 0
         self._taps = None
+        # further (key prefix, module) pairs whose tensors go to the same handle: the model's decoder halves (decoder.py); empty for an
+        # encoder-only model, which then loads exactly what it always has
+        self._extra_weights = []
+        self._decoder_layers = 0
+        self._decoder_vocab = 0
         # large batches run as two half-batches on two HIP streams (bit-identical, ~2 % faster: include/loco_asr.h,
         # loco_set_streams); set to 1 to keep everything on the caller's stream
         self.streams = 2
@@ -346,7 +351,7 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         if self._weights_dirty:
             self.drain()  # forwards still in flight on the slots' streams read the planes that are about to be rebuilt
-            for prefix, mod in (("prenet.", self.prenet), ("wrapped_encoder.", self.wrapped_encoder)):
+            for prefix, mod in [("prenet.", self.prenet), ("wrapped_encoder.", self.wrapped_encoder)] + list(self._extra_weights):
                 for name, p in mod.state_dict().items():
                     t = p.detach()
                     if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
@@ -362,6 +367,11 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             _lib.check(self._lib.loco_set_weight(self._handle, b"prenet.pos_sinusoidal_embed.weights",
                                                  C.c_void_p(tab.data_ptr()), shape, 2), "sinusoid table")
             self._sin_rows = rows
+        if self._weights_dirty and self._extra_weights:
+            from .decoder import MAX_TEXT_POSITIONS
+            tab = sinusoid_table(MAX_TEXT_POSITIONS + PAD_TOKEN_ID + 1).contiguous()  # HF's decoder table, bit for bit (452 rows)
+            _lib.check(self._lib.loco_set_weight(self._handle, b"decoder.prenet.embed_positions.weights", C.c_void_p(tab.data_ptr()),
+                                                 (C.c_int64 * 2)(tab.shape[0], HIDDEN), 2), "decoder position table")
         if self._weights_dirty:
             _lib.check(self._lib.loco_finalize_weights(self._handle, stream), "finalize_weights")
             self._weights_dirty = False
@@ -705,27 +715,104 @@ def bind_attention_outputs(lib, handle, layers: int, B: int, T: int, device) -> 
     return probs
 
 
+def _decoder_layer_names(layer: int):
+    from .decoder import decoder_layer_keys
+    return decoder_layer_keys(layer)
+
+
 class _SpeechT5Core(nn.Module):
-    def __init__(self, encoder):
+    def __init__(self, encoder, decoder=None):
         super().__init__()
         self.encoder = encoder
+        if decoder is not None:
+            self.decoder = decoder
 
 
 class SpeechT5ForSpeechToTextMI355X(nn.Module):
-    """Only as much of HF's SpeechT5ForSpeechToText as the reference touches: ``.speecht5.encoder``."""
+    """HF's SpeechT5ForSpeechToText as the reference uses it: ``.speecht5.encoder`` (the embedding path), and -- when decoder
+    weights are loaded (``decoder_layers > 0``) -- ``.speecht5.decoder`` / ``.text_decoder_postnet`` with ``forward(...,
+    decoder_input_ids=...)`` and greedy ``generate`` (decoder.py).  An encoder-only model is exactly what it was."""
 
-    def __init__(self, layers: int = LAYERS, precision: str = "f16x3"):
+    def __init__(self, layers: int = LAYERS, precision: str = "f16x3", decoder_layers: int = 0, vocab_size: Optional[int] = None):
         super().__init__()
-        self.speecht5 = _SpeechT5Core(SpeechT5EncoderWithSpeechPrenetMI355X(layers, precision))
+        encoder = SpeechT5EncoderWithSpeechPrenetMI355X(layers, precision)
+        decoder = None
+        if decoder_layers:
+            from . import decoder as dec
+            ref = _Ref()
+            ref.obj = encoder
+            decoder, postnet = dec.make_decoder_modules(ref, decoder_layers, vocab_size or dec.TEXT_VOCAB)
+            encoder._extra_weights = [("decoder.", decoder), ("text_decoder_postnet.", postnet)]
+            encoder._decoder_layers = decoder_layers
+            encoder._decoder_vocab = vocab_size or dec.TEXT_VOCAB
+            self._decoder_runtime = dec.DecoderRuntime(encoder)
+        self.speecht5 = _SpeechT5Core(encoder, decoder)
+        if decoder is not None:
+            self.text_decoder_postnet = postnet
         self.eval()
+
+    @property
+    def has_decoder(self) -> bool:
+        return hasattr(self, "text_decoder_postnet")
+
+    def _require_decoder(self, what: str):
+        if not self.has_decoder:
+            why = getattr(self, "_no_decoder_reason", None)
+            raise RuntimeError(f"{what} needs the decoder, and this model was loaded without one: speecht5.decoder.* and "
+                               "text_decoder_postnet.lm_head.weight are missing (from_pretrained on a full speech-to-text checkpoint, or "
+                               "from_state_dicts(..., decoder_state_dict=, postnet_state_dict=))" + (f" -- {why}" if why else ""))
+
+    def _encode(self, input_values, attention_mask):
+        out = self.speecht5.encoder(input_values=input_values, attention_mask=attention_mask)
+        return out.last_hidden_state, self.speecht5.encoder.last_frames
+
+    @torch.no_grad()
+    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                decoder_input_ids: Optional[torch.Tensor] = None, output_hidden_states: Optional[bool] = None, **kwargs):
+        """``model(**audios, decoder_input_ids=ids)``: teacher-forced logits [B, S, vocab] and ``encoder_last_hidden_state``
+        (``output_hidden_states=True``: also the 7 ``decoder_hidden_states``).  Causal self-attention over the ids as given (no
+        decoder attention mask, as in the reference's calls); cross-attention over each clip's valid encoder frames."""
+        for k in kwargs:
+            if k in ("decoder_attention_mask", "labels", "past_key_values", "encoder_outputs", "use_cache", "output_attentions"):
+                raise NotImplementedError(f"forward({k}=...) is not implemented")
+            raise TypeError(f"forward() got an unexpected keyword argument '{k}'")
+        self._require_decoder("forward(decoder_input_ids=...)")
+        if decoder_input_ids is None:
+            raise ValueError("You have to specify `decoder_input_ids` (for embeddings alone call model.speecht5.encoder)")
+        from .decoder import Seq2SeqLMOutput
+        enc_out, frames = self._encode(input_values, attention_mask)
+        if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != enc_out.shape[0]:
+            raise ValueError(f"decoder_input_ids must be [batch, tokens] with batch {enc_out.shape[0]}, got {tuple(decoder_input_ids.shape)}")
+        ids = decoder_input_ids.to(device=enc_out.device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(enc_out.device):
+            logits, hidden = self._decoder_runtime.forward(enc_out, frames, ids, bool(output_hidden_states))
+        return Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden)
+
+    @torch.no_grad()
+    def generate(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
+                 max_new_tokens: Optional[int] = None, return_logits: bool = False, **kwargs):
+        """Greedy search as HF's ``generate`` runs it for this model: LongTensor [B, S] starting with decoder_start_token_id 2, a
+        row that has emitted </s> (2) is filled with <pad> (1), S = the longest row or ``max_length`` (total, start token included;
+        ``max_new_tokens`` counts the tokens after it).  ``return_logits=True``: also the logits [S - 1, B, vocab] each step chose from."""
+        from . import decoder as dec
+        dec.check_generate_kwargs(kwargs)
+        self._require_decoder("generate()")
+        n = dec.resolve_max_length(max_length, max_new_tokens)
+        enc_out, frames = self._encode(input_values, attention_mask)
+        with torch.cuda.device(enc_out.device):
+            return self._decoder_runtime.generate(enc_out, frames, n, return_logits)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):
         """``SpeechT5ForSpeechToText.from_pretrained(...)`` of the fine-tuned script (…finetuned…py:95) for a checkpoint ON
         DISK: a directory holding ``model.safetensors`` / ``pytorch_model.bin`` (or their sharded index), one such file, or a hub
         name that is already in the local HuggingFace cache -- nothing is ever downloaded.  Keeps ``speecht5.encoder.prenet.*``
-        and ``speecht5.encoder.wrapped_encoder.*`` (either spelling of the weight-normed positional conv), takes the layer count
-        from the keys, and fails BY NAME on anything the encoder needs and the file lacks (load_state_dict(strict=True))."""
+        and ``speecht5.encoder.wrapped_encoder.*`` (either spelling of the weight-normed positional conv) and, when the file has
+        them, ``speecht5.decoder.*`` and ``text_decoder_postnet.*`` (the tied embedding / lm_head pair may be present once); takes
+        the layer counts from the keys, and fails BY NAME on anything the encoder needs and the file lacks
+        (load_state_dict(strict=True)).  The decoder is kept only when the file holds a COMPLETE one (checkpoint_map.decoder_problem):
+        a file with the encoder and stray or partial decoder tensors gives the encoder-only model it always gave, and ``generate`` /
+        ``decoder_input_ids`` then raise with the name of the first decoder tensor that is missing or misshapen."""
         import re
         from . import checkpoint_map
         checkpoint_map.check_hf_config(str(pretrained_model_name_or_path))
@@ -733,12 +820,42 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         ids = [int(m_.group(1)) for m_ in (re.match(r"layers\.(\d+)\.", k) for k in enc) if m_]
         if not ids:
             raise KeyError(f"{pretrained_model_name_or_path}: no speecht5.encoder.wrapped_encoder.layers.N.* tensors")
-        return cls.from_state_dicts(pre, enc, layers=max(ids) + 1, precision=precision)
+        dec_sd, post_sd = checkpoint_map.load_hf_decoder(str(pretrained_model_name_or_path))
+        problem = checkpoint_map.decoder_problem(dec_sd, post_sd)
+        if problem is not None:  # no (complete) decoder in the file: the encoder-only model this call has always returned
+            model = cls.from_state_dicts(pre, enc, layers=max(ids) + 1, precision=precision)
+            model._no_decoder_reason = f"{pretrained_model_name_or_path}: {problem}"
+            return model
+        known = {"prenet.embed_tokens.weight"} | {"wrapped_decoder." + n for l in range(64) for n, _, _ in _decoder_layer_names(l)}
+        dec_sd = {k: v for k, v in dec_sd.items() if k in known}  # e.g. a stray wrapped_decoder.layer_norm of another architecture
+        return cls.from_state_dicts(pre, enc, layers=max(ids) + 1, precision=precision, decoder_state_dict=dec_sd,
+                                    postnet_state_dict={k: v for k, v in post_sd.items() if k == "lm_head.weight"})
 
     @classmethod
-    def from_state_dicts(cls, prenet_state_dict, encoder_state_dict, layers: int = LAYERS, precision: str = "f16x3"):
-        """What the base script does after from_pretrained (…base…py:98-100), minus the hub download."""
-        model = cls(layers, precision)
+    def from_state_dicts(cls, prenet_state_dict, encoder_state_dict, layers: int = LAYERS, precision: str = "f16x3",
+                         decoder_state_dict=None, postnet_state_dict=None):
+        """What the base script does after from_pretrained (…base…py:98-100), minus the hub download.  With ``decoder_state_dict``
+        (keys ``prenet.embed_tokens.weight``, ``wrapped_decoder.layers.N.*``) and / or ``postnet_state_dict`` (``lm_head.weight``)
+        the model also decodes; of the tied pair embed_tokens / lm_head one may be absent (it is taken from the other)."""
+        import re
+        dec_layers, vocab = 0, None
+        if decoder_state_dict is not None or postnet_state_dict is not None:
+            decoder_state_dict = dict(decoder_state_dict or {})
+            postnet_state_dict = dict(postnet_state_dict or {})
+            emb, head = decoder_state_dict.get("prenet.embed_tokens.weight"), postnet_state_dict.get("lm_head.weight")
+            if emb is None and head is None:
+                raise KeyError("decoder weights without prenet.embed_tokens.weight or lm_head.weight (the tied pair: one of them is needed)")
+            decoder_state_dict.setdefault("prenet.embed_tokens.weight", head)
+            postnet_state_dict.setdefault("lm_head.weight", emb)
+            ids = [int(m_.group(1)) for m_ in (re.match(r"wrapped_decoder\.layers\.(\d+)\.", k) for k in decoder_state_dict) if m_]
+            if not ids:
+                raise KeyError("decoder_state_dict: no wrapped_decoder.layers.N.* tensors")
+            dec_layers, vocab = max(ids) + 1, int(decoder_state_dict["prenet.embed_tokens.weight"].shape[0])
+        model = cls(layers, precision, decoder_layers=dec_layers, vocab_size=vocab)
         model.speecht5.encoder.wrapped_encoder.load_state_dict(encoder_state_dict)
         model.speecht5.encoder.prenet.load_state_dict(prenet_state_dict)
+        if dec_layers:
+            as_t = lambda d: {k: (v if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in d.items()}  # noqa: E731
+            model.speecht5.decoder.load_state_dict(as_t(decoder_state_dict))
+            model.text_decoder_postnet.load_state_dict(as_t(postnet_state_dict))
         return model

@@ -285,3 +285,46 @@ def head_batch(B: int, T: int, tag: str):
     c = hashed_uniform(f"head/cls/{tag}", (B,), 11)
     cls = np.clip(((c + 1) / 2 * 101).astype(np.int64), 0, 100)
     return x, np.eye(101, dtype=np.int64)[cls], lens
+
+
+# ---- text decoder (SpeechT5DecoderWithTextPrenet + SpeechT5TextDecoderPostnet) ---------------------------------------------------
+DECODER_LAYERS = 6
+
+
+def decoder_state_dict(seed: int = 0, layers: int = DECODER_LAYERS) -> dict[str, np.ndarray]:
+    """numpy fp32 decoder weights under HF's names below ``speecht5.``: ``decoder.prenet.embed_tokens.weight``,
+    ``decoder.wrapped_decoder.layers.N.*`` and ``text_decoder_postnet.lm_head.weight`` -- the last two of the first tied, as
+    ``tie_word_embeddings=True`` has them (the SAME array).  Scales as for the encoder: attention logits of standard deviation ~2
+    (self and cross), LayerNorm affines that are not the identity, an embedding of the size of the sinusoid positions, sub-layers
+    half the size of the residual they are added to (token and position survive to the top) and a LAST feed-forward four times its
+    residual: with the tied lm_head anything weaker lets the input token's own embedding ride the residual stream to the logits,
+    and greedy search then repeats one token for ever (no </s>, nothing to test)."""
+    sd: dict[str, np.ndarray] = {}
+    emb = _w("decoder.prenet.embed_tokens.weight", (TEXT_VOCAB, HIDDEN), 0.35, seed)
+    sd["decoder.prenet.embed_tokens.weight"] = emb
+    for l in range(layers):
+        b = f"decoder.wrapped_decoder.layers.{l}."
+        for attn in ("self_attn", "encoder_attn"):
+            for proj, std in (("q_proj", 1.5), ("k_proj", 1.5), ("v_proj", 1.0), ("out_proj", 0.5)):
+                n = f"{b}{attn}.{proj}."
+                sd[n + "weight"] = _w(n + "weight", (HIDDEN, HIDDEN), std / math.sqrt(HIDDEN), seed)
+                sd[n + "bias"] = _w(n + "bias", (HIDDEN,), 0.02, seed)
+        for ln in ("self_attn_layer_norm", "encoder_attn_layer_norm", "final_layer_norm"):
+            sd[f"{b}{ln}.weight"] = _w(f"{b}{ln}.weight", (HIDDEN,), 0.1, seed, 1.0)
+            sd[f"{b}{ln}.bias"] = _w(f"{b}{ln}.bias", (HIDDEN,), 0.1, seed)
+        n = f"{b}feed_forward.intermediate_dense."
+        sd[n + "weight"] = _w(n + "weight", (FFN, HIDDEN), 1.2 / math.sqrt(HIDDEN), seed)
+        sd[n + "bias"] = _w(n + "bias", (FFN,), 0.02, seed)
+        n = f"{b}feed_forward.output_dense."
+        sd[n + "weight"] = _w(n + "weight", (HIDDEN, FFN), (4.0 if l == layers - 1 else 0.5) / math.sqrt(FFN), seed)
+        sd[n + "bias"] = _w(n + "bias", (HIDDEN,), 0.02, seed)
+    sd["text_decoder_postnet.lm_head.weight"] = emb
+    return sd
+
+
+def split_decoder_state_dict(sd: dict):
+    """(decoder_sd, postnet_sd) with the prefixes ``decoder.`` / ``text_decoder_postnet.`` stripped: what
+    ``model.speecht5.decoder.load_state_dict`` and ``model.text_decoder_postnet.load_state_dict`` take."""
+    dec = {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
+    post = {k[len("text_decoder_postnet."):]: v for k, v in sd.items() if k.startswith("text_decoder_postnet.")}
+    return dec, post

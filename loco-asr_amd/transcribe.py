@@ -1,0 +1,131 @@
+"""Greedy transcription CLI: ``python -m loco-asr_amd.transcribe`` writes one JSON line per utterance, {"id", "token_ids"} (and
+"text" when a SentencePiece model for ``--tokenizer`` is found ON DISK; nothing is ever fetched).
+
+Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  Small on
+purpose: no data parallelism, no packing.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
+same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
+``--synthetic N`` seeded clips; weights: ``--pretrained DIR`` (a HuggingFace speech-to-text checkpoint directory with the decoder)
+or ``--random-init`` (the deterministic synthetic weights).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import synth
+from .decoder import EOS_TOKEN_ID, PAD_TOKEN_ID
+from .encoder import SpeechT5ForSpeechToTextMI355X
+
+
+def load_tokenizer(path):
+    """A SentencePiece processor for ``path`` (an ``spm_char.model`` file or a directory holding one), or None."""
+    if not path:
+        return None
+    cand = [path, os.path.join(path, "spm_char.model")]
+    spm_file = next((c for c in cand if os.path.isfile(c)), None)
+    if spm_file is None:
+        return None
+    try:
+        import sentencepiece as spm
+    except ImportError:
+        return None
+    return spm.SentencePieceProcessor(model_file=spm_file)
+
+
+def strip_special(ids):
+    out = []
+    for t in ids[1:]:
+        if t == EOS_TOKEN_ID:
+            break
+        if t != PAD_TOKEN_ID:
+            out.append(int(t))
+    return out
+
+
+def gather_items(args):
+    """[(utterance id, audio path or None, samples for a synthetic clip)] in corpus order; exactly one input source."""
+    sources = [bool(args.split), bool(args.files), args.synthetic > 0]
+    if sum(sources) != 1:
+        raise SystemExit("give exactly one input: --split (with --data-path), audio FILES, or --synthetic N")
+    if args.split:
+        from .extract import read_slurp_split
+        return [(str(it[0]), it[2], 0) for it in read_slurp_split(args.data_path, args.split)]
+    if args.files:
+        return [(os.path.splitext(os.path.basename(f))[0], f, 0) for f in args.files]
+    lengths = synth.mixed_lengths(args.synthetic, int(args.synthetic_seconds * synth.SAMPLE_RATE))
+    return [(f"synthetic-{i:06d}", None, n) for i, n in enumerate(lengths)]
+
+
+def load_batch(items, first_index, processor, device):
+    """One reference batch: decoded (or synthesised) clips, padded to the longest and masked as the feature extractor does."""
+    from .extract import load_audio_16k
+    clips = [synth.clip(first_index + i, n) if path is None else load_audio_16k(path, device=device) for i, (_, path, n) in enumerate(items)]
+    if any(torch.is_tensor(c) and c.is_cuda for c in clips):  # a resampled clip lives on the device: pad the whole batch there
+        clips = [c if torch.is_tensor(c) else torch.from_numpy(np.asarray(c)).to(device) for c in clips]
+    return processor(audio=clips, sampling_rate=synth.SAMPLE_RATE, return_tensors="pt", padding="longest")
+
+
+def build_model(args):
+    if args.pretrained:
+        model = SpeechT5ForSpeechToTextMI355X.from_pretrained(args.pretrained, precision=args.precision)
+    elif args.random_init:
+        t = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
+        pre, enc = synth.split_state_dict(synth.encoder_state_dict(0))
+        dec, post = synth.split_decoder_state_dict(synth.decoder_state_dict(0))
+        model = SpeechT5ForSpeechToTextMI355X.from_state_dicts(t(pre), t(enc), precision=args.precision, decoder_state_dict=t(dec),
+                                                                postnet_state_dict=t(post))
+    else:
+        raise SystemExit("give --pretrained DIR or --random-init")
+    if not model.has_decoder:
+        raise SystemExit(f"{args.pretrained}: the checkpoint has no speecht5.decoder.* / text_decoder_postnet.* tensors: nothing to transcribe with")
+    return model.to("cuda")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m loco-asr_amd.transcribe", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--pretrained", default=None, metavar="DIR", help="HuggingFace SpeechT5ForSpeechToText checkpoint on disk (never downloaded)")
+    ap.add_argument("--random-init", action="store_true", help="deterministic synthetic weights (no checkpoint available)")
+    ap.add_argument("files", nargs="*", metavar="FILE", help="audio files (.wav / .flac) to transcribe, in this order")
+    ap.add_argument("--data-path", default="slurp", help="SLURP root (dataset/slurp/<split>.jsonl, audio/slurp_real), as extract.py")
+    ap.add_argument("--split", "-s", choices=["train", "devel", "test", "train_synthetic"], default=None)
+    ap.add_argument("--do-normalize", action="store_true", help="zero-mean unit-variance waveforms, as the HF feature extractor's do_normalize")
+    ap.add_argument("--synthetic", type=int, default=0, help="transcribe N seeded synthetic clips")
+    ap.add_argument("--synthetic-seconds", type=float, default=5.0)
+    ap.add_argument("--batch-size", type=int, default=2, help="utterances per generate call (the reference's loop: 2)")
+    ap.add_argument("--max-length", type=int, default=100, help="total tokens per utterance, start token included (the reference's notebooks: 100)")
+    ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
+    ap.add_argument("--precision", choices=["f16x3", "f32", "f16x2"], default="f16x3", help="arithmetic of the ENCODER (the decoder is fp32)")
+    ap.add_argument("--out", default="-", help="JSON-lines file, - = stdout")
+    args = ap.parse_args(argv)
+    if args.batch_size < 1:
+        raise SystemExit("--batch-size must be >= 1")
+    items = gather_items(args)
+    from .feature_extractor import SpeechT5FeatureExtractorMI355X
+    processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
+    model = build_model(args)
+    tok = load_tokenizer(args.tokenizer)
+    device = torch.device("cuda", torch.cuda.current_device())
+    fh = sys.stdout if args.out == "-" else open(args.out, "w")
+    try:
+        for b0 in range(0, len(items), args.batch_size):
+            chunk = items[b0:b0 + args.batch_size]
+            f = load_batch(chunk, b0, processor, device)
+            ids = model.generate(f["input_values"].to(device), f["attention_mask"].to(device), max_length=args.max_length).cpu().tolist()
+            for (uid, _, _), row in zip(chunk, ids):
+                rec = {"id": uid, "token_ids": row}
+                if tok is not None:
+                    rec["text"] = tok.decode(strip_special(row))
+                fh.write(json.dumps(rec) + "\n")
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
