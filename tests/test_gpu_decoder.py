@@ -184,7 +184,7 @@ def test_batch_above_cap(gu):
 
 # ---- 5. operators ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("K", [768, 3072])
-@pytest.mark.parametrize("M", [1, 2, 17, 64])
+@pytest.mark.parametrize("M", [1, 2, 3, 17, 63, 64])  # 3 and 63: M mod 4 = 3, the remainder of the 4-row register pass
 @pytest.mark.parametrize("epi", [0, 1, 2])
 def test_op_skinny_gemm(gu, M, K, epi):
     N = {768: 2304, 3072: 81}[K] if epi != 1 else 3072 if K == 768 else 768
@@ -206,6 +206,34 @@ def test_op_skinny_gemm(gu, M, K, epi):
     r = gu.rel_l2(c, ref)
     record_figure("op_skinny_gemm", M=M, N=N, K=K, epilogue=epi, rel_l2=r)
     assert r <= BAR_GEMM, r
+
+
+@pytest.mark.parametrize("M,K,epi", [(63, 768, 2), (3, 3072, 2), (17, 768, 1)])
+def test_op_skinny_gemm_strided(gu, M, K, epi):
+    """Row strides wider than the rows (lda > K, ldr > N, ldc > N): the gap columns of A and R hold values that would show in the
+    result if read, the gap columns of C a sentinel that must stay."""
+    N = 81 if K == 3072 else 2304
+    lda, ldr, ldc = K + 8, N + 5, N + 7  # lda stays a multiple of 4 floats (the kernel's 16-byte loads)
+    hu = gu.la.synth.hashed_uniform
+    A = hu(f"sgs/A/{M}/{K}", (M, lda), 3) * np.float32(1.7)
+    W = hu(f"sgs/W/{N}/{K}", (N, K), 3) * np.float32(2.0 / np.sqrt(K))
+    bias = hu(f"sgs/b/{N}", (N,), 3) * np.float32(0.3)
+    R = hu(f"sgs/R/{M}/{N}", (M, ldr), 3)
+    ref = torch.from_numpy(A[:, :K]).double() @ torch.from_numpy(W).double().T + torch.from_numpy(bias).double()
+    if epi == 1:
+        ref = torch.nn.functional.gelu(ref)
+    if epi == 2:
+        ref = ref + torch.from_numpy(R[:, :N]).double()
+    a, w, b_, r_ = gu.dev(A), gu.dev(W), gu.dev(bias), gu.dev(R)
+    sentinel = -12345.5
+    c = torch.full((M, ldc), sentinel, device="cuda")
+    gu.check(gu.lib().loco_op_skinny_gemm(gu.ptr(a), lda, gu.ptr(w), K, gu.ptr(b_), gu.ptr(r_) if epi == 2 else None, ldr, gu.ptr(c), ldc, M, N, K, epi,
+                                          gu.stream()), "skinny_gemm")
+    torch.cuda.synchronize()
+    r = gu.rel_l2(c[:, :N], ref)
+    record_figure("op_skinny_gemm_strided", M=M, N=N, K=K, epilogue=epi, lda=lda, ldr=ldr, ldc=ldc, rel_l2=r)
+    assert r <= BAR_GEMM, r
+    assert bool((c[:, N:] == sentinel).all())
 
 
 def _attn_ref(q, k, v, counts, causal, offset, scale):
