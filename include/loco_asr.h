@@ -543,6 +543,51 @@ size_t loco_decoder_attention_scratch_bytes(int32_t B, int32_t Sq, int32_t Tk);
 int loco_op_decoder_attention(const float* q, const float* k, const float* v, const int32_t* key_counts, float* out, int32_t B, int32_t Sq,
                               int32_t Tk, int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- decoder slot pool: greedy decoding of a corpus, finished rows refilled -------------------------------------------------------
+ * loco_decoder_generate carries every row of one batch until the longest has ended.  A pool has `slots` decoder rows that each sit at
+ * their OWN position: a slot is free, open (decoding one utterance) or finished (its tokens wait to be read); a finished or free slot
+ * is handed the next utterance by loco_decoder_pool_admit while the other slots go on.  An utterance's tokens and step logits are a
+ * pure function of its own encoder rows, frame count and cap -- bit for bit, whichever utterances share the pool, whichever slot it
+ * sits in and however the launches were sized: the cross k|v of a clip is a product of its own, and attention splits a key range at
+ * fixed key indices (multiples of 256), merged in split order.  (loco_decoder_generate keeps its own split rule and its bits; the two
+ * agree to the fp32 summation order, not bitwise.)
+ *   workspace   >= loco_decoder_pool_workspace_bytes(enc, slots, T_cap, S_max) bytes (device): slot state (position, cap, frames,
+ *               status, length), token buffer i32 [slots, S_max], cross k|v [slots, T_cap, layers, 1536], self k|v [layers, slots,
+ *               S_max, 1536], row buffers and scratch.  ALL state of a pool lives there: two pools of one handle may run side by
+ *               side.  Every call takes the same (slots, T_cap, S_max) the workspace was sized and initialised with.
+ *   loco_decoder_pool_init   every slot free.  Must precede the first admit.
+ *   loco_decoder_pool_admit  n clips into the slots slot_ids[0..n) (HOST, distinct): clip i's encoder rows are enc_out + i *
+ *               clip_stride floats (device, [enc_rows[i], 768] dense rows; clip_stride % 4 == 0); enc_rows i32 [n] HOST = rows
+ *               projected into the slot's cross k|v, enc_frames i32 [n] DEVICE (NULL: enc_rows) = valid frames, cross-attention sees
+ *               keys j < min(enc_frames[i], enc_rows[i]) and rows beyond are never read; caps i32 [n] HOST = the utterance's own
+ *               max_length (<s> included).  The slot restarts at <s>, position 0; nothing of its previous occupant is read again.
+ *               Reads the slots' status back (one stream synchronisation) to refuse an open slot.
+ *   loco_decoder_pool_step   one token for every open slot: slot r consumes token pos[r], writes k|v row pos[r] of its cache, attends
+ *               to its keys j <= pos[r] and its frames, appends the argmax (lowest index wins ties) at pos[r] + 1 and is finished when
+ *               that token is </s> (2) or pos[r] + 2 == cap[r].  Free and finished slots compute on zeros and write nothing.
+ *               max_pos >= pos[r] and max_frames >= frames[r] of every open slot size the launches (host-side bounds: no device
+ *               read); a slot beyond max_pos waits, keys beyond max_frames are not seen.  step_logits NULL or f32 [slots, V]
+ *               (device): this step's logits, rows of slots that are not open undefined but finite.  Asynchronous, reads no host
+ *               memory, a linear chain of launches.
+ *   loco_decoder_pool_poll   enqueue a copy of the poll block to host_block (caller-owned, pinned): i32 [4 + 2 slots] = [slots open, 0,
+ *               0, 0, status[slots] (0 free, 1 open, 2 finished), lengths[slots] (tokens written, <s> included)]
+ *   loco_decoder_pool_read   enqueue a copy of slot `slot`'s token row i32 [S_max] to tokens (HOST); its first lengths[slot] entries
+ *               are the utterance
+ * Errors: slots > loco_decoder_max_batch(), a clip of more than T_cap rows, a cap outside 2 .. S_max, S_max outside 2 .. 450:
+ * LOCO_E_INVALID naming the limit; admitting into an open slot, or a handle without decoder weights: LOCO_E_STATE; a workspace below
+ * loco_decoder_pool_workspace_bytes (which is 0 for arguments outside the limits or a handle without a decoder): LOCO_E_WORKSPACE. */
+size_t loco_decoder_pool_workspace_bytes(const loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max);
+int loco_decoder_pool_init(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, void* workspace, size_t workspace_bytes, void* stream);
+int loco_decoder_pool_admit(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, const int32_t* slot_ids, const float* enc_out,
+                            int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int loco_decoder_pool_step(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames, float* step_logits,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int loco_decoder_pool_poll(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t* host_block, const void* workspace,
+                           size_t workspace_bytes, void* stream);
+int loco_decoder_pool_read(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t slot, int32_t* tokens, const void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

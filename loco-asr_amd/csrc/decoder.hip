@@ -30,12 +30,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 // products each -- so that the longest rounding chain is a few dozen terms before the butterfly (K = 3072 meets the 5e-6 bar
 // of the operator tests with that blocking).  The ks waves of a column group meet in LDS and are added in slice order.
 // Workgroup = 4 waves = (4 / ks) column groups; grid.x covers N, grid.y blocks of 64 rows.
-template <int EPI>
+// ROWS (the slot pool's q | k|v product): row m of the C2 part goes to cache row c2_rows[m] of its own clip (C2 + m ldc2 + c2_rows[m]
+// c2_row_stride) and is dropped when c2_rows[m] < 0 -- the destination row comes from the device, not from a host scalar.
+template <int EPI, bool ROWS = false>
 __global__ __launch_bounds__(kSkinnyThreads) void skinny_gemm_kernel(const float* __restrict__ A, long lda, const float* __restrict__ W,
                                                                      long ldw, const float* __restrict__ bias,
                                                                      const float* __restrict__ R, long ldr, float* __restrict__ C,
                                                                      long ldc, float* __restrict__ C2, long ldc2, int nsplit, int M,
-                                                                     int N, int K, int ks) {
+                                                                     int N, int K, int ks, const int32_t* __restrict__ c2_rows = nullptr,
+                                                                     long c2_row_stride = 0) {
     __shared__ float red[4][kSkinnyMT * kSkinnyNC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slice = wave % ks, group = wave / ks, groups = 4 / ks;
@@ -54,6 +57,8 @@ __global__ __launch_bounds__(kSkinnyThreads) void skinny_gemm_kernel(const float
         for (int r = 0; r < kSkinnyMT; ++r)
 #pragma unroll
             for (int c = 0; c < kSkinnyNC; ++c) acc[r][c] = 0.f;
+        int c2_row = 0;  // ROWS: read before the K loop, so that the epilogue does not wait for it
+        if (ROWS) c2_row = c2_rows[min(m0 + (lane % (kSkinnyMT * kSkinnyNC)) / kSkinnyNC, M - 1)];
         for (int ch = slice; ch < chunks; ch += ks) {
             const int k = ch * kSkinnyKC;
             f32x4 wv[kSkinnyNC], av[kSkinnyMT];
@@ -92,8 +97,10 @@ __global__ __launch_bounds__(kSkinnyThreads) void skinny_gemm_kernel(const float
                 if (EPI == kEpiResidual) v += R[(long)m * ldr + n];
                 if (n < nsplit)
                     C[(long)m * ldc + n] = v;
-                else
+                else if (!ROWS)
                     C2[(long)m * ldc2 + (n - nsplit)] = v;
+                else if (c2_row >= 0)
+                    C2[(long)m * ldc2 + (long)c2_row * c2_row_stride + (n - nsplit)] = v;
             }
         }
         __syncthreads();
@@ -325,6 +332,19 @@ hipError_t launch_skinny_gemm(const float* A, long lda, const float* W, long ldw
     return hipGetLastError();
 }
 
+hipError_t launch_skinny_gemm_rows(const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc, float* C2,
+                                   long ldc2, const int32_t* c2_rows, long c2_row_stride, int nsplit, int M, int N, int K, hipStream_t s) {
+    if (M <= 0 || M > kSkinnyMaxM || N <= 0 || K <= 0 || K % kSkinnyKC != 0 || nsplit < 0 || nsplit > N) return hipErrorInvalidValue;
+    if ((lda | ldw) & 3) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return hipErrorInvalidValue;
+    if (!C || !C2 || !c2_rows) return hipErrorInvalidValue;
+    const int ks = skinny_gemm_slices(N, K), cols = (4 / ks) * kSkinnyNC;
+    const dim3 grid((unsigned)((N + cols - 1) / cols), 1), block(kSkinnyThreads);
+    hipLaunchKernelGGL((skinny_gemm_kernel<kEpiNone, true>), grid, block, 0, s, A, lda, W, ldw, bias, nullptr, 0, C, ldc, C2, ldc2, nsplit, M, N, K, ks,
+                       c2_rows, c2_row_stride);
+    return hipGetLastError();
+}
+
 // Key splits of one attention launch: a pure function of the shape (so that a step is reproducible), at most ceil(Tk / 256)
 // and at most kDecAttnMaxSplit of them (a split's key range is a multiple of 64 and never shorter than 128 keys), enough waves for ~4 per SIMD of the chip when the key range allows it.
 int dec_attention_splits(int B, int Sq, int Tk) {
@@ -356,6 +376,33 @@ hipError_t launch_dec_attention(const float* q, long ldq, long sq, const float* 
     a.keys_per_split = ((Tk + a.nsplit - 1) / a.nsplit + 63) / 64 * 64;
     const long rows = (long)B * kHeads * Sq, units = rows * a.nsplit;
     if (units > 0x7fffffffL * 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dec_attention_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);
+    if (a.nsplit > 1) hipLaunchKernelGGL(dec_attention_combine, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The slot pool's attention (one query per slot): split s covers keys [256 s, 256 s + 256) whatever the launch's key bound is, and the
+// splits are merged in split order with empty ones skipped, so a slot's output is a pure function of its own key count -- not of the
+// slots beside it nor of the bound the host sized the launch by.  One launched split writes its result directly: the same bits as the
+// merge of one split (weight exp(0) = 1).  Tk_bound >= every kcount[b] that is to be seen in full; scratch >= dec_pool_attention_scratch_bytes.
+int dec_pool_attention_splits(int Tk_bound) { return Tk_bound <= kDecPoolSplitKeys ? 1 : (Tk_bound + kDecPoolSplitKeys - 1) / kDecPoolSplitKeys; }
+
+size_t dec_pool_attention_scratch_bytes(int slots, int Tk_bound) {
+    return (size_t)slots * kHeads * dec_pool_attention_splits(Tk_bound) * 66 * sizeof(float);
+}
+
+hipError_t launch_dec_pool_attention(const float* q, const float* k, long ldk, long sk, const float* v, const int32_t* kcount, float* out,
+                                     int slots, int Tk_bound, float* scratch, hipStream_t s) {
+    if (slots <= 0 || slots > kSkinnyMaxM || Tk_bound <= 0 || !q || !k || !v || !out || !kcount || !scratch) return hipErrorInvalidValue;
+    if ((ldk | sk) & 3) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) return hipErrorInvalidValue;
+    DecAttnArgs a{};
+    a.q = q, a.k = k, a.v = v, a.kcount = kcount, a.out = out, a.part = scratch;
+    a.ldq = kHidden, a.ldk = ldk, a.ldv = ldk, a.ldo = kHidden, a.sq = kHidden, a.sk = sk, a.sv = sk, a.so = kHidden;
+    a.B = slots, a.Sq = 1, a.Tk = Tk_bound, a.causal = 0, a.causal_offset = 0, a.scale = 1.0f;
+    a.nsplit = dec_pool_attention_splits(Tk_bound);
+    a.keys_per_split = kDecPoolSplitKeys;
+    const long rows = (long)slots * kHeads, units = rows * a.nsplit;
     hipLaunchKernelGGL(dec_attention_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);
     if (a.nsplit > 1) hipLaunchKernelGGL(dec_attention_combine, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
     return hipGetLastError();

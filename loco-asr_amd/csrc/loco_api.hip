@@ -2227,6 +2227,194 @@ int loco_decoder_generate(loco_encoder* e, const float* enc_out, const int32_t* 
     return LOCO_OK;
 }
 
+// ---- decoder slot pool ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// Workspace of one pool (caller-owned): the slot state first (the poll block -- [0] slots open, [4, 4 + slots) status, then lengths --
+// is one contiguous run), the caches, then the step's row buffers and the attention scratch.
+struct PoolPlan {
+    int slots, T, S, L;
+    size_t off_poll, off_pos, off_cap, off_frames, off_counts, off_tokens, off_nonpad, off_cross, off_self, off_x0, off_x1, off_tmp, off_q, off_ctx,
+        off_ffn, off_logits, off_attn, total;
+};
+
+void make_pool_plan(int layers, int slots, int T, int S, PoolPlan& p) {
+    p.slots = slots, p.T = T, p.S = S, p.L = layers;
+    const size_t f = sizeof(float), i = sizeof(int32_t);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        size_t at = o;
+        o += align_up(bytes);
+        return at;
+    };
+    p.off_poll = take((size_t)(4 + 2 * slots) * i);
+    p.off_pos = take(slots * i);
+    p.off_cap = take(slots * i);
+    p.off_frames = take(slots * i);
+    p.off_counts = take((size_t)3 * slots * i);  // self key counts, cross key counts, cache rows of the step
+    p.off_tokens = take((size_t)slots * S * i);
+    p.off_nonpad = take((size_t)2 * slots * i);  // the token each slot consumes next and its running non-pad count
+    p.off_cross = take((size_t)slots * T * p.L * 2 * kHidden * f);  // [slots][T_cap][layers][k | v]
+    p.off_self = take((size_t)p.L * slots * S * 2 * kHidden * f);   // [layers][slots][S_max][k | v]
+    p.off_x0 = take((size_t)slots * kHidden * f);
+    p.off_x1 = take((size_t)slots * kHidden * f);
+    p.off_tmp = take((size_t)slots * kHidden * f);
+    p.off_q = take((size_t)slots * kHidden * f);
+    p.off_ctx = take((size_t)slots * kHidden * f);
+    p.off_ffn = take((size_t)slots * kFfn * f);
+    p.off_logits = take((size_t)slots * 128 * f);
+    p.off_attn = take(dec_pool_attention_scratch_bytes(slots, T > S ? T : S));
+    p.total = o;
+}
+
+PoolState pool_state(const PoolPlan& p, char* ws) {
+    auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    PoolState st{};
+    st.poll = I(p.off_poll), st.status = st.poll + 4, st.lengths = st.status + p.slots;
+    st.pos = I(p.off_pos), st.cap = I(p.off_cap), st.frames = I(p.off_frames);
+    st.self_count = I(p.off_counts), st.cross_count = st.self_count + p.slots, st.kv_row = st.cross_count + p.slots;
+    st.tokens = I(p.off_tokens), st.cur = I(p.off_nonpad), st.cnt = st.cur + p.slots;
+    st.slots = p.slots, st.S_max = p.S, st.T_cap = p.T;
+    return st;
+}
+
+int pool_check(const loco_encoder* e, const char* fn, int slots, int T, int S, const void* ws, size_t bytes, PoolPlan& p) {
+    if (!e) return fail(LOCO_E_INVALID, "%s: null encoder", fn);
+    if (!e->finalized || !e->dec.ready)
+        return fail(LOCO_E_STATE, "%s: the handle has no decoder weights (decoder.prenet.*, decoder.wrapped_decoder.*, text_decoder_postnet.*) or "
+                                  "loco_finalize_weights has not run", fn);
+    if (slots <= 0 || T <= 0) return fail(LOCO_E_INVALID, "%s: slots and T_cap must be positive", fn);
+    if (slots > kSkinnyMaxM) return fail(LOCO_E_INVALID, "%s: %d slots exceed the decode step's limit of %d rows", fn, slots, kSkinnyMaxM);
+    if (S < 2 || S > kDecMaxPositions)
+        return fail(LOCO_E_INVALID, "%s: S_max = %d is outside 2 .. max_text_positions = %d", fn, S, kDecMaxPositions);
+    if (!ws) return fail(LOCO_E_INVALID, "%s: null workspace", fn);
+    make_pool_plan(e->dec.layers, slots, T, S, p);
+    if (bytes < p.total) return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, bytes, p.total);
+    return LOCO_OK;
+}
+
+}  // namespace
+
+size_t loco_decoder_pool_workspace_bytes(const loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max) {
+    if (!e || slots <= 0 || slots > kSkinnyMaxM || T_cap <= 0 || S_max < 2 || S_max > kDecMaxPositions) return 0;
+    if (!loco_has_decoder(e)) return 0;
+    PoolPlan p;
+    make_pool_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, p);
+    return p.total;
+}
+
+int loco_decoder_pool_init(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, void* workspace, size_t workspace_bytes, void* stream) {
+    PoolPlan p;
+    DEC_TRY(pool_check(e, "loco_decoder_pool_init", slots, T_cap, S_max, workspace, workspace_bytes, p));
+    HIP_TRY(launch_pool_init(pool_state(p, static_cast<char*>(workspace)), (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_admit(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, const int32_t* slot_ids, const float* enc_out,
+                            int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_admit";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (n <= 0 || n > slots) return fail(LOCO_E_INVALID, "%s: %d clips for a pool of %d slots", fn, n, slots);
+    if (!slot_ids || !enc_out || !enc_rows || !caps) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
+        return fail(LOCO_E_INVALID, "%s: enc_out and the clip stride must be 16-byte aligned", fn);
+    PoolAdmit a{};
+    a.n = n;
+    unsigned long long seen = 0;
+    for (int i = 0; i < n; ++i) {
+        if (slot_ids[i] < 0 || slot_ids[i] >= slots) return fail(LOCO_E_INVALID, "%s: slot %d of a pool of %d slots", fn, slot_ids[i], slots);
+        if (seen >> slot_ids[i] & 1) return fail(LOCO_E_INVALID, "%s: slot %d is named twice", fn, slot_ids[i]);
+        seen |= 1ull << slot_ids[i];
+        if (enc_rows[i] < 1 || enc_rows[i] > T_cap)
+            return fail(LOCO_E_INVALID, "%s: clip %d has %d encoder rows, the pool holds 1 .. T_cap = %d per slot", fn, i, enc_rows[i], T_cap);
+        if (n > 1 && clip_stride < (int64_t)enc_rows[i] * kHidden)  // clips would overlap in enc_out
+            return fail(LOCO_E_INVALID, "%s: clip stride %lld is shorter than clip %d's %d rows", fn, (long long)clip_stride, i, enc_rows[i]);
+        if (caps[i] < 2 || caps[i] > S_max) return fail(LOCO_E_INVALID, "%s: clip %d has cap %d, outside 2 .. S_max = %d", fn, i, caps[i], S_max);
+        a.slot[i] = slot_ids[i], a.cap[i] = caps[i], a.rows[i] = enc_rows[i];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    // a slot that is open may not be overwritten: the slots' status is read back (the one place the pool waits for the stream; the
+    // caller admits after a poll, when the stream is idle anyway)
+    std::vector<int32_t> status(slots);
+    HIP_TRY(hipMemcpyAsync(status.data(), st.status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i)
+        if (status[slot_ids[i]] == kPoolOpen) return fail(LOCO_E_STATE, "%s: slot %d is open (its utterance has not finished)", fn, slot_ids[i]);
+    // cross-attention k|v of every layer, one exact-fp32 product per clip into the slot's own region: the rows of a clip are the same
+    // bits whichever clips are admitted beside it
+    const int N = p.L * 2 * kHidden;
+    for (int i = 0; i < n; ++i)
+        DEC_TRY(run_gemm(e, s, enc_out + (size_t)i * clip_stride, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0,
+                         reinterpret_cast<float*>(ws + p.off_cross) + (size_t)slot_ids[i] * T_cap * N, N, enc_rows[i], N, kHidden, kEpiNone));
+    HIP_TRY(launch_pool_admit(st, a, enc_frames, kDecStartToken, s));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_step(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames, float* step_logits,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_step";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (max_pos < 0 || max_pos + 1 >= S_max) return fail(LOCO_E_INVALID, "%s: position bound %d writes token %d of a buffer of %d", fn, max_pos, max_pos + 1, S_max);
+    if (max_frames < 1 || max_frames > T_cap) return fail(LOCO_E_INVALID, "%s: frame bound %d is outside 1 .. T_cap = %d", fn, max_frames, T_cap);
+    const DecoderW& d = e->dec;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    float *x0 = F(p.off_x0), *x1 = F(p.off_x1), *tmp = F(p.off_tmp), *q = F(p.off_q), *ctx = F(p.off_ctx), *ffn = F(p.off_ffn), *scr = F(p.off_attn);
+    float* logits = step_logits ? step_logits : F(p.off_logits);
+    const long ld_cross = (long)p.L * 2 * kHidden, ld_self = 2 * kHidden;
+    const int B = slots;
+    HIP_TRY(launch_pool_embed(st, d.embed, d.vocab, d.pos_tab, d.pos_rows, x0, max_pos, max_frames, s));
+    for (int l = 0; l < p.L; ++l) {
+        const DecLayerW& lw = d.L[l];
+        float* cache = F(p.off_self) + (size_t)l * B * p.S * ld_self;
+        // q -> row buffer, k|v -> row pos[r] of slot r's cache
+        HIP_TRY(launch_skinny_gemm_rows(x0, kHidden, lw.wqkv, kHidden, lw.bqkv, q, kHidden, cache, (long)p.S * ld_self, st.kv_row, ld_self, kHidden, B,
+                                        kQkv, kHidden, s));
+        HIP_TRY(launch_dec_pool_attention(q, cache, ld_self, (long)p.S * ld_self, cache + kHidden, st.self_count, ctx, B, max_pos + 1, scr, s));
+        DEC_TRY(run_skinny(s, ctx, lw.self_out, x0, tmp, B, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.self_ln.w, lw.self_ln.b, x1, B, kHidden));
+        DEC_TRY(run_skinny(s, x1, WB{lw.wcq, lw.bcq}, nullptr, q, B, kHidden, kHidden, kEpiNone));
+        const float* ck = F(p.off_cross) + (size_t)l * 2 * kHidden;
+        HIP_TRY(launch_dec_pool_attention(q, ck, ld_cross, (long)p.T * ld_cross, ck + kHidden, st.cross_count, ctx, B, max_frames, scr, s));
+        DEC_TRY(run_skinny(s, ctx, lw.cross_out, x1, tmp, B, kHidden, kHidden, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.cross_ln.w, lw.cross_ln.b, x0, B, kHidden));
+        DEC_TRY(run_skinny(s, x0, lw.ffn_in, nullptr, ffn, B, kFfn, kHidden, kEpiGelu));
+        DEC_TRY(run_skinny(s, ffn, lw.ffn_out, x0, tmp, B, kHidden, kFfn, kEpiResidual));
+        DEC_TRY(run_ln(e, s, tmp, lw.final_ln.w, lw.final_ln.b, x0, B, kHidden));
+    }
+    DEC_TRY(run_skinny(s, x0, WB{d.lm_head, nullptr}, nullptr, logits, B, d.vocab, kHidden, kEpiNone));
+    HIP_TRY(launch_pool_select(st, logits, d.vocab, kDecEosToken, s));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_poll(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t* host_block, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    PoolPlan p;
+    DEC_TRY(pool_check(e, "loco_decoder_pool_poll", slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (!host_block) return fail(LOCO_E_INVALID, "loco_decoder_pool_poll: null host block");
+    HIP_TRY(hipMemcpyAsync(host_block, static_cast<const char*>(workspace) + p.off_poll, (size_t)(4 + 2 * slots) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_read(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t slot, int32_t* tokens, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    PoolPlan p;
+    DEC_TRY(pool_check(e, "loco_decoder_pool_read", slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (slot < 0 || slot >= slots) return fail(LOCO_E_INVALID, "loco_decoder_pool_read: slot %d of a pool of %d slots", slot, slots);
+    if (!tokens) return fail(LOCO_E_INVALID, "loco_decoder_pool_read: null token buffer");
+    HIP_TRY(hipMemcpyAsync(tokens, static_cast<const char*>(workspace) + p.off_tokens + (size_t)slot * S_max * sizeof(int32_t),
+                           (size_t)S_max * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
 int loco_op_skinny_gemm(const float* A, int64_t lda, const float* Wt, int64_t ldw, const float* bias, const float* R, int64_t ldr, float* C,
                         int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* stream) {
     if (!A || !Wt || !C) return fail(LOCO_E_INVALID, "loco_op_skinny_gemm: null argument");

@@ -331,6 +331,35 @@ hipError_t launch_dec_select(const float* logits, int vocab, int B, int32_t* tok
                              int32_t* state, int eos, int pad, hipStream_t s);
 hipError_t launch_dec_begin(int32_t* tokens, int B, int S_max, int start, int pad, int32_t* lengths, int32_t* state, hipStream_t s);
 
+// ---- decoder slot pool (decoder.hip: the row-scatter GEMM and the fixed-boundary attention; decoder_pool.hip: the slot state) ----
+constexpr int kDecPoolSplitKeys = 256;  // split s of a pool attention covers keys [256 s, 256 s + 256)
+constexpr int kPoolFree = 0, kPoolOpen = 1, kPoolFinished = 2;
+// launch_skinny_gemm's kEpiNone form for M <= 64 rows whose C2 part of row m goes to C2[m ldc2 + c2_rows[m] c2_row_stride + ...]
+// (c2_rows on the device; a negative entry drops the row's C2 part)
+hipError_t launch_skinny_gemm_rows(const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc, float* C2,
+                                   long ldc2, const int32_t* c2_rows, long c2_row_stride, int nsplit, int M, int N, int K, hipStream_t s);
+int dec_pool_attention_splits(int Tk_bound);
+size_t dec_pool_attention_scratch_bytes(int slots, int Tk_bound);
+hipError_t launch_dec_pool_attention(const float* q, const float* k, long ldk, long sk, const float* v, const int32_t* kcount, float* out,
+                                     int slots, int Tk_bound, float* scratch, hipStream_t s);
+// Per-slot state, all i32 [slots] on the device: status (kPool*), pos (token the slot consumes next), cap, frames, lengths; poll[0] =
+// slots open.  tokens is [slots, S_max].
+struct PoolState {
+    int32_t *poll, *status, *pos, *cap, *frames, *lengths, *tokens;
+    int32_t *cur, *cnt;  // the token a slot consumes next and the non-pad tokens of its utterance up to and including it
+    int32_t *self_count, *cross_count, *kv_row;  // what a step's embed kernel derives for the step's GEMM and attention launches
+    int slots, S_max, T_cap;
+};
+struct PoolAdmit {  // by value: at most 64 clips
+    int n;
+    int32_t slot[kSkinnyMaxM], cap[kSkinnyMaxM], rows[kSkinnyMaxM];
+};
+hipError_t launch_pool_init(const PoolState& p, hipStream_t s);
+hipError_t launch_pool_admit(const PoolState& p, const PoolAdmit& a, const int32_t* frames, int start, hipStream_t s);
+hipError_t launch_pool_embed(const PoolState& p, const float* embed, int vocab, const float* table, int table_rows, float* x, int max_pos,
+                             int max_frames, hipStream_t s);
+hipError_t launch_pool_select(const PoolState& p, const float* logits, int vocab, int eos, hipStream_t s);
+
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
 }  // namespace loco

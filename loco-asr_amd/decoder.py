@@ -12,6 +12,7 @@ decoder attention mask raise by name.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -198,3 +199,162 @@ class DecoderRuntime:
         ids = tokens[:, :S].to(torch.long).to(device)
         self.last_lengths = lengths
         return (ids, steps[:S - 1]) if return_logits else ids
+
+
+def resolve_caps(n: int, max_length=None, max_new_tokens=None):
+    """One total length per utterance: ``max_length`` an int (or None) for all, or one int per utterance."""
+    per_utterance = False
+    if max_length is not None and max_new_tokens is None:
+        try:
+            max_length = operator.index(max_length)  # int, numpy integer, 0-d tensor
+        except TypeError:
+            per_utterance = True
+    if per_utterance:
+        caps = [resolve_max_length(int(v)) for v in max_length]
+        if len(caps) != n:
+            raise ValueError(f"max_length names {len(caps)} utterances, the batches hold {n}")
+        return caps
+    return [resolve_max_length(max_length, max_new_tokens)] * n
+
+
+@dataclass
+class PoolItem:
+    """One utterance waiting for a slot: clip ``clip`` of ``enc_out`` [B, T, 768] (a packed forward's output), of which ``rows`` rows
+    belong to its own reference batch; ``frames`` i32 [B] on the device."""
+    key: int
+    enc_out: torch.Tensor
+    frames: torch.Tensor
+    clip: int
+    rows: int
+    cap: int
+
+
+class DecoderPool:
+    """Host side of loco_decoder_pool_*: ``slots`` decoder rows, each at its own position; a row that ends hands its slot to the next
+    utterance.  Owns the workspace and the pinned poll block.  The host keeps an exact bound on every slot's position (the steps
+    enqueued since its admission, at most cap - 2), so a step's launches are sized without reading the device; the device is looked at
+    every ``poll_steps`` steps (8, as loco_decoder_generate does), when finished rows are collected and waiting ones admitted.
+    Single caller, one stream, as DecoderRuntime."""
+
+    def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False):
+        self.enc, self.lib = encoder, encoder._lib
+        self.slots, self.T_cap, self.S_max = int(slots), int(T_cap), int(S_max)
+        self.device = device
+        self.poll_steps = int(poll_steps)
+        self.return_logits = return_logits
+        self.vocab = encoder._decoder_vocab
+        need = int(self.lib.loco_decoder_pool_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max))
+        self.workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        self._shape = (self.slots, self.T_cap, self.S_max)
+        # the limits are the library's: with need == 0 the call below names the one that was crossed
+        _lib.check(self.lib.loco_decoder_pool_init(encoder._handle, *self._shape, self._ws(), need, self._stream()), "loco_decoder_pool_init")
+        self.block = torch.zeros(4 + 2 * self.slots, dtype=torch.int32).pin_memory()
+        self.tokens = torch.zeros((self.slots, self.S_max), dtype=torch.int32).pin_memory()
+        self.entries = [None] * self.slots  # per slot: (item, step count at admission), None = free on the host's books
+        self.steps = 0                      # steps enqueued so far
+        self.waiting = []
+        self._rounds = []                   # (first step, logits [k, slots, V]) of the rounds an open utterance may still need
+
+    def _ws(self):
+        return C.c_void_p(self.workspace.data_ptr())
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def submit(self, items):
+        self.waiting.extend(items)
+
+    @property
+    def busy(self) -> bool:
+        return bool(self.waiting) or any(e is not None for e in self.entries)
+
+    def admit(self, slot_ids, items):
+        """Clips of ONE encoder output, consecutive in it, into the given free slots."""
+        n = len(items)
+        first = items[0]
+        assert all(it.enc_out is first.enc_out and it.clip == first.clip + i for i, it in enumerate(items))
+        ids = (C.c_int32 * n)(*slot_ids)
+        rows = (C.c_int32 * n)(*[it.rows for it in items])
+        caps = (C.c_int32 * n)(*[it.cap for it in items])
+        out = first.enc_out
+        frames = first.frames[first.clip:] if first.frames is not None else None
+        _lib.check(self.lib.loco_decoder_pool_admit(
+            self.enc._handle, *self._shape, n, ids, C.c_void_p(out[first.clip].data_ptr()), out.stride(0),
+            rows, C.c_void_p(frames.data_ptr()) if frames is not None else None, caps, self._ws(), self.workspace.numel(), self._stream()),
+            "loco_decoder_pool_admit")
+        for r, it in zip(slot_ids, items):
+            self.entries[r] = (it, self.steps)
+
+    def _fill(self):
+        free = [r for r in range(self.slots) if self.entries[r] is None]
+        while free and self.waiting:
+            run = [self.waiting[0]]
+            while len(run) < len(free) and len(run) < len(self.waiting) and self.waiting[len(run)].enc_out is run[0].enc_out \
+                    and self.waiting[len(run)].clip == run[0].clip + len(run):
+                run.append(self.waiting[len(run)])
+            self.admit(free[:len(run)], run)
+            del self.waiting[:len(run)], free[:len(run)]
+
+    def bounds(self):
+        """(max_pos, max_frames, steps until every slot on the books has reached its cap)."""
+        live = [(it, self.steps - s0) for e in self.entries if e is not None for it, s0 in [e]]
+        max_pos = max(min(done, it.cap - 2) for it, done in live)
+        return max_pos, max(it.rows for it, _ in live), max(it.cap - 1 - done for it, done in live)
+
+    def step(self, logits=None):
+        max_pos, max_frames, _ = self.bounds()
+        _lib.check(self.lib.loco_decoder_pool_step(self.enc._handle, *self._shape, max_pos, max_frames,
+                                                   C.c_void_p(logits.data_ptr()) if logits is not None else None, self._ws(), self.workspace.numel(),
+                                                   self._stream()), "loco_decoder_pool_step")
+        self.steps += 1
+
+    def poll(self):
+        """(status, lengths) of every slot after the work enqueued so far (waits for the stream)."""
+        _lib.check(self.lib.loco_decoder_pool_poll(self.enc._handle, *self._shape, C.c_void_p(self.block.data_ptr()), self._ws(), self.workspace.numel(),
+                                                   self._stream()), "loco_decoder_pool_poll")
+        torch.cuda.current_stream(self.device).synchronize()
+        b = self.block.tolist()
+        return b[4:4 + self.slots], b[4 + self.slots:]
+
+    def collect(self):
+        """Finished utterances since the last call: [(key, ids LongTensor, step logits [len - 1, V] or None)]; their slots are free."""
+        status, lengths = self.poll()
+        done = [r for r in range(self.slots) if self.entries[r] is not None and status[r] == 2]
+        for r in done:
+            _lib.check(self.lib.loco_decoder_pool_read(self.enc._handle, *self._shape, r, C.c_void_p(self.tokens[r].data_ptr()), self._ws(),
+                                                       self.workspace.numel(), self._stream()), "loco_decoder_pool_read")
+        if done:
+            torch.cuda.current_stream(self.device).synchronize()
+        out = []
+        for r in done:
+            it, s0 = self.entries[r]
+            n = lengths[r]
+            lg = None
+            if self.return_logits:
+                parts = [t[max(s0 - g, 0):s0 + n - 1 - g, r] for g, t in self._rounds if g < s0 + n - 1 and g + t.shape[0] > s0]
+                lg = torch.cat(parts) if parts else torch.empty((0, self.vocab), dtype=torch.float32, device=self.device)
+            out.append((it.key, self.tokens[r, :n].to(torch.long), lg))
+            self.entries[r] = None
+        if self.return_logits:
+            oldest = min([s0 for e in self.entries if e is not None for _, s0 in [e]], default=self.steps)
+            self._rounds = [(g, t) for g, t in self._rounds if g + t.shape[0] > oldest]
+        return out
+
+    def round(self):
+        """Admit what waits into the free slots, run up to ``poll_steps`` steps, collect."""
+        self._fill()
+        if not any(e is not None for e in self.entries):
+            return []
+        k = max(1, min(self.poll_steps, self.bounds()[2]))
+        lg = torch.empty((k, self.slots, self.vocab), dtype=torch.float32, device=self.device) if self.return_logits else None
+        if lg is not None:
+            self._rounds.append((self.steps, lg))
+        for j in range(k):
+            self.step(lg[j] if lg is not None else None)
+        return self.collect()
+
+    def drain(self):
+        out = []
+        while self.busy:
+            out += self.round()
+        return out

@@ -802,6 +802,64 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         with torch.cuda.device(enc_out.device):
             return self._decoder_runtime.generate(enc_out, frames, n, return_logits)
 
+    @torch.no_grad()
+    def generate_many(self, batches, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, return_logits: bool = False,
+                      pack: int = 8, **kwargs):
+        """Greedy transcripts of a corpus: ``batches`` is what ``pack_batches`` takes (reference batches of ``input_values`` /
+        ``attention_mask``), ``max_length`` an int or one int per utterance (total length, start token included).  The batches are
+        encoded ``pack`` at a time through ``forward_packed`` -- every clip keeps its own batch's padded length -- and decoded in a
+        pool of ``slots`` decoder rows in which a row that ends hands its slot to the next utterance (decoder.DecoderPool).
+
+        Returns a list, in input order, of 1-D LongTensors (host): <s> ... up to and including </s>, or the utterance's cap of tokens
+        for a row that never ended -- row u of ``generate(**batch_k, max_length=cap_u)`` without its trailing <pad>, up to the fp32
+        summation order of the packed encoder and of the attention's key splits.  An utterance's result does not depend on the
+        utterances decoded beside it.  ``return_logits=True``: (ids, logits) with one [len - 1, vocab] device tensor per utterance."""
+        from . import decoder as dec
+        dec.check_generate_kwargs(kwargs)
+        self._require_decoder("generate_many()")
+        batches = list(batches)
+        sizes = [int(b["input_values"].shape[0]) for b in batches]
+        total = sum(sizes)
+        caps = dec.resolve_caps(total, max_length, max_new_tokens)
+        if int(pack) < 1:
+            raise ValueError("pack must be >= 1")
+        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
+        if not 1 <= int(slots) <= most:
+            raise ValueError(f"generate_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        if total == 0:
+            return ([], []) if return_logits else []
+        enc = self.speecht5.encoder
+        lib = enc._lib
+        device = enc._device()
+        T_cap = max(int(lib.loco_output_frames(int(b["input_values"].shape[1]))) for b in batches if b["input_values"].shape[0])
+        if T_cap < 1:
+            raise ValueError("input shorter than one encoder frame (400 samples)")
+        pool = None
+        results, key, nxt = {}, 0, 0
+        batches = [b for b in batches if b["input_values"].shape[0]]
+        with torch.cuda.device(device):
+            while nxt < len(batches) or (pool is not None and pool.busy):
+                if nxt < len(batches) and (pool is None or len(pool.waiting) < int(slots)):
+                    ticket = enc.forward_packed_async(batches[nxt:nxt + int(pack)])
+                    nxt += int(pack)
+                    ticket.result()
+                    out, spans = ticket.packed_output()
+                    frames = enc.last_frames
+                    if pool is None:  # after the first forward: the handle exists and carries the decoder's weights
+                        pool = dec.DecoderPool(enc, min(int(slots), total), T_cap, max(caps), device,
+                                               return_logits=return_logits)
+                    items = []
+                    for b0, nb, t in spans:
+                        for c in range(b0, b0 + nb):
+                            items.append(dec.PoolItem(key=key, enc_out=out, frames=frames, clip=c, rows=t, cap=caps[key]))
+                            key += 1
+                    pool.submit(items)
+                    continue
+                for k, ids, lg in pool.round():
+                    results[k] = (ids, lg)
+        ids = [results[k][0] for k in range(total)]
+        return (ids, [results[k][1] for k in range(total)]) if return_logits else ids
+
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):
         """``SpeechT5ForSpeechToText.from_pretrained(...)`` of the fine-tuned script (…finetuned…py:95) for a checkpoint ON

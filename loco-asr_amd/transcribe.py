@@ -1,8 +1,9 @@
 """Greedy transcription CLI: ``python -m loco-asr_amd.transcribe`` writes one JSON line per utterance, {"id", "token_ids"} (and
 "text" when a SentencePiece model for ``--tokenizer`` is found ON DISK; nothing is ever fetched).
 
-Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  Small on
-purpose: no data parallelism, no packing.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
+Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  With
+``--slots N`` the pairs are encoded ``--pack G`` at a time and decoded in a pool of N decoder rows in which a finished row hands its
+slot to the next utterance (``generate_many``); the lines written are the same.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
 ``--synthetic N`` seeded clips; weights: ``--pretrained DIR`` (a HuggingFace speech-to-text checkpoint directory with the decoder)
 or ``--random-init`` (the deterministic synthetic weights).
@@ -98,12 +99,16 @@ def main(argv=None):
     ap.add_argument("--synthetic-seconds", type=float, default=5.0)
     ap.add_argument("--batch-size", type=int, default=2, help="utterances per generate call (the reference's loop: 2)")
     ap.add_argument("--max-length", type=int, default=100, help="total tokens per utterance, start token included (the reference's notebooks: 100)")
+    ap.add_argument("--slots", type=int, default=0, help="decode in a pool of N rows with finished rows refilled (1 .. 64); 0 = one generate call per batch")
+    ap.add_argument("--pack", type=int, default=8, metavar="G", help="with --slots: batches per packed encoder forward")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
     ap.add_argument("--precision", choices=["f16x3", "f32", "f16x2"], default="f16x3", help="arithmetic of the ENCODER (the decoder is fp32)")
     ap.add_argument("--out", default="-", help="JSON-lines file, - = stdout")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch-size must be >= 1")
+    if args.slots < 0 or args.pack < 1:
+        raise SystemExit("--slots must be >= 0 and --pack >= 1")
     items = gather_items(args)
     from .feature_extractor import SpeechT5FeatureExtractorMI355X
     processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
@@ -111,16 +116,31 @@ def main(argv=None):
     tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
+    def write(chunk, ids):
+        for (uid, _, _), row in zip(chunk, ids):
+            rec = {"id": uid, "token_ids": row}
+            if tok is not None:
+                rec["text"] = tok.decode(strip_special(row))
+            fh.write(json.dumps(rec) + "\n")
+
     try:
-        for b0 in range(0, len(items), args.batch_size):
-            chunk = items[b0:b0 + args.batch_size]
-            f = load_batch(chunk, b0, processor, device)
-            ids = model.generate(f["input_values"].to(device), f["attention_mask"].to(device), max_length=args.max_length).cpu().tolist()
-            for (uid, _, _), row in zip(chunk, ids):
-                rec = {"id": uid, "token_ids": row}
-                if tok is not None:
-                    rec["text"] = tok.decode(strip_special(row))
-                fh.write(json.dumps(rec) + "\n")
+        starts = list(range(0, len(items), args.batch_size))
+        if args.slots:
+            window = max(args.pack, 4 * args.slots)  # batches loaded, encoded and decoded per generate_many call
+            for w0 in range(0, len(starts), window):
+                chunks = [items[b0:b0 + args.batch_size] for b0 in starts[w0:w0 + window]]
+                feats = [load_batch(chunk, b0, processor, device) for chunk, b0 in zip(chunks, starts[w0:w0 + window])]
+                rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack)
+                for chunk in chunks:
+                    ids, rows = [r.tolist() for r in rows[:len(chunk)]], rows[len(chunk):]
+                    width = max(len(r) for r in ids)  # generate's rows: <pad> up to the longest row of the batch
+                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids])
+        else:
+            for b0 in starts:
+                chunk = items[b0:b0 + args.batch_size]
+                f = load_batch(chunk, b0, processor, device)
+                ids = model.generate(f["input_values"].to(device), f["attention_mask"].to(device), max_length=args.max_length).cpu().tolist()
+                write(chunk, ids)
     finally:
         if fh is not sys.stdout:
             fh.close()

@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Bit-for-bit comparison of the existing decoder entry points between two builds of this repository (a parent checkout and this
+tree, each with its own libloco_asr.so): loco_decoder_generate (ids and step logits) and loco_decoder_begin + loco_decoder_step on
+GENERATE["b7_len40_30s"], and loco_decoder_forward (logits and the 7 hidden states) on TEACHER_FORCED[3] of
+tests/decoder_sweep_cases.py, 12 + 6 layers.  One process per tree, since a process loads one library:
+
+    python tools/decoder_parent_compare.py dump PARENT_TREE out/parent
+    python tools/decoder_parent_compare.py dump . out/new
+    python tools/decoder_parent_compare.py compare out/parent out/new     # exits non-zero on any differing byte
+"""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+
+
+def dump(root, outdir):
+    import torch
+    root = os.path.abspath(root)
+    os.makedirs(outdir, exist_ok=True)
+    for p in (root, os.path.join(root, "tests")):
+        sys.path.insert(0, p)
+    la = importlib.import_module("loco-asr_amd")
+    assert os.path.dirname(os.path.dirname(os.path.abspath(la.__file__))) == root, la.__file__
+    import decoder_sweep_cases as cases
+    synth = la.synth
+    t = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
+    pre, enc = synth.split_state_dict(synth.encoder_state_dict(0))
+    dec, post = synth.split_decoder_state_dict(synth.decoder_state_dict(13))
+    model = la.SpeechT5ForSpeechToTextMI355X.from_state_dicts(t(pre), t(enc), decoder_state_dict=t(dec), postnet_state_dict=t(post)).to("cuda")
+    save = lambda name, x: np.save(os.path.join(outdir, name + ".npy"), x.cpu().numpy())  # noqa: E731
+    _, lengths_of, first_index, max_length = cases.GENERATE["b7_len40_30s"]
+    x, m = synth.batch(lengths_of(synth), first_index=first_index)
+    enc_out, frames = model._encode(torch.from_numpy(x).cuda(), torch.from_numpy(m).cuda())
+    ids, steps = model._decoder_runtime.generate(enc_out, frames, max_length, True)
+    torch.cuda.synchronize()
+    save("generate_ids", ids), save("generate_step_logits", steps), save("encoder_out", enc_out)
+    lib, h = model.speecht5.encoder._lib, model.speecht5.encoder._handle
+    B, T, S = enc_out.shape[0], enc_out.shape[1], 12
+    need = lib.loco_decoder_workspace_bytes(h, B, T, S)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    p = lambda tn: C.c_void_p(tn.data_ptr())  # noqa: E731
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.loco_decoder_begin(h, p(enc_out), p(frames), B, T, S, p(ws), need, st) == 0
+    lg = torch.empty((S - 1, B, 81), device="cuda")
+    for step in range(S - 1):
+        assert lib.loco_decoder_step(h, B, T, S, step, p(lg[step]), p(ws), need, st) == 0
+    torch.cuda.synchronize()
+    save("step_logits", lg)
+    Bt, St, Tt, fr = cases.TEACHER_FORCED[3]
+    e = (synth.hashed_uniform(f"dec_oracle/enc/{Bt}/{St}/{Tt}", (Bt, Tt, 768), 2) * np.float32(1.5)).astype(np.float32)
+    tids = cases.teacher_forced_ids(synth, Bt, St)
+    logits, hs = model._decoder_runtime.forward(torch.from_numpy(e).cuda(), torch.tensor(fr, dtype=torch.int32).cuda(),
+                                                torch.from_numpy(tids).to(torch.int32).cuda(), True)
+    torch.cuda.synchronize()
+    save("forward_logits", logits), save("forward_hidden", torch.stack(hs))
+    print("dumped", sorted(os.listdir(outdir)), "from", root)
+
+
+def compare(a, b):
+    ok = True
+    for f in sorted(os.listdir(a)):
+        x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
+        same = x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
+        print(f, x.shape, "bit-identical" if same else "DIFFERENT")
+        ok = ok and same
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "dump":
+        dump(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
