@@ -588,6 +588,24 @@ int loco_decoder_pool_poll(loco_encoder* enc, int32_t slots, int32_t T_cap, int3
 int loco_decoder_pool_read(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t slot, int32_t* tokens, const void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- decoder scores: log-probabilities of a transcript's tokens, per-sequence sums, the labels= loss --------------------------------
+ * loco_decoder_score turns logits (loco_decoder_forward's [B, S, V], or a block of step logits) into what a transcript is judged by.
+ * Stateless: no handle, no workspace.  Asynchronous, reads no host memory, two launches on `stream`; it can be captured like a step.
+ *   logits         f32 (device), row m = b * S + t at logits + m * ld, ld >= V floats; columns >= V of a row are never read
+ *   targets        i32 [B * S] (device) or NULL.  NULL: the target of a row is its argmax (the lowest index wins ties, the first NaN
+ *                  wins: the decode step's rule).  targets[m] == ignore_index: the position does not count and its log-probability
+ *                  is 0.  Another value outside [0, V) is never used as an index: the row's log-probability is NaN and it counts.
+ *   token_logprobs f32 [B * S]: log_softmax(row)[target] = x[target] - max - log(sum exp(x - max)) in fp32 -- bit for bit a function
+ *                  of the row's own V numbers, wherever the row sits and whatever the other rows hold.  Non-finite logits as
+ *                  torch.log_softmax: -inf entries add nothing; a row that is all -inf, or holds +inf or NaN, gives NaN.
+ *   chosen         NULL or i32 [B * S]: the target each row used (the argmax when targets is NULL)
+ *   seq_logprob    NULL or f32 [B]: sum of sequence b's counted log-probabilities;  seq_count  NULL or i32 [B]: how many counted
+ *   loss           NULL or f32 [1]: -(sum over b of the sums) / (sum over b of the counts), HF's CrossEntropyLoss() mean over the
+ *                  tokens that are not ignored; NaN when none counts.  Sums are accumulated in double in an order fixed by (B, S).
+ * Errors: a null logits or token_logprobs, B, S or V below 1, ld < V, B * S above 2^31 - 1: LOCO_E_INVALID. */
+int loco_decoder_score(const float* logits, int64_t ld, const int32_t* targets, int32_t B, int32_t S, int32_t V, int32_t ignore_index,
+                       float* token_logprobs, int32_t* chosen, float* seq_logprob, int32_t* seq_count, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,7 @@ SIGNATURES = {
     "loco_decoder_pool_step": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_decoder_pool_poll": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_decoder_pool_read": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "loco_decoder_score": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "loco_op_decoder_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _sz, _vp]),

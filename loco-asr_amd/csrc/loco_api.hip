@@ -2437,3 +2437,16 @@ int loco_op_decoder_attention(const float* q, const float* k, const float* v, co
                                  (long)Sq * kHidden, B, Sq, Tk, causal, causal_offset, scale, static_cast<float*>(scratch), (hipStream_t)stream));
     return LOCO_OK;
 }
+
+// ---- decoder scores (decoder_score.hip) ----
+int loco_decoder_score(const float* logits, int64_t ld, const int32_t* targets, int32_t B, int32_t S, int32_t V, int32_t ignore_index,
+                       float* token_logprobs, int32_t* chosen, float* seq_logprob, int32_t* seq_count, float* loss, void* stream) {
+    if (!logits || !token_logprobs) return fail(LOCO_E_INVALID, "loco_decoder_score: null logits or token_logprobs");
+    if (B < 1 || S < 1 || V < 1) return fail(LOCO_E_INVALID, "loco_decoder_score: B = %d, S = %d, V = %d must all be >= 1", B, S, V);
+    if (ld < V) return fail(LOCO_E_INVALID, "loco_decoder_score: row stride ld = %lld < V = %d", (long long)ld, V);
+    if ((long)B * S > 0x7fffffffL) return fail(LOCO_E_INVALID, "loco_decoder_score: B * S = %ld rows exceed 2^31 - 1", (long)B * S);
+    HIP_TRY(launch_token_logprob(logits, (long)ld, targets, (long)B * S, V, ignore_index, token_logprobs, chosen, (hipStream_t)stream));
+    if (seq_logprob || seq_count || loss)
+        HIP_TRY(launch_score_reduce(token_logprobs, targets, B, S, ignore_index, seq_logprob, seq_count, loss, (hipStream_t)stream));
+    return LOCO_OK;
+}

@@ -360,6 +360,16 @@ hipError_t launch_pool_embed(const PoolState& p, const float* embed, int vocab, 
                              int max_frames, hipStream_t s);
 hipError_t launch_pool_select(const PoolState& p, const float* logits, int vocab, int eos, hipStream_t s);
 
+// ---- decoder scores (decoder_score.hip) ----
+// logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (dec_select_kernel's rule) when targets is
+// null; 0 where targets[m] == ignore_index, NaN for another target outside [0, V); chosen (optional) [M] = the target used
+hipError_t launch_token_logprob(const float* logits, long ld, const int32_t* targets, long M, int V, int ignore_index, float* logprob,
+                                int32_t* chosen, hipStream_t s);
+// seq_logprob[b] / seq_count[b] (optional) = sum / number of the positions of sequence b whose target is not ignore_index (null targets:
+// all); loss[0] (optional) = -(sum over b) / (count over b), accumulated in double in an order that depends on (B, S) only
+hipError_t launch_score_reduce(const float* logprob, const int32_t* targets, int B, int S, int ignore_index, float* seq_logprob,
+                               int32_t* seq_count, float* loss, hipStream_t s);
+
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
 }  // namespace loco

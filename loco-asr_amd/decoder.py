@@ -7,7 +7,8 @@ the C ABI's ``loco_decoder_*`` entry points (include/loco_asr.h).
 ``SpeechT5DecoderWithTextPrenetMI355X`` (``.prenet``, ``.wrapped_decoder``) and ``SpeechT5TextDecoderPostnetMI355X`` only own
 parameters, so that ``load_state_dict`` of HF's dicts works; every FLOP runs in the HIP kernels of csrc/decoder.hip (the decode step)
 and the library's exact-fp32 GEMM / LayerNorm (the teacher-forced pass).  Greedy search only: beam search, sampling, prefixes and a
-decoder attention mask raise by name.
+decoder attention mask raise by name.  Scores -- the ``labels=`` loss, per-token and per-transcript log-probabilities -- come from
+``loco_decoder_score`` (csrc/decoder_score.hip) on the logits of either path.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ from .synth import DECODER_LAYERS, FFN, HIDDEN, MAX_TEXT_POSITIONS, TEXT_VOCAB
 DECODER_START_TOKEN_ID = 2
 EOS_TOKEN_ID = 2
 PAD_TOKEN_ID = 1
+IGNORE_INDEX = -100  # labels with this value do not count (torch's CrossEntropyLoss default, what HF pads labels with)
 DEFAULT_MAX_LENGTH = 21  # what HF 5.x generate resolves for a default SpeechT5Config: max_new_tokens = 20 after the start token (pinned by g13 a_default_ids)
 
 _UNSUPPORTED_GENERATE = ("num_beams", "do_sample", "decoder_input_ids", "decoder_attention_mask", "temperature", "top_k", "top_p",
@@ -39,6 +41,29 @@ class Seq2SeqLMOutput:
     logits: torch.Tensor = None
     encoder_last_hidden_state: torch.Tensor = None
     decoder_hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
+    loss: Optional[torch.Tensor] = None            # labels=: 0-d, the mean cross-entropy over the labels that are not -100
+    token_logprobs: Optional[torch.Tensor] = None  # labels=: [B, S] log P(labels[b, t]), 0 where the label is -100
+
+
+@dataclass
+class TranscriptScores:
+    """What ``score`` returns: ``token_logprobs`` [B, S] (0 at ignored labels), ``sequence_logprob`` [B] their sum per row, ``tokens``
+    i32 [B] the labels that counted, ``loss`` 0-d = -sum / count over the batch."""
+    token_logprobs: torch.Tensor = None
+    sequence_logprob: torch.Tensor = None
+    tokens: torch.Tensor = None
+    loss: torch.Tensor = None
+
+
+@dataclass
+class GreedySearchOutput:
+    """``generate(return_dict_in_generate=True)``: ``sequences`` is what ``generate`` returns otherwise.  With ``output_scores=True``
+    also ``scores`` (S - 1 tensors [B, vocab]: the raw logits each step chose from), ``token_logprobs`` [B, S - 1] (entry t =
+    log P(sequences[:, t + 1]); 0 at the <pad> columns of a row that had ended) and ``sequence_logprobs`` [B]."""
+    sequences: torch.Tensor = None
+    scores: Optional[Tuple[torch.Tensor, ...]] = None
+    token_logprobs: Optional[torch.Tensor] = None
+    sequence_logprobs: Optional[torch.Tensor] = None
 
 
 def _holder_base():
@@ -103,6 +128,59 @@ def position_ids(input_ids: torch.Tensor, past_key_values_length: int = 0) -> to
     implements: a token's position is the count of non-pad tokens up to and including it, plus 1; <pad> maps to row 1 (zeros)."""
     mask = input_ids.ne(PAD_TOKEN_ID).int()
     return ((torch.cumsum(mask, dim=1).type_as(mask) + past_key_values_length) * mask).long() + PAD_TOKEN_ID
+
+
+def shift_tokens_right(labels: torch.Tensor, pad_token_id: int = PAD_TOKEN_ID, decoder_start_token_id: int = DECODER_START_TOKEN_ID) -> torch.Tensor:
+    """HF's shift_tokens_right (modeling_speecht5.py): the decoder's input for ``labels`` -- the start token in column 0, the labels
+    one column to the right, -100 replaced by <pad>."""
+    shifted = labels.new_zeros(labels.shape)
+    shifted[:, 1:] = labels[:, :-1]
+    shifted[:, 0] = decoder_start_token_id
+    return shifted.masked_fill(shifted == IGNORE_INDEX, pad_token_id)
+
+
+def check_labels(labels, batch: int, vocab: int, ids_shape=None) -> torch.Tensor:
+    """``labels`` as a host LongTensor [batch, S] with every value in [0, vocab) or -100; ValueError naming the offender otherwise."""
+    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[0] != batch or labels.shape[1] < 1:
+        got = tuple(labels.shape) if torch.is_tensor(labels) else type(labels).__name__
+        raise ValueError(f"labels must be a [batch, tokens] tensor with batch {batch}, got {got}")
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f"labels must hold integer token ids, got dtype {labels.dtype}")
+    if ids_shape is not None and tuple(labels.shape) != tuple(ids_shape):
+        raise ValueError(f"labels {tuple(labels.shape)} and decoder_input_ids {tuple(ids_shape)} must have the same shape")
+    if labels.shape[1] > MAX_TEXT_POSITIONS:
+        raise ValueError(f"labels of {labels.shape[1]} tokens exceed max_text_positions = {MAX_TEXT_POSITIONS}")
+    host = labels.detach().to(device="cpu", dtype=torch.long)
+    bad = ((host < 0) | (host >= vocab)) & (host != IGNORE_INDEX)
+    if bool(bad.any()):
+        b, t = (int(v) for v in bad.nonzero()[0])
+        raise ValueError(f"labels[{b}, {t}] = {int(host[b, t])} is neither a token id in [0, {vocab}) nor {IGNORE_INDEX}")
+    return host
+
+
+def score_logits(lib, logits: torch.Tensor, targets: Optional[torch.Tensor], B: int, S: int, reduce: bool = True, chosen: bool = False):
+    """loco_decoder_score on ``logits`` (f32, device, B * S rows of one row stride, the last dimension the vocabulary) against
+    ``targets`` i32 [B, S] on the device (None: each row's argmax).  Returns (token_logprobs [B, S], sequence sums [B], counts i32 [B],
+    loss 0-d, chosen i32 [B, S]); what was not asked for is None.  Enqueued on the current stream; nothing is read back."""
+    if logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError("score_logits: logits must be an fp32 device tensor (there is no CPU path)")
+    V = int(logits.shape[-1])
+    rows = logits.reshape(-1, V) if logits.is_contiguous() else logits
+    if rows.dim() != 2 or rows.shape[0] != B * S or rows.stride(1) != 1:
+        raise ValueError(f"score_logits: logits {tuple(logits.shape)} are not {B * S} rows of one stride")
+    if targets is not None and (targets.dtype != torch.int32 or targets.device != logits.device or targets.numel() != B * S or not targets.is_contiguous()):
+        raise ValueError("score_logits: targets must be a contiguous i32 device tensor with one entry per row")
+    device = logits.device
+    lp = torch.empty((B, S), dtype=torch.float32, device=device)
+    seq = torch.empty((B,), dtype=torch.float32, device=device) if reduce else None
+    cnt = torch.empty((B,), dtype=torch.int32, device=device) if reduce else None
+    loss = torch.empty((1,), dtype=torch.float32, device=device) if reduce else None
+    ch = torch.empty((B, S), dtype=torch.int32, device=device) if chosen else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(device):
+        _lib.check(lib.loco_decoder_score(p(rows), rows.stride(0) if rows.shape[0] > 1 else V, p(targets), B, S, V, IGNORE_INDEX, p(lp), p(ch), p(seq),
+                                          p(cnt), p(loss), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "loco_decoder_score")
+    return lp, seq, cnt, (loss.reshape(()) if loss is not None else None), ch
 
 
 def resolve_max_length(max_length=None, max_new_tokens=None) -> int:
@@ -236,12 +314,14 @@ class DecoderPool:
     every ``poll_steps`` steps (8, as loco_decoder_generate does), when finished rows are collected and waiting ones admitted.
     Single caller, one stream, as DecoderRuntime."""
 
-    def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False):
+    def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False,
+                 return_scores: bool = False):
         self.enc, self.lib = encoder, encoder._lib
         self.slots, self.T_cap, self.S_max = int(slots), int(T_cap), int(S_max)
         self.device = device
         self.poll_steps = int(poll_steps)
         self.return_logits = return_logits
+        self.return_scores = return_scores  # collect() then yields 4-tuples: (..., log P of every generated token [len - 1])
         self.vocab = encoder._decoder_vocab
         need = int(self.lib.loco_decoder_pool_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max))
         self.workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
@@ -254,6 +334,7 @@ class DecoderPool:
         self.steps = 0                      # steps enqueued so far
         self.waiting = []
         self._rounds = []                   # (first step, logits [k, slots, V]) of the rounds an open utterance may still need
+        self._score_rounds = []             # (first step, log-probabilities [k, slots]) likewise
 
     def _ws(self):
         return C.c_void_p(self.workspace.data_ptr())
@@ -317,7 +398,8 @@ class DecoderPool:
         return b[4:4 + self.slots], b[4 + self.slots:]
 
     def collect(self):
-        """Finished utterances since the last call: [(key, ids LongTensor, step logits [len - 1, V] or None)]; their slots are free."""
+        """Finished utterances since the last call: [(key, ids LongTensor, step logits [len - 1, V] or None)], with ``return_scores``
+        [(key, ids, logits or None, log-probabilities [len - 1])]; their slots are free."""
         status, lengths = self.poll()
         done = [r for r in range(self.slots) if self.entries[r] is not None and status[r] == 2]
         for r in done:
@@ -333,11 +415,17 @@ class DecoderPool:
             if self.return_logits:
                 parts = [t[max(s0 - g, 0):s0 + n - 1 - g, r] for g, t in self._rounds if g < s0 + n - 1 and g + t.shape[0] > s0]
                 lg = torch.cat(parts) if parts else torch.empty((0, self.vocab), dtype=torch.float32, device=self.device)
-            out.append((it.key, self.tokens[r, :n].to(torch.long), lg))
+            if self.return_scores:
+                parts = [t[max(s0 - g, 0):s0 + n - 1 - g, r] for g, t in self._score_rounds if g < s0 + n - 1 and g + t.shape[0] > s0]
+                sc = torch.cat(parts) if parts else torch.empty((0,), dtype=torch.float32, device=self.device)
+                out.append((it.key, self.tokens[r, :n].to(torch.long), lg, sc))
+            else:
+                out.append((it.key, self.tokens[r, :n].to(torch.long), lg))
             self.entries[r] = None
-        if self.return_logits:
+        if self.return_logits or self.return_scores:
             oldest = min([s0 for e in self.entries if e is not None for _, s0 in [e]], default=self.steps)
             self._rounds = [(g, t) for g, t in self._rounds if g + t.shape[0] > oldest]
+            self._score_rounds = [(g, t) for g, t in self._score_rounds if g + t.shape[0] > oldest]
         return out
 
     def round(self):
@@ -346,11 +434,15 @@ class DecoderPool:
         if not any(e is not None for e in self.entries):
             return []
         k = max(1, min(self.poll_steps, self.bounds()[2]))
-        lg = torch.empty((k, self.slots, self.vocab), dtype=torch.float32, device=self.device) if self.return_logits else None
-        if lg is not None:
+        want = self.return_logits or self.return_scores
+        lg = torch.empty((k, self.slots, self.vocab), dtype=torch.float32, device=self.device) if want else None
+        if self.return_logits:
             self._rounds.append((self.steps, lg))
+        first = self.steps
         for j in range(k):
             self.step(lg[j] if lg is not None else None)
+        if self.return_scores:  # the round's block in one launch: every row against its own argmax, the token the step appended
+            self._score_rounds.append((first, score_logits(self.lib, lg, None, k, self.slots, reduce=False)[0]))
         return self.collect()
 
     def drain(self):

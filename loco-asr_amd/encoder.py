@@ -768,43 +768,143 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
 
     @torch.no_grad()
     def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                decoder_input_ids: Optional[torch.Tensor] = None, output_hidden_states: Optional[bool] = None, **kwargs):
+                decoder_input_ids: Optional[torch.Tensor] = None, output_hidden_states: Optional[bool] = None,
+                labels: Optional[torch.Tensor] = None, **kwargs):
         """``model(**audios, decoder_input_ids=ids)``: teacher-forced logits [B, S, vocab] and ``encoder_last_hidden_state``
         (``output_hidden_states=True``: also the 7 ``decoder_hidden_states``).  Causal self-attention over the ids as given (no
-        decoder attention mask, as in the reference's calls); cross-attention over each clip's valid encoder frames."""
+        decoder attention mask, as in the reference's calls); cross-attention over each clip's valid encoder frames.
+
+        ``labels`` [B, S] (token ids, -100 = not counted): also ``loss``, HF's mean cross-entropy over the counted labels, and
+        ``token_logprobs`` [B, S].  Without ``decoder_input_ids`` the decoder reads the labels shifted right (decoder.shift_tokens_right),
+        as HF does; with both, the given ids are read and the loss is taken against ``labels``."""
         for k in kwargs:
-            if k in ("decoder_attention_mask", "labels", "past_key_values", "encoder_outputs", "use_cache", "output_attentions"):
+            if k in ("decoder_attention_mask", "past_key_values", "encoder_outputs", "use_cache", "output_attentions"):
                 raise NotImplementedError(f"forward({k}=...) is not implemented")
             raise TypeError(f"forward() got an unexpected keyword argument '{k}'")
-        self._require_decoder("forward(decoder_input_ids=...)")
-        if decoder_input_ids is None:
+        self._require_decoder("forward(labels=...)" if labels is not None and decoder_input_ids is None else "forward(decoder_input_ids=...)")
+        if decoder_input_ids is None and labels is None:
             raise ValueError("You have to specify `decoder_input_ids` (for embeddings alone call model.speecht5.encoder)")
-        from .decoder import Seq2SeqLMOutput
+        from . import decoder as dec
+        targets = None
+        if labels is not None:  # on the host, before any launch
+            host = dec.check_labels(labels, int(input_values.shape[0]), self.speecht5.encoder._decoder_vocab,
+                                    decoder_input_ids.shape if decoder_input_ids is not None else None)
+            if decoder_input_ids is None:
+                decoder_input_ids = dec.shift_tokens_right(host)
+            targets = host.to(torch.int32)
         enc_out, frames = self._encode(input_values, attention_mask)
         if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != enc_out.shape[0]:
             raise ValueError(f"decoder_input_ids must be [batch, tokens] with batch {enc_out.shape[0]}, got {tuple(decoder_input_ids.shape)}")
         ids = decoder_input_ids.to(device=enc_out.device, dtype=torch.int32).contiguous()
         with torch.cuda.device(enc_out.device):
             logits, hidden = self._decoder_runtime.forward(enc_out, frames, ids, bool(output_hidden_states))
-        return Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden)
+            loss = logprobs = None
+            if targets is not None:
+                logprobs, _, _, loss, _ = dec.score_logits(self.speecht5.encoder._lib, logits, targets.to(enc_out.device).contiguous(), *ids.shape)
+        return dec.Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden, loss=loss, token_logprobs=logprobs)
+
+    @torch.no_grad()
+    def score(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+        """How likely the model finds the transcripts ``labels`` [B, S] (-100 = not counted) for these clips: decoder.TranscriptScores
+        with ``token_logprobs`` [B, S], ``sequence_logprob`` [B], ``tokens`` [B] and ``loss`` -- ``forward(labels=...)``'s pass, without
+        handing the logits out."""
+        self._require_decoder("score()")
+        if labels is None:
+            raise ValueError("score() needs labels")
+        from . import decoder as dec
+        host = dec.check_labels(labels, int(input_values.shape[0]), self.speecht5.encoder._decoder_vocab)
+        enc_out, frames = self._encode(input_values, attention_mask)
+        return self._score_encoded(enc_out, frames, host)
+
+    def _score_encoded(self, enc_out, frames, labels_host):
+        from . import decoder as dec
+        device = enc_out.device
+        ids = dec.shift_tokens_right(labels_host).to(device=device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(device):
+            logits, _ = self._decoder_runtime.forward(enc_out, frames, ids)
+            lp, seq, cnt, loss, _ = dec.score_logits(self.speecht5.encoder._lib, logits, labels_host.to(device=device, dtype=torch.int32).contiguous(),
+                                                     *ids.shape)
+        return dec.TranscriptScores(token_logprobs=lp, sequence_logprob=seq, tokens=cnt, loss=loss)
+
+    @torch.no_grad()
+    def score_many(self, batches, labels, pack: int = 8):
+        """Scores of a corpus: ``batches`` is what ``generate_many`` takes, ``labels`` one 1-D LongTensor per utterance in input order.
+        The batches are encoded ``pack`` at a time through ``forward_packed``; each pack's clips go through ONE teacher-forced
+        decoder pass on the packed output and its frame counts, their labels padded with -100 to the pack's longest, and are scored
+        in one launch.  Returns a list, in input order, of (``token_logprobs`` 1-D of the utterance's own length, its sum 0-d), both
+        on the device.  An utterance's scores are those of ``score`` on its own batch up to the fp32 summation order of the packed
+        encoder and of the decoder's products, whatever ``pack`` is; the scoring kernel itself adds nothing to that (a row's
+        log-probability is a function of the row's logits alone)."""
+        from . import decoder as dec
+        self._require_decoder("score_many()")
+        batches = [b for b in batches if b["input_values"].shape[0]]
+        labels = list(labels)
+        total = sum(int(b["input_values"].shape[0]) for b in batches)
+        if len(labels) != total:
+            raise ValueError(f"score_many: {len(labels)} label rows for {total} utterances")
+        if int(pack) < 1:
+            raise ValueError("pack must be >= 1")
+        enc = self.speecht5.encoder
+        hosts = []
+        for u, lab in enumerate(labels):
+            if not torch.is_tensor(lab) or lab.dim() != 1:
+                raise ValueError(f"score_many: labels[{u}] must be a 1-D tensor of token ids")
+            hosts.append(dec.check_labels(lab[None], 1, enc._decoder_vocab)[0])
+        results, u0 = [], 0
+        for g0 in range(0, len(batches), int(pack)):
+            group = batches[g0:g0 + int(pack)]
+            ticket = enc.forward_packed_async(group)
+            ticket.result()
+            out, _ = ticket.packed_output()
+            n = int(out.shape[0])
+            rows = hosts[u0:u0 + n]
+            S = max(int(r.shape[0]) for r in rows)
+            lab = torch.full((n, S), dec.IGNORE_INDEX, dtype=torch.long)
+            for i, r in enumerate(rows):
+                lab[i, :r.shape[0]] = r
+            sc = self._score_encoded(out, enc.last_frames, lab)
+            for i, r in enumerate(rows):
+                results.append((sc.token_logprobs[i, :r.shape[0]], sc.sequence_logprob[i]))
+            u0 += n
+        return results
 
     @torch.no_grad()
     def generate(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
-                 max_new_tokens: Optional[int] = None, return_logits: bool = False, **kwargs):
+                 max_new_tokens: Optional[int] = None, return_logits: bool = False, return_dict_in_generate: bool = False,
+                 output_scores: bool = False, **kwargs):
         """Greedy search as HF's ``generate`` runs it for this model: LongTensor [B, S] starting with decoder_start_token_id 2, a
         row that has emitted </s> (2) is filled with <pad> (1), S = the longest row or ``max_length`` (total, start token included;
-        ``max_new_tokens`` counts the tokens after it).  ``return_logits=True``: also the logits [S - 1, B, vocab] each step chose from."""
+        ``max_new_tokens`` counts the tokens after it).  ``return_logits=True``: also the logits [S - 1, B, vocab] each step chose from.
+
+        ``return_dict_in_generate=True``: a decoder.GreedySearchOutput whose ``sequences`` are those ids; with ``output_scores=True``
+        it also carries ``scores`` (the S - 1 step logits [B, vocab]), ``token_logprobs`` [B, S - 1] and ``sequence_logprobs`` [B].
+        ``output_scores`` alone changes nothing, as in HF."""
         from . import decoder as dec
         dec.check_generate_kwargs(kwargs)
         self._require_decoder("generate()")
         n = dec.resolve_max_length(max_length, max_new_tokens)
         enc_out, frames = self._encode(input_values, attention_mask)
+        with_scores = bool(return_dict_in_generate) and bool(output_scores)
         with torch.cuda.device(enc_out.device):
-            return self._decoder_runtime.generate(enc_out, frames, n, return_logits)
+            rt = self._decoder_runtime
+            res = rt.generate(enc_out, frames, n, return_logits or with_scores)
+            if not return_dict_in_generate:
+                return res
+            ids, steps = res if (return_logits or with_scores) else (res, None)
+            out = dec.GreedySearchOutput(sequences=ids)
+            if with_scores:
+                B, S = ids.shape
+                # targets: the returned ids, -100 from each row's length on (the host holds ids' lengths already)
+                cols = torch.arange(1, S)[None, :]
+                targets = torch.where(cols < rt.last_lengths[:, None].long(), ids[:, 1:].cpu(), torch.tensor(dec.IGNORE_INDEX)).to(torch.int32)
+                by_row = steps.permute(1, 0, 2).contiguous()  # [B, S - 1, V]: a row's steps form one sequence
+                lp, seq, _, _, _ = dec.score_logits(self.speecht5.encoder._lib, by_row, targets.to(enc_out.device).contiguous(), B, S - 1)
+                out.scores, out.token_logprobs, out.sequence_logprobs = tuple(steps[t] for t in range(S - 1)), lp, seq
+            return (out, steps) if return_logits else out
 
     @torch.no_grad()
     def generate_many(self, batches, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, return_logits: bool = False,
-                      pack: int = 8, **kwargs):
+                      pack: int = 8, return_scores: bool = False, **kwargs):
         """Greedy transcripts of a corpus: ``batches`` is what ``pack_batches`` takes (reference batches of ``input_values`` /
         ``attention_mask``), ``max_length`` an int or one int per utterance (total length, start token included).  The batches are
         encoded ``pack`` at a time through ``forward_packed`` -- every clip keeps its own batch's padded length -- and decoded in a
@@ -813,7 +913,9 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         Returns a list, in input order, of 1-D LongTensors (host): <s> ... up to and including </s>, or the utterance's cap of tokens
         for a row that never ended -- row u of ``generate(**batch_k, max_length=cap_u)`` without its trailing <pad>, up to the fp32
         summation order of the packed encoder and of the attention's key splits.  An utterance's result does not depend on the
-        utterances decoded beside it.  ``return_logits=True``: (ids, logits) with one [len - 1, vocab] device tensor per utterance."""
+        utterances decoded beside it.  ``return_logits=True``: (ids, logits) with one [len - 1, vocab] device tensor per utterance.
+        ``return_scores=True``: (ids, scores) with one [len - 1] device tensor per utterance, the log-probability of every generated
+        token (both: (ids, logits, scores))."""
         from . import decoder as dec
         dec.check_generate_kwargs(kwargs)
         self._require_decoder("generate_many()")
@@ -826,8 +928,9 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
         if not 1 <= int(slots) <= most:
             raise ValueError(f"generate_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        extras = int(bool(return_logits)) + int(bool(return_scores))
         if total == 0:
-            return ([], []) if return_logits else []
+            return ([],) * (1 + extras) if extras else []
         enc = self.speecht5.encoder
         lib = enc._lib
         device = enc._device()
@@ -847,7 +950,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                     frames = enc.last_frames
                     if pool is None:  # after the first forward: the handle exists and carries the decoder's weights
                         pool = dec.DecoderPool(enc, min(int(slots), total), T_cap, max(caps), device,
-                                               return_logits=return_logits)
+                                               return_logits=return_logits, return_scores=return_scores)
                     items = []
                     for b0, nb, t in spans:
                         for c in range(b0, b0 + nb):
@@ -855,10 +958,14 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                             key += 1
                     pool.submit(items)
                     continue
-                for k, ids, lg in pool.round():
-                    results[k] = (ids, lg)
-        ids = [results[k][0] for k in range(total)]
-        return (ids, [results[k][1] for k in range(total)]) if return_logits else ids
+                for k, *rest in pool.round():
+                    results[k] = rest
+        out = [[results[k][0] for k in range(total)]]
+        if return_logits:
+            out.append([results[k][1] for k in range(total)])
+        if return_scores:
+            out.append([results[k][2] for k in range(total)])
+        return tuple(out) if extras else out[0]
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):

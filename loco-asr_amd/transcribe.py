@@ -1,5 +1,6 @@
 """Greedy transcription CLI: ``python -m loco-asr_amd.transcribe`` writes one JSON line per utterance, {"id", "token_ids"} (and
-"text" when a SentencePiece model for ``--tokenizer`` is found ON DISK; nothing is ever fetched).
+"text" when a SentencePiece model for ``--tokenizer`` is found ON DISK; nothing is ever fetched).  ``--scores`` adds "logprob", the sum of
+the generated tokens' log-probabilities, and "avg_logprob", that sum divided by their number -- a confidence to filter lines by.
 
 Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  With
 ``--slots N`` the pairs are encoded ``--pack G`` at a time and decoded in a pool of N decoder rows in which a finished row hands its
@@ -12,6 +13,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -101,6 +103,7 @@ def main(argv=None):
     ap.add_argument("--max-length", type=int, default=100, help="total tokens per utterance, start token included (the reference's notebooks: 100)")
     ap.add_argument("--slots", type=int, default=0, help="decode in a pool of N rows with finished rows refilled (1 .. 64); 0 = one generate call per batch")
     ap.add_argument("--pack", type=int, default=8, metavar="G", help="with --slots: batches per packed encoder forward")
+    ap.add_argument("--scores", action="store_true", help="also write \"logprob\" (sum over the generated tokens) and \"avg_logprob\" (per generated token)")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
     ap.add_argument("--precision", choices=["f16x3", "f32", "f16x2"], default="f16x3", help="arithmetic of the ENCODER (the decoder is fp32)")
     ap.add_argument("--out", default="-", help="JSON-lines file, - = stdout")
@@ -116,11 +119,16 @@ def main(argv=None):
     tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    def write(chunk, ids):
-        for (uid, _, _), row in zip(chunk, ids):
+    def write(chunk, ids, scores=None):
+        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated)."""
+        for i, ((uid, _, _), row) in enumerate(zip(chunk, ids)):
             rec = {"id": uid, "token_ids": row}
             if tok is not None:
                 rec["text"] = tok.decode(strip_special(row))
+            if scores is not None:
+                total, n = scores[i]
+                rec["logprob"] = total
+                rec["avg_logprob"] = total / n
             fh.write(json.dumps(rec) + "\n")
 
     try:
@@ -130,17 +138,31 @@ def main(argv=None):
             for w0 in range(0, len(starts), window):
                 chunks = [items[b0:b0 + args.batch_size] for b0 in starts[w0:w0 + window]]
                 feats = [load_batch(chunk, b0, processor, device) for chunk, b0 in zip(chunks, starts[w0:w0 + window])]
-                rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack)
+                rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
+                sums = None
+                if args.scores:
+                    rows, per_token = rows
+                    flat = torch.cat(per_token).cpu().tolist()  # one read-back per window
+                    ends = np.cumsum([t.shape[0] for t in per_token]).tolist()
+                    sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
                 for chunk in chunks:
                     ids, rows = [r.tolist() for r in rows[:len(chunk)]], rows[len(chunk):]
                     width = max(len(r) for r in ids)  # generate's rows: <pad> up to the longest row of the batch
-                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids])
+                    scores = None
+                    if sums is not None:
+                        scores, sums = [(v, len(r) - 1) for v, r in zip(sums[:len(chunk)], ids)], sums[len(chunk):]
+                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores)
         else:
             for b0 in starts:
                 chunk = items[b0:b0 + args.batch_size]
                 f = load_batch(chunk, b0, processor, device)
-                ids = model.generate(f["input_values"].to(device), f["attention_mask"].to(device), max_length=args.max_length).cpu().tolist()
-                write(chunk, ids)
+                x, m = f["input_values"].to(device), f["attention_mask"].to(device)
+                if args.scores:
+                    out = model.generate(x, m, max_length=args.max_length, return_dict_in_generate=True, output_scores=True)
+                    generated = (model._decoder_runtime.last_lengths - 1).tolist()
+                    write(chunk, out.sequences.cpu().tolist(), list(zip(out.sequence_logprobs.cpu().tolist(), generated)))
+                else:
+                    write(chunk, model.generate(x, m, max_length=args.max_length).cpu().tolist())
     finally:
         if fh is not sys.stdout:
             fh.close()
