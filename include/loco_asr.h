@@ -606,6 +606,45 @@ int loco_decoder_pool_read(loco_encoder* enc, int32_t slots, int32_t T_cap, int3
 int loco_decoder_score(const float* logits, int64_t ld, const int32_t* targets, int32_t B, int32_t S, int32_t V, int32_t ignore_index,
                        float* token_logprobs, int32_t* chosen, float* seq_logprob, int32_t* seq_count, float* loss, void* stream);
 
+/* ---- decoder attention probabilities and token timestamps ---------------------------------------------------------------------------
+ * The decoder's attention kernels never form P (online softmax, key splits); these entry points form it with launches of their own
+ * (csrc/decoder_probs.hip) beside the unchanged ones, in exact fp32 like every decoder product.
+ *   loco_decoder_forward_attn   loco_decoder_forward plus self_attentions / cross_attentions: each NULL or a HOST array of `layers`
+ *               device pointers, f32 [B, 12, S, S] / f32 [B, 12, S, T_enc] (HF's decoder_attentions / cross_attentions).  Self: key j
+ *               is visible to query i iff j <= i (no decoder padding mask: <pad> tokens are keys like any other).  Cross: key j is
+ *               visible iff j < enc_frames[b] (NULL: all T_enc).  Every other entry is written as exactly 0.0f and its key row is
+ *               never read.  Logits and hidden states are bit for bit loco_decoder_forward's; with both arrays NULL the call enqueues
+ *               exactly loco_decoder_forward's launches.  Same workspace and limits (S <= 450: LOCO_E_INVALID naming the limit; no
+ *               decoder weights: LOCO_E_STATE).
+ *   loco_decoder_align          where in the audio each token was spoken.  decoder_input_ids i32 [B, S] (device) are the labels shifted
+ *               right, so that query row s predicts label s; token_counts i32 [B] (device) = n_b, the labels of row b that count (a
+ *               prefix of the row).  A[b, s, t] = mean of the cross-attention P over the (layer, head) pairs in layer_heads (HOST, i32
+ *               [pairs][2], distinct; NULL = every pair), accumulated in fp32 layer-major, head-minor, then multiplied by 1 / pairs.
+ *               A monotone DTW over the cost -(double)A[b, s < n_b, t < F_b] (F_b = enc_frames[b], NULL: T_enc) runs in double: D[0,0] =
+ *               c[0,0], D[s,t] = c[s,t] + min(D[s-1,t-1], D[s-1,t], D[s,t-1]), missing neighbours +inf, ties resolved diagonal first,
+ *               then (s-1,t), then (s,t-1); one workgroup per clip.  start_frames / end_frames i32 [B, S] (device) = the first frame
+ *               and the last frame + 1 of token s on the path from (n_b - 1, F_b - 1) back to (0, 0); -1 for s >= n_b (a row with
+ *               n_b == 0 runs nothing).  attention: f32 [B, S, T_enc] (device) receiving A, or NULL (A stays in the workspace).
+ *               workspace >= loco_decoder_align_workspace_bytes (the decoder's workspace, ONE layer's P, A, one back-pointer byte per
+ *               cell).  Asynchronous; reads no device memory on the host.
+ *   loco_op_decoder_attention_probs   the probabilities kernel alone: q rows at q + b sq + i ldq, key rows at k + b sk + j ldk (floats;
+ *               head h at column 64 h; every stride a multiple of 4, row strides >= 768), P f32 [B, 12, Sq, Tk] dense.
+ *   loco_op_dtw_align           the DTW alone on a given A (row (b, s) at A + (b S + s) ld floats, ld >= T): n i32 [B] and frames i32
+ *               [B] or NULL on the device; workspace >= loco_dtw_align_workspace_bytes(B, S, T) bytes; S <= 450 (LOCO_E_INVALID). */
+int loco_decoder_forward_attn(loco_encoder* enc, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                              const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states,
+                              float* const* self_attentions, float* const* cross_attentions, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t loco_decoder_align_workspace_bytes(const loco_encoder* enc, int32_t B, int32_t T_enc, int32_t S);
+int loco_decoder_align(loco_encoder* enc, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                       const int32_t* decoder_input_ids, int32_t S, const int32_t* token_counts, const int32_t* layer_heads, int32_t pairs,
+                       float* attention, int32_t* start_frames, int32_t* end_frames, void* workspace, size_t workspace_bytes, void* stream);
+int loco_op_decoder_attention_probs(const float* q, const float* k, const int32_t* key_counts, float* P, int32_t B, int32_t Sq, int32_t Tk,
+                                    int32_t causal, int64_t ldq, int64_t sq, int64_t ldk, int64_t sk, float scale, void* stream);
+size_t loco_dtw_align_workspace_bytes(int32_t B, int32_t S, int32_t T);
+int loco_op_dtw_align(const float* A, int64_t ld, const int32_t* n, const int32_t* frames, int32_t B, int32_t S, int32_t T, int32_t* start,
+                      int32_t* end, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2116,14 +2116,26 @@ size_t loco_decoder_workspace_bytes(const loco_encoder* e, int32_t B, int32_t T_
     return p.total;
 }
 
-int loco_decoder_forward(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
-                         const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-    DecPlan p;
-    DEC_TRY(dec_check(e, "loco_decoder_forward", B, T_enc, S, workspace, workspace_bytes, p));
-    if (!enc_out || !decoder_input_ids || !logits) return fail(LOCO_E_INVALID, "loco_decoder_forward: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
+namespace {
+
+// What a teacher-forced pass hands out besides logits and hidden states.  All null: exactly loco_decoder_forward's launches.
+struct DecAttnSink {
+    float* const* self_attn = nullptr;   // host array of `layers` device pointers f32 [B,12,S,S], or null
+    float* const* cross_attn = nullptr;  // ... f32 [B,12,S,T_enc], or null
+    // loco_decoder_align: A = mean of the cross-attention P over the selected (layer, head) pairs, one layer's P in `scratch` at a time
+    float* mean = nullptr;
+    float* scratch = nullptr;
+    const unsigned* heads = nullptr;  // [layers] bit h = head h of the layer is selected
+    int pairs = 0, first_layer = 0, last_layer = 0;
+};
+
+// The layer walk of the teacher-forced pass, shared by loco_decoder_forward, loco_decoder_forward_attn and loco_decoder_align.  The
+// probabilities are formed by launches of their own between the existing ones (each reads the q projection its attention launch read,
+// before the next product overwrites it), so logits and hidden states are the same bits with and without them.  logits == null (the
+// alignment): the walk ends after the last selected layer's cross-attention.
+int dec_forward_walk(loco_encoder* e, const DecPlan& p, char* ws, const float* enc_out, const int32_t* enc_frames, const int32_t* decoder_input_ids,
+                     float* logits, float* const* hidden_states, const DecAttnSink& sink, hipStream_t s) {
+    const int B = p.B, T_enc = p.T, S = p.S;
     const DecoderW& d = e->dec;
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
@@ -2145,11 +2157,23 @@ int loco_decoder_forward(loco_encoder* e, const float* enc_out, const int32_t* e
         DEC_TRY(run_gemm(e, s, x0, kHidden, lw.wqkv + (size_t)kHidden * kHidden, kHidden, lw.bqkv + kHidden, nullptr, 0, cache, ld_self, M, 2 * kHidden,
                          kHidden, kEpiNone));
         DEC_TRY(dec_attention(s, q, kHidden, (long)S * kHidden, cache, ld_self, (long)S * ld_self, nullptr, ctx, B, S, S, 1, scr));
+        if (sink.self_attn)
+            HIP_TRY(launch_dec_attention_probs(q, kHidden, (long)S * kHidden, cache, ld_self, (long)S * ld_self, nullptr, sink.self_attn[l], B, S, S, 1,
+                                               1.0f, s));
         DEC_TRY(run_gemm(e, s, ctx, kHidden, lw.self_out.w, kHidden, lw.self_out.b, x0, kHidden, tmp, kHidden, M, kHidden, kHidden, kEpiResidual));
         DEC_TRY(run_ln(e, s, tmp, lw.self_ln.w, lw.self_ln.b, x1, M, kHidden));
         DEC_TRY(run_gemm(e, s, x1, kHidden, lw.wcq, kHidden, lw.bcq, nullptr, 0, q, kHidden, M, kHidden, kHidden, kEpiNone));
-        DEC_TRY(dec_attention(s, q, kHidden, (long)S * kHidden, F(p.off_cross) + (size_t)l * 2 * kHidden, ld_cross, (long)T_enc * ld_cross,
-                              I(p.off_frames), ctx, B, S, T_enc, 0, scr));
+        const float* ck = F(p.off_cross) + (size_t)l * 2 * kHidden;
+        DEC_TRY(dec_attention(s, q, kHidden, (long)S * kHidden, ck, ld_cross, (long)T_enc * ld_cross, I(p.off_frames), ctx, B, S, T_enc, 0, scr));
+        const bool averaged = sink.mean && sink.heads[l];
+        float* pc = sink.cross_attn ? sink.cross_attn[l] : (averaged ? sink.scratch : nullptr);
+        if (pc)
+            HIP_TRY(launch_dec_attention_probs(q, kHidden, (long)S * kHidden, ck, ld_cross, (long)T_enc * ld_cross, I(p.off_frames), pc, B, S, T_enc, 0,
+                                               1.0f, s));
+        if (averaged)
+            HIP_TRY(launch_dec_attn_mean(pc, sink.mean, B, S, T_enc, sink.heads[l], l == sink.first_layer, l == sink.last_layer,
+                                         1.0f / (float)sink.pairs, s));
+        if (!logits && !hidden_states && sink.mean && l == sink.last_layer) return LOCO_OK;
         DEC_TRY(run_gemm(e, s, ctx, kHidden, lw.cross_out.w, kHidden, lw.cross_out.b, x1, kHidden, tmp, kHidden, M, kHidden, kHidden, kEpiResidual));
         DEC_TRY(run_ln(e, s, tmp, lw.cross_ln.w, lw.cross_ln.b, x0, M, kHidden));
         DEC_TRY(run_gemm(e, s, x0, kHidden, lw.ffn_in.w, kHidden, lw.ffn_in.b, nullptr, 0, ffn, kFfn, M, kFfn, kHidden, kEpiGelu));
@@ -2157,8 +2181,107 @@ int loco_decoder_forward(loco_encoder* e, const float* enc_out, const int32_t* e
         DEC_TRY(run_ln(e, s, tmp, lw.final_ln.w, lw.final_ln.b, x0, M, kHidden));
     }
     if (hidden_states) DEC_TRY(run_copy(e, s, hidden_states[p.L], x0, (size_t)M * kHidden));
+    if (!logits) return LOCO_OK;
     // lm_head: N = vocab (81) is no multiple of the MFMA GEMM's 4-column epilogue; the weight-streaming kernel takes any N, 64 rows per grid row
     return run_skinny(s, x0, WB{d.lm_head, nullptr}, nullptr, logits, M, d.vocab, kHidden, kEpiNone);
+}
+
+int dec_forward_entry(const char* fn, loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                      const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, float* const* self_attentions,
+                      float* const* cross_attentions, void* workspace, size_t workspace_bytes, void* stream) {
+    DecPlan p;
+    DEC_TRY(dec_check(e, fn, B, T_enc, S, workspace, workspace_bytes, p));
+    if (!enc_out || !decoder_input_ids || !logits) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    for (int l = 0; l < p.L; ++l)
+        if ((self_attentions && !self_attentions[l]) || (cross_attentions && !cross_attentions[l]))
+            return fail(LOCO_E_INVALID, "%s: null attention output of layer %d (an array of %d device pointers is expected)", fn, l, p.L);
+    DecAttnSink sink;
+    sink.self_attn = self_attentions, sink.cross_attn = cross_attentions;
+    return dec_forward_walk(e, p, static_cast<char*>(workspace), enc_out, enc_frames, decoder_input_ids, logits, hidden_states, sink,
+                            (hipStream_t)stream);
+}
+
+// loco_decoder_align's workspace: the decoder's own, then one layer's cross-attention P, A, the DTW's back-pointers
+struct AlignPlan {
+    DecPlan dec;
+    size_t off_probs, off_mean, off_back, total;
+};
+
+void make_align_plan(int layers, int B, int T, int S, AlignPlan& a) {
+    make_dec_plan(layers, B, T, S, a.dec);
+    size_t o = a.dec.total;
+    const size_t cells = (size_t)B * S * T;
+    a.off_probs = o, o += align_up(cells * kHeads * sizeof(float));
+    a.off_mean = o, o += align_up(cells * sizeof(float));
+    a.off_back = o, o += align_up(cells);
+    a.total = o;
+}
+
+}  // namespace
+
+int loco_decoder_forward(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                         const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return dec_forward_entry("loco_decoder_forward", e, enc_out, enc_frames, B, T_enc, decoder_input_ids, S, logits, hidden_states, nullptr, nullptr,
+                             workspace, workspace_bytes, stream);
+}
+
+int loco_decoder_forward_attn(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc,
+                              const int32_t* decoder_input_ids, int32_t S, float* logits, float* const* hidden_states, float* const* self_attentions,
+                              float* const* cross_attentions, void* workspace, size_t workspace_bytes, void* stream) {
+    return dec_forward_entry("loco_decoder_forward_attn", e, enc_out, enc_frames, B, T_enc, decoder_input_ids, S, logits, hidden_states,
+                             self_attentions, cross_attentions, workspace, workspace_bytes, stream);
+}
+
+size_t loco_decoder_align_workspace_bytes(const loco_encoder* e, int32_t B, int32_t T_enc, int32_t S) {
+    if (!e || B <= 0 || T_enc <= 0 || S <= 0 || S > kDecMaxPositions) return 0;
+    if (!loco_has_decoder(e)) return 0;
+    AlignPlan a;
+    make_align_plan(decoder_layers_loaded(e, nullptr), B, T_enc, S, a);
+    return a.total;
+}
+
+int loco_decoder_align(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, const int32_t* decoder_input_ids,
+                       int32_t S, const int32_t* token_counts, const int32_t* layer_heads, int32_t pairs, float* attention, int32_t* start_frames,
+                       int32_t* end_frames, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_align";
+    DecPlan p;
+    DEC_TRY(dec_check(e, fn, B, T_enc, S, workspace, (size_t)-1, p));  // the size is checked against the alignment's own plan below
+    AlignPlan a;
+    make_align_plan(e->dec.layers, B, T_enc, S, a);
+    if (workspace_bytes < a.total) return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, a.total);
+    if (!enc_out || !decoder_input_ids || !token_counts || !start_frames || !end_frames) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    std::vector<unsigned> heads(a.dec.L, 0u);
+    DecAttnSink sink;
+    if (!layer_heads) {  // every pair
+        for (auto& h : heads) h = (1u << kHeads) - 1;
+        sink.pairs = a.dec.L * kHeads;
+    } else {
+        if (pairs < 1) return fail(LOCO_E_INVALID, "%s: an alignment head list needs at least one (layer, head) pair", fn);
+        for (int i = 0; i < pairs; ++i) {
+            const int l = layer_heads[2 * i], h = layer_heads[2 * i + 1];
+            if (l < 0 || l >= a.dec.L || h < 0 || h >= kHeads)
+                return fail(LOCO_E_INVALID, "%s: alignment head %d = (layer %d, head %d) is outside %d layers x %d heads", fn, i, l, h, a.dec.L, kHeads);
+            if (heads[l] >> h & 1u) return fail(LOCO_E_INVALID, "%s: alignment head (layer %d, head %d) is named twice", fn, l, h);
+            heads[l] |= 1u << h;
+        }
+        sink.pairs = pairs;
+    }
+    sink.first_layer = -1;
+    for (int l = 0; l < a.dec.L; ++l)
+        if (heads[l]) {
+            if (sink.first_layer < 0) sink.first_layer = l;
+            sink.last_layer = l;
+        }
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    sink.heads = heads.data();
+    sink.scratch = reinterpret_cast<float*>(ws + a.off_probs);
+    sink.mean = attention ? attention : reinterpret_cast<float*>(ws + a.off_mean);
+    DEC_TRY(dec_forward_walk(e, a.dec, ws, enc_out, enc_frames, decoder_input_ids, nullptr, nullptr, sink, s));
+    HIP_TRY(launch_dtw_align(sink.mean, T_enc, token_counts, reinterpret_cast<const int32_t*>(ws + a.dec.off_frames), B, S, T_enc, start_frames,
+                             end_frames, reinterpret_cast<unsigned char*>(ws + a.off_back), s));
+    return LOCO_OK;
 }
 
 int loco_decoder_begin(loco_encoder* e, const float* enc_out, const int32_t* enc_frames, int32_t B, int32_t T_enc, int32_t S_max,
@@ -2435,6 +2558,31 @@ int loco_op_decoder_attention(const float* q, const float* k, const float* v, co
         return fail(LOCO_E_WORKSPACE, "loco_op_decoder_attention: scratch %zu < %zu bytes", scratch_bytes, dec_attention_scratch_bytes(B, Sq, Tk));
     HIP_TRY(launch_dec_attention(q, kHidden, (long)Sq * kHidden, k, kHidden, (long)Tk * kHidden, v, kHidden, (long)Tk * kHidden, key_counts, out, kHidden,
                                  (long)Sq * kHidden, B, Sq, Tk, causal, causal_offset, scale, static_cast<float*>(scratch), (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+// ---- decoder attention probabilities and the DTW as operators (decoder_probs.hip) ----
+int loco_op_decoder_attention_probs(const float* q, const float* k, const int32_t* key_counts, float* P, int32_t B, int32_t Sq, int32_t Tk,
+                                    int32_t causal, int64_t ldq, int64_t sq, int64_t ldk, int64_t sk, float scale, void* stream) {
+    const char* fn = "loco_op_decoder_attention_probs";
+    if (!q || !k || !P || B <= 0 || Sq <= 0 || Tk <= 0) return fail(LOCO_E_INVALID, "%s: null / non-positive argument", fn);
+    if (ldq < kHidden || ldk < kHidden || ((ldq | ldk | sq | sk) & 3))
+        return fail(LOCO_E_INVALID, "%s: row strides must be >= 768 floats, every stride a multiple of 4 floats", fn);
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) return fail(LOCO_E_INVALID, "%s: q and k must be 16-byte aligned", fn);
+    HIP_TRY(launch_dec_attention_probs(q, (long)ldq, (long)sq, k, (long)ldk, (long)sk, key_counts, P, B, Sq, Tk, causal, scale, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+size_t loco_dtw_align_workspace_bytes(int32_t B, int32_t S, int32_t T) { return B > 0 && S > 0 && T > 0 ? (size_t)B * S * T : 0; }
+
+int loco_op_dtw_align(const float* A, int64_t ld, const int32_t* n, const int32_t* frames, int32_t B, int32_t S, int32_t T, int32_t* start,
+                      int32_t* end, void* workspace, void* stream) {
+    const char* fn = "loco_op_dtw_align";
+    if (!A || !n || !start || !end || !workspace) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (B <= 0 || S <= 0 || T <= 0) return fail(LOCO_E_INVALID, "%s: B, S and T must be positive", fn);
+    if (S > kDecAlignMaxTokens) return fail(LOCO_E_INVALID, "%s: %d tokens exceed the limit of %d rows (max_text_positions)", fn, S, kDecAlignMaxTokens);
+    if (ld < T) return fail(LOCO_E_INVALID, "%s: row stride ld = %lld < T = %d", fn, (long long)ld, T);
+    HIP_TRY(launch_dtw_align(A, (long)ld, n, frames, B, S, T, start, end, static_cast<unsigned char*>(workspace), (hipStream_t)stream));
     return LOCO_OK;
 }
 

@@ -370,6 +370,19 @@ hipError_t launch_token_logprob(const float* logits, long ld, const int32_t* tar
 hipError_t launch_score_reduce(const float* logprob, const int32_t* targets, int B, int S, int ignore_index, float* seq_logprob,
                                int32_t* seq_count, float* loss, hipStream_t s);
 
+// ---- decoder attention probabilities and token alignment (decoder_probs.hip) ----
+constexpr int kDecAlignMaxTokens = 450;  // token rows of one DTW workgroup (max_text_positions)
+// P[b,h,i,j] f32 [B,12,Sq,Tk] = softmax_j(scale q[b,i,h,:] . k[b,j,h,:]) over keys j < kcount[b] (null: Tk) and, when causal, j <= i;
+// every other entry exactly 0 and its key row never read; ld* = row strides, s* = clip strides in floats
+hipError_t launch_dec_attention_probs(const float* q, long ldq, long sq, const float* k, long ldk, long sk, const int32_t* kcount, float* P,
+                                      int B, int Sq, int Tk, int causal, float scale, hipStream_t s);
+// A[b,s,t] = (first ? 0 : A[b,s,t]) + sum of P[b,h,s,t] over the heads h whose bit is set in `heads`, ascending; times inv_n when last
+hipError_t launch_dec_attn_mean(const float* P, float* A, int B, int S, int T, unsigned heads, int first, int last, float inv_n, hipStream_t s);
+// monotone DTW over -A[b, s < n[b], t < frames[b] (null: T)] in double (row stride ld floats): start / end i32 [B,S] = each token's
+// first frame and last frame + 1 on the path, -1 for s >= n[b]; back >= B * S * T bytes of back-pointers; S <= kDecAlignMaxTokens
+hipError_t launch_dtw_align(const float* A, long ld, const int32_t* n, const int32_t* frames, int B, int S, int T, int32_t* start, int32_t* end,
+                            unsigned char* back, hipStream_t s);
+
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
 }  // namespace loco

@@ -6,7 +6,8 @@ the C ABI's ``loco_decoder_*`` entry points (include/loco_asr.h).
 
 ``SpeechT5DecoderWithTextPrenetMI355X`` (``.prenet``, ``.wrapped_decoder``) and ``SpeechT5TextDecoderPostnetMI355X`` only own
 parameters, so that ``load_state_dict`` of HF's dicts works; every FLOP runs in the HIP kernels of csrc/decoder.hip (the decode step)
-and the library's exact-fp32 GEMM / LayerNorm (the teacher-forced pass).  Greedy search only: beam search, sampling, prefixes and a
+and the library's exact-fp32 GEMM / LayerNorm (the teacher-forced pass); csrc/decoder_probs.hip forms the attention probabilities of
+``output_attentions=True`` and the token timestamps of ``align``.  Greedy search only: beam search, sampling, prefixes and a
 decoder attention mask raise by name.  Scores -- the ``labels=`` loss, per-token and per-transcript log-probabilities -- come from
 ``loco_decoder_score`` (csrc/decoder_score.hip) on the logits of either path.
 """
@@ -43,6 +44,10 @@ class Seq2SeqLMOutput:
     decoder_hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
     loss: Optional[torch.Tensor] = None            # labels=: 0-d, the mean cross-entropy over the labels that are not -100
     token_logprobs: Optional[torch.Tensor] = None  # labels=: [B, S] log P(labels[b, t]), 0 where the label is -100
+    # output_attentions=True: one fp32 tensor per layer, HF's shapes -- [B, 12, S, S], [B, 12, S, T_enc], [B, 12, T_enc, T_enc]
+    decoder_attentions: Optional[Tuple[torch.Tensor, ...]] = None
+    cross_attentions: Optional[Tuple[torch.Tensor, ...]] = None
+    encoder_attentions: Optional[Tuple[torch.Tensor, ...]] = None
 
 
 @dataclass
@@ -53,6 +58,51 @@ class TranscriptScores:
     sequence_logprob: torch.Tensor = None
     tokens: torch.Tensor = None
     loss: torch.Tensor = None
+
+
+FRAME_SECONDS = 320 / 16000  # the conv stack's stride: one encoder frame every 20 ms
+
+
+@dataclass
+class TokenAlignment:
+    """What ``align`` returns: token s of row b was spoken in the encoder frames ``start_frames[b, s]`` .. ``end_frames[b, s]`` (exclusive),
+    i32 [B, S], -1 where the label is -100.  ``start_times`` / ``end_times`` f32 [B, S] are those frames x 320 / 16000 seconds (-1 where
+    the frame is -1); the conv stack's receptive-field offset (a frame sees 400 samples, not 320) is ignored.  ``attention`` (on request)
+    is the matrix the path was found on: f32 [B, S, T_enc], the mean cross-attention of the selected (layer, head) pairs."""
+    start_frames: torch.Tensor = None
+    end_frames: torch.Tensor = None
+    start_times: torch.Tensor = None
+    end_times: torch.Tensor = None
+    attention: Optional[torch.Tensor] = None
+
+
+def alignment_counts(labels_host: torch.Tensor) -> torch.Tensor:
+    """n_b of every row of checked labels: the labels that count.  For an alignment -100 may only be a suffix of a row (a token
+    between two ignored ones has no place on a monotone path): ValueError naming the first counted label after an ignored one."""
+    counted = labels_host != IGNORE_INDEX
+    n = counted.sum(dim=1)
+    late = counted & (torch.arange(labels_host.shape[1])[None, :] >= n[:, None])
+    if bool(late.any()):
+        b, t = (int(v) for v in late.nonzero()[0])
+        first = int((~counted[b]).nonzero()[0])
+        raise ValueError(f"align: labels[{b}, {first}] = {IGNORE_INDEX} is followed by the counted label labels[{b}, {t}] = {int(labels_host[b, t])}; "
+                         f"{IGNORE_INDEX} may only pad the end of a row")
+    return n.to(torch.int32)
+
+
+def check_alignment_heads(alignment_heads, layers: int, heads: int = 12):
+    """None (every pair) or distinct (layer, head) pairs as a flat ctypes i32 array and their number; ValueError naming the offender."""
+    if alignment_heads is None:
+        return None, 0
+    pairs = [tuple(int(v) for v in p) for p in alignment_heads]
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError("alignment_heads must be a non-empty list of (layer, head) pairs")
+    for l, h in pairs:
+        if not (0 <= l < layers and 0 <= h < heads):
+            raise ValueError(f"alignment_heads: (layer {l}, head {h}) is outside {layers} layers x {heads} heads")
+    if len(set(pairs)) != len(pairs):
+        raise ValueError("alignment_heads names a (layer, head) pair twice")
+    return (C.c_int32 * (2 * len(pairs)))(*[v for p in pairs for v in p]), len(pairs)
 
 
 @dataclass
@@ -257,6 +307,50 @@ class DecoderRuntime:
             C.c_void_p(ids.data_ptr()), S, C.c_void_p(logits.data_ptr()), hs_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
             self._stream(device)), "loco_decoder_forward")
         return logits, (tuple(hs) if hs is not None else None)
+
+    def forward_attn(self, enc_out, frames, ids, output_hidden_states=False):
+        """``forward`` through loco_decoder_forward_attn: (logits, hidden states or None, self-attention P, cross-attention P), the
+        last two tuples of one fp32 tensor per layer, [B, 12, S, S] and [B, 12, S, T_enc]."""
+        B, T, _ = enc_out.shape
+        S = ids.shape[1]
+        if S > MAX_TEXT_POSITIONS:
+            raise ValueError(f"decoder_input_ids of {S} tokens exceed max_text_positions = {MAX_TEXT_POSITIONS}")
+        device = enc_out.device
+        ws = self.workspace(B, T, S, device)
+        layers = self.enc._decoder_layers
+        logits = torch.empty((B, S, self.enc._decoder_vocab), dtype=torch.float32, device=device)
+        hs, hs_ptrs = None, None
+        if output_hidden_states:
+            hs = [torch.empty((B, S, HIDDEN), dtype=torch.float32, device=device) for _ in range(layers + 1)]
+            hs_ptrs = (C.c_void_p * len(hs))(*[t.data_ptr() for t in hs])
+        self_p = tuple(torch.empty((B, 12, S, S), dtype=torch.float32, device=device) for _ in range(layers))
+        cross_p = tuple(torch.empty((B, 12, S, T), dtype=torch.float32, device=device) for _ in range(layers))
+        arr = lambda ts: (C.c_void_p * layers)(*[t.data_ptr() for t in ts])  # noqa: E731
+        _lib.check(self.lib.loco_decoder_forward_attn(
+            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
+            C.c_void_p(ids.data_ptr()), S, C.c_void_p(logits.data_ptr()), hs_ptrs, arr(self_p), arr(cross_p), C.c_void_p(ws.data_ptr()), ws.numel(),
+            self._stream(device)), "loco_decoder_forward_attn")
+        return logits, (tuple(hs) if hs is not None else None), self_p, cross_p
+
+    def align(self, enc_out, frames, ids, counts, heads=None, pairs=0, return_attention=False):
+        """loco_decoder_align: (start i32 [B, S], end i32 [B, S], A f32 [B, S, T] or None), all on the device, nothing read back."""
+        B, T, _ = enc_out.shape
+        S = ids.shape[1]
+        device = enc_out.device
+        need = int(self.lib.loco_decoder_align_workspace_bytes(self.enc._handle, B, T, S))
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = self._workspace
+        start = torch.empty((B, S), dtype=torch.int32, device=device)
+        end = torch.empty((B, S), dtype=torch.int32, device=device)
+        A = torch.empty((B, S, T), dtype=torch.float32, device=device) if return_attention else None
+        _lib.check(self.lib.loco_decoder_align(
+            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
+            C.c_void_p(ids.data_ptr()), S, C.c_void_p(counts.data_ptr()), heads, pairs, C.c_void_p(A.data_ptr()) if A is not None else None,
+            C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), self._stream(device)),
+            "loco_decoder_align")
+        return start, end, A
 
     def generate(self, enc_out, frames, max_length, return_logits=False):
         B, T, _ = enc_out.shape

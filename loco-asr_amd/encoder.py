@@ -766,19 +766,28 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         out = self.speecht5.encoder(input_values=input_values, attention_mask=attention_mask)
         return out.last_hidden_state, self.speecht5.encoder.last_frames
 
+    def _encode_with_attentions(self, input_values, attention_mask):
+        out = self.speecht5.encoder(input_values=input_values, attention_mask=attention_mask, output_attentions=True)
+        return out.last_hidden_state, self.speecht5.encoder.last_frames, out.attentions
+
     @torch.no_grad()
     def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 decoder_input_ids: Optional[torch.Tensor] = None, output_hidden_states: Optional[bool] = None,
-                labels: Optional[torch.Tensor] = None, **kwargs):
+                labels: Optional[torch.Tensor] = None, output_attentions: Optional[bool] = None, **kwargs):
         """``model(**audios, decoder_input_ids=ids)``: teacher-forced logits [B, S, vocab] and ``encoder_last_hidden_state``
         (``output_hidden_states=True``: also the 7 ``decoder_hidden_states``).  Causal self-attention over the ids as given (no
         decoder attention mask, as in the reference's calls); cross-attention over each clip's valid encoder frames.
 
         ``labels`` [B, S] (token ids, -100 = not counted): also ``loss``, HF's mean cross-entropy over the counted labels, and
         ``token_logprobs`` [B, S].  Without ``decoder_input_ids`` the decoder reads the labels shifted right (decoder.shift_tokens_right),
-        as HF does; with both, the given ids are read and the loss is taken against ``labels``."""
+        as HF does; with both, the given ids are read and the loss is taken against ``labels``.
+
+        ``output_attentions=True``: also ``decoder_attentions`` (6 x [B, 12, S, S], key j visible to query i iff j <= i),
+        ``cross_attentions`` (6 x [B, 12, S, T_enc], key j visible iff it is a valid frame of its clip) and ``encoder_attentions`` (the
+        encoder's own flag), fp32, masked entries exactly 0; formed by launches of their own (csrc/decoder_probs.hip), so logits
+        and hidden states are the same bits with and without the flag."""
         for k in kwargs:
-            if k in ("decoder_attention_mask", "past_key_values", "encoder_outputs", "use_cache", "output_attentions"):
+            if k in ("decoder_attention_mask", "past_key_values", "encoder_outputs", "use_cache"):
                 raise NotImplementedError(f"forward({k}=...) is not implemented")
             raise TypeError(f"forward() got an unexpected keyword argument '{k}'")
         self._require_decoder("forward(labels=...)" if labels is not None and decoder_input_ids is None else "forward(decoder_input_ids=...)")
@@ -792,16 +801,99 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
             if decoder_input_ids is None:
                 decoder_input_ids = dec.shift_tokens_right(host)
             targets = host.to(torch.int32)
-        enc_out, frames = self._encode(input_values, attention_mask)
+        enc_attn = self_attn = cross_attn = None
+        if output_attentions:
+            enc_out, frames, enc_attn = self._encode_with_attentions(input_values, attention_mask)
+        else:
+            enc_out, frames = self._encode(input_values, attention_mask)
         if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != enc_out.shape[0]:
             raise ValueError(f"decoder_input_ids must be [batch, tokens] with batch {enc_out.shape[0]}, got {tuple(decoder_input_ids.shape)}")
         ids = decoder_input_ids.to(device=enc_out.device, dtype=torch.int32).contiguous()
         with torch.cuda.device(enc_out.device):
-            logits, hidden = self._decoder_runtime.forward(enc_out, frames, ids, bool(output_hidden_states))
+            if output_attentions:
+                logits, hidden, self_attn, cross_attn = self._decoder_runtime.forward_attn(enc_out, frames, ids, bool(output_hidden_states))
+            else:
+                logits, hidden = self._decoder_runtime.forward(enc_out, frames, ids, bool(output_hidden_states))
             loss = logprobs = None
             if targets is not None:
                 logprobs, _, _, loss, _ = dec.score_logits(self.speecht5.encoder._lib, logits, targets.to(enc_out.device).contiguous(), *ids.shape)
-        return dec.Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden, loss=loss, token_logprobs=logprobs)
+        return dec.Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden, loss=loss, token_logprobs=logprobs,
+                                   decoder_attentions=self_attn, cross_attentions=cross_attn, encoder_attentions=enc_attn)
+
+    @torch.no_grad()
+    def align(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+              alignment_heads=None, return_attention: bool = False):
+        """Where in the audio each token of the transcripts ``labels`` [B, S] was spoken: a decoder.TokenAlignment with ``start_frames`` /
+        ``end_frames`` i32 [B, S] (encoder frames, end exclusive, -1 where the label is -100) and ``start_times`` / ``end_times`` in seconds
+        (frames x 320 / 16000, the conv stack's stride; its receptive-field offset is ignored).  -100 may only pad the end of a row.
+
+        One teacher-forced pass on the labels shifted right; the mean of the cross-attention probabilities over ``alignment_heads``
+        ((layer, head) pairs; None = all 72) is the soft alignment A [B, S, T_enc] (``return_attention=True`` hands it out), and a
+        monotone DTW over -A from (0, 0) to (n_b - 1, frames_b - 1) -- on the device, in double -- gives every token its frames."""
+        self._require_decoder("align()")
+        if labels is None:
+            raise ValueError("align() needs labels")
+        from . import decoder as dec
+        enc = self.speecht5.encoder
+        host = dec.check_labels(labels, int(input_values.shape[0]), enc._decoder_vocab)
+        counts = dec.alignment_counts(host)
+        heads, pairs = dec.check_alignment_heads(alignment_heads, enc._decoder_layers)
+        enc_out, frames = self._encode(input_values, attention_mask)
+        return self._align_encoded(enc_out, frames, host, counts, heads, pairs, return_attention)
+
+    def _align_encoded(self, enc_out, frames, labels_host, counts, heads, pairs, return_attention):
+        from . import decoder as dec
+        device = enc_out.device
+        ids = dec.shift_tokens_right(labels_host).to(device=device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(device):
+            start, end, A = self._decoder_runtime.align(enc_out, frames, ids, counts.to(device).contiguous(), heads, pairs, return_attention)
+            seconds = lambda f: torch.where(f < 0, -1.0, f.to(torch.float32) * dec.FRAME_SECONDS).to(torch.float32)  # noqa: E731
+            return dec.TokenAlignment(start_frames=start, end_frames=end, start_times=seconds(start), end_times=seconds(end), attention=A)
+
+    @torch.no_grad()
+    def align_many(self, batches, labels, pack: int = 8, alignment_heads=None, return_attention: bool = False):
+        """Token timestamps of a corpus, built the way ``score_many`` is: ``batches`` is what ``generate_many`` takes, ``labels`` one
+        1-D LongTensor per utterance in input order (no -100 needed: each row is padded to its pack's longest).  The batches are
+        encoded ``pack`` at a time through ``forward_packed``; each pack's clips go through ONE ``align`` pass on the packed output and
+        its frame counts.  Returns a list, in input order, of decoder.TokenAlignment whose fields are the utterance's own 1-D slices
+        (``attention`` [len, T of its pack]).  An utterance's A is that of ``align`` on its own batch up to the fp32 summation order
+        of the packed encoder and of the decoder's products; its path is the DTW of that A."""
+        from . import decoder as dec
+        self._require_decoder("align_many()")
+        batches = [b for b in batches if b["input_values"].shape[0]]
+        labels = list(labels)
+        total = sum(int(b["input_values"].shape[0]) for b in batches)
+        if len(labels) != total:
+            raise ValueError(f"align_many: {len(labels)} label rows for {total} utterances")
+        if int(pack) < 1:
+            raise ValueError("pack must be >= 1")
+        enc = self.speecht5.encoder
+        heads, pairs = dec.check_alignment_heads(alignment_heads, enc._decoder_layers)
+        hosts = []
+        for u, lab in enumerate(labels):
+            if not torch.is_tensor(lab) or lab.dim() != 1:
+                raise ValueError(f"align_many: labels[{u}] must be a 1-D tensor of token ids")
+            hosts.append(dec.check_labels(lab[None], 1, enc._decoder_vocab)[0])
+            dec.alignment_counts(hosts[-1][None])
+        results, u0 = [], 0
+        for g0 in range(0, len(batches), int(pack)):
+            group = batches[g0:g0 + int(pack)]
+            ticket = enc.forward_packed_async(group)
+            ticket.result()
+            out, _ = ticket.packed_output()
+            n = int(out.shape[0])
+            rows = hosts[u0:u0 + n]
+            S = max(int(r.shape[0]) for r in rows)
+            lab = torch.full((n, S), dec.IGNORE_INDEX, dtype=torch.long)
+            for i, r in enumerate(rows):
+                lab[i, :r.shape[0]] = r
+            al = self._align_encoded(out, enc.last_frames, lab, dec.alignment_counts(lab), heads, pairs, return_attention)
+            for i, r in enumerate(rows):
+                k = int(r.shape[0])
+                results.append(dec.TokenAlignment(start_frames=al.start_frames[i, :k], end_frames=al.end_frames[i, :k], start_times=al.start_times[i, :k],
+                                                  end_times=al.end_times[i, :k], attention=al.attention[i, :k] if al.attention is not None else None))
+            u0 += n
+        return results
 
     @torch.no_grad()
     def score(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):

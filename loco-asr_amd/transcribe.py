@@ -1,6 +1,8 @@
 """Greedy transcription CLI: ``python -m loco-asr_amd.transcribe`` writes one JSON line per utterance, {"id", "token_ids"} (and
 "text" when a SentencePiece model for ``--tokenizer`` is found ON DISK; nothing is ever fetched).  ``--scores`` adds "logprob", the sum of
 the generated tokens' log-probabilities, and "avg_logprob", that sum divided by their number -- a confidence to filter lines by.
+``--timestamps`` adds "token_times", one [start_s, end_s] pair per generated token (the ids after the start token, up to the row's own
+end; the <pad> columns behind it get none): ``align`` / ``align_many`` on the generated ids, the mean cross-attention and a monotone DTW.
 
 Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  With
 ``--slots N`` the pairs are encoded ``--pack G`` at a time and decoded in a pool of N decoder rows in which a finished row hands its
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from . import synth
-from .decoder import EOS_TOKEN_ID, PAD_TOKEN_ID
+from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID
 from .encoder import SpeechT5ForSpeechToTextMI355X
 
 
@@ -48,6 +50,30 @@ def strip_special(ids):
         if t != PAD_TOKEN_ID:
             out.append(int(t))
     return out
+
+
+def row_length(row):
+    """Tokens of a generated row up to and including its </s> (the start token counts; the whole row when it never ended)."""
+    for i, t in enumerate(row[1:], 1):
+        if t == EOS_TOKEN_ID:
+            return i + 1
+    return len(row)
+
+
+def timestamp_labels(rows):
+    """The labels ``align`` reads for generated rows: the ids after the start token, the <pad> columns behind a row's end as -100."""
+    width = max(len(r) for r in rows) - 1
+    lab = torch.full((len(rows), max(width, 1)), IGNORE_INDEX, dtype=torch.long)
+    for i, r in enumerate(rows):
+        n = row_length(r) - 1
+        lab[i, :n] = torch.tensor(r[1:1 + n], dtype=torch.long)
+    return lab
+
+
+def token_times(al, i, n):
+    """[[start_s, end_s], ...] of the first n tokens of row i of a TokenAlignment (one read-back)."""
+    st, en = al.start_times[i, :n].cpu().tolist(), al.end_times[i, :n].cpu().tolist()
+    return [[round(a, 4), round(b, 4)] for a, b in zip(st, en)]
 
 
 def gather_items(args):
@@ -104,6 +130,7 @@ def main(argv=None):
     ap.add_argument("--slots", type=int, default=0, help="decode in a pool of N rows with finished rows refilled (1 .. 64); 0 = one generate call per batch")
     ap.add_argument("--pack", type=int, default=8, metavar="G", help="with --slots: batches per packed encoder forward")
     ap.add_argument("--scores", action="store_true", help="also write \"logprob\" (sum over the generated tokens) and \"avg_logprob\" (per generated token)")
+    ap.add_argument("--timestamps", action="store_true", help="also write \"token_times\": [start_s, end_s] of every generated token (cross-attention + DTW)")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
     ap.add_argument("--precision", choices=["f16x3", "f32", "f16x2"], default="f16x3", help="arithmetic of the ENCODER (the decoder is fp32)")
     ap.add_argument("--out", default="-", help="JSON-lines file, - = stdout")
@@ -119,8 +146,8 @@ def main(argv=None):
     tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    def write(chunk, ids, scores=None):
-        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated)."""
+    def write(chunk, ids, scores=None, times=None):
+        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated); ``times``: per row the pairs."""
         for i, ((uid, _, _), row) in enumerate(zip(chunk, ids)):
             rec = {"id": uid, "token_ids": row}
             if tok is not None:
@@ -129,6 +156,8 @@ def main(argv=None):
                 total, n = scores[i]
                 rec["logprob"] = total
                 rec["avg_logprob"] = total / n
+            if times is not None:
+                rec["token_times"] = times[i]
             fh.write(json.dumps(rec) + "\n")
 
     try:
@@ -145,24 +174,37 @@ def main(argv=None):
                     flat = torch.cat(per_token).cpu().tolist()  # one read-back per window
                     ends = np.cumsum([t.shape[0] for t in per_token]).tolist()
                     sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
+                stamps = None
+                if args.timestamps:  # the utterances' own tokens after the start token: no padding inside align_many's input
+                    als = model.align_many(feats, [r[1:] for r in rows], pack=args.pack)
+                    stamps = [[[round(a, 4), round(b, 4)] for a, b in zip(al.start_times.cpu().tolist(), al.end_times.cpu().tolist())] for al in als]
                 for chunk in chunks:
                     ids, rows = [r.tolist() for r in rows[:len(chunk)]], rows[len(chunk):]
                     width = max(len(r) for r in ids)  # generate's rows: <pad> up to the longest row of the batch
                     scores = None
                     if sums is not None:
                         scores, sums = [(v, len(r) - 1) for v, r in zip(sums[:len(chunk)], ids)], sums[len(chunk):]
-                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores)
+                    times = None
+                    if stamps is not None:
+                        times, stamps = stamps[:len(chunk)], stamps[len(chunk):]
+                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times)
         else:
             for b0 in starts:
                 chunk = items[b0:b0 + args.batch_size]
                 f = load_batch(chunk, b0, processor, device)
                 x, m = f["input_values"].to(device), f["attention_mask"].to(device)
+                scores = None
                 if args.scores:
                     out = model.generate(x, m, max_length=args.max_length, return_dict_in_generate=True, output_scores=True)
                     generated = (model._decoder_runtime.last_lengths - 1).tolist()
-                    write(chunk, out.sequences.cpu().tolist(), list(zip(out.sequence_logprobs.cpu().tolist(), generated)))
+                    ids, scores = out.sequences.cpu().tolist(), list(zip(out.sequence_logprobs.cpu().tolist(), generated))
                 else:
-                    write(chunk, model.generate(x, m, max_length=args.max_length).cpu().tolist())
+                    ids = model.generate(x, m, max_length=args.max_length).cpu().tolist()
+                times = None
+                if args.timestamps:
+                    al = model.align(x, m, labels=timestamp_labels(ids))
+                    times = [token_times(al, i, row_length(r) - 1) for i, r in enumerate(ids)]
+                write(chunk, ids, scores, times)
     finally:
         if fh is not sys.stdout:
             fh.close()
