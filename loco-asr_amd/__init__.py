@@ -7,10 +7,10 @@ loads the HIP library (``libloco_asr.so``) and fails loudly if it has not been b
 """
 from . import synth  # noqa: F401
 from ._lib import LIB_PATH, LocoError  # noqa: F401
-from .encoder import (BaseModelOutput, Pack, SpeechT5EncoderWithSpeechPrenetMI355X,  # noqa: F401
-                      SpeechT5ForSpeechToTextMI355X, sinusoid_table)
+from .encoder import BaseModelOutput, Pack, SpeechT5EncoderWithSpeechPrenetMI355X, sinusoid_table  # noqa: F401
 from .feature_extractor import BatchFeature, SpeechT5FeatureExtractorMI355X  # noqa: F401
 from .intent_head import IntentClassifierMI355X  # noqa: F401
+from .speech_to_text import SpeechT5ForSpeechToTextMI355X  # noqa: F401
 from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextToSpeechMI355X,  # noqa: F401
                            scaled_positional_table)
 

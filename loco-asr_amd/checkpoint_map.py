@@ -121,7 +121,7 @@ def to_fairseq_names(prenet_sd: Dict[str, object], encoder_sd: Dict[str, object]
 # ---- checkpoints on disk ----------------------------------------------------------------------------------------------------
 # The two callers the reference has:
 #   * fine-tuned: SpeechT5ForSpeechToText.from_pretrained("microsoft/speecht5_asr")       (…finetuned…py:95)
-#       -> load_hf_checkpoint(dir) + SpeechT5ForSpeechToTextMI355X.from_pretrained(dir) (encoder.py)
+#       -> load_hf_checkpoint(dir) + SpeechT5ForSpeechToTextMI355X.from_pretrained(dir) (speech_to_text.py)
 #   * base: three pickles under extracted/speecht5/mapping/ made from a fairseq speecht5_base.pt (…base…py:40-49,
 #     map_speecht5_hf.py:157-181)  ->  `python -m loco-asr_amd.checkpoint_map speecht5_base.pt --out extracted/speecht5/mapping/`
 HF_PREFIXES = ("speecht5.encoder.prenet.", "speecht5.encoder.wrapped_encoder.")

@@ -19,9 +19,9 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
-from torch import nn
 
 from . import _lib
+from .holders import _register, _WeightHolder
 from .synth import DECODER_LAYERS, FFN, HIDDEN, MAX_TEXT_POSITIONS, TEXT_VOCAB
 
 DECODER_START_TOKEN_ID = 2
@@ -76,6 +76,11 @@ class TokenAlignment:
     attention: Optional[torch.Tensor] = None
 
 
+def _ptr(t):
+    """``t``'s address for the C ABI, None (a null pointer) for None."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def alignment_counts(labels_host: torch.Tensor) -> torch.Tensor:
     """n_b of every row of checked labels: the labels that count.  For an alignment -100 may only be a suffix of a row (a token
     between two ignored ones has no place on a monotone path): ValueError naming the first counted label after an ignored one."""
@@ -116,16 +121,6 @@ class GreedySearchOutput:
     sequence_logprobs: Optional[torch.Tensor] = None
 
 
-def _holder_base():
-    from .encoder import _WeightHolder
-    return _WeightHolder
-
-
-def _register(root, dotted, shape, init=0.0):
-    from .encoder import _register as reg
-    reg(root, dotted, shape, init)
-
-
 def decoder_layer_keys(layer: int):
     """(name below ``wrapped_decoder.``, shape, init) of one SpeechT5DecoderLayer (HF modeling_speecht5.py:1070-1100)."""
     b = f"layers.{layer}."
@@ -142,35 +137,30 @@ def decoder_layer_keys(layer: int):
     yield f"{b}feed_forward.output_dense.bias", (HIDDEN,), 0.0
 
 
-def make_decoder_modules(owner_ref, layers: int = DECODER_LAYERS, vocab: int = TEXT_VOCAB):
-    """(SpeechT5DecoderWithTextPrenetMI355X, SpeechT5TextDecoderPostnetMI355X) whose parameter changes mark ``owner_ref()``'s
-    weights dirty (the encoder module owns the library handle)."""
-    Holder = _holder_base()
+class SpeechT5DecoderWithTextPrenetMI355X(_WeightHolder):
+    """Parameter names of HF SpeechT5DecoderWithTextPrenet: ``prenet.embed_tokens.weight`` and ``wrapped_decoder.layers.N.*``
+    (``prenet.embed_positions.weights`` is a non-persistent buffer in HF: not a key; the table is regenerated).  Parameter changes
+    mark ``owner_ref()``'s weights dirty (the encoder module owns the library handle)."""
 
-    class SpeechT5DecoderWithTextPrenetMI355X(Holder):
-        """Parameter names of HF SpeechT5DecoderWithTextPrenet: ``prenet.embed_tokens.weight`` and ``wrapped_decoder.layers.N.*``
-        (``prenet.embed_positions.weights`` is a non-persistent buffer in HF: not a key; the table is regenerated)."""
+    def __init__(self, owner_ref, layers: int = DECODER_LAYERS, vocab: int = TEXT_VOCAB):
+        super().__init__(owner_ref)
+        _register(self, "prenet.embed_tokens.weight", (vocab, HIDDEN))
+        self.num_layers = layers
+        for l in range(layers):
+            for name, shape, init in decoder_layer_keys(l):
+                _register(self, "wrapped_decoder." + name, shape, init)
 
-        def __init__(self):
-            super().__init__(owner_ref)
-            _register(self, "prenet.embed_tokens.weight", (vocab, HIDDEN))
-            self.num_layers = layers
-            for l in range(layers):
-                for name, shape, init in decoder_layer_keys(l):
-                    _register(self, "wrapped_decoder." + name, shape, init)
+    def _translate(self, sd):
+        sd.pop("prenet.embed_positions.weights", None)
+        return sd
 
-        def _translate(self, sd):
-            sd.pop("prenet.embed_positions.weights", None)
-            return sd
 
-    class SpeechT5TextDecoderPostnetMI355X(Holder):
-        """Parameter name of HF SpeechT5TextDecoderPostnet: ``lm_head.weight`` (no bias)."""
+class SpeechT5TextDecoderPostnetMI355X(_WeightHolder):
+    """Parameter name of HF SpeechT5TextDecoderPostnet: ``lm_head.weight`` (no bias)."""
 
-        def __init__(self):
-            super().__init__(owner_ref)
-            _register(self, "lm_head.weight", (vocab, HIDDEN))
-
-    return SpeechT5DecoderWithTextPrenetMI355X(), SpeechT5TextDecoderPostnetMI355X()
+    def __init__(self, owner_ref, vocab: int = TEXT_VOCAB):
+        super().__init__(owner_ref)
+        _register(self, "lm_head.weight", (vocab, HIDDEN))
 
 
 def position_ids(input_ids: torch.Tensor, past_key_values_length: int = 0) -> torch.Tensor:
@@ -226,10 +216,9 @@ def score_logits(lib, logits: torch.Tensor, targets: Optional[torch.Tensor], B: 
     cnt = torch.empty((B,), dtype=torch.int32, device=device) if reduce else None
     loss = torch.empty((1,), dtype=torch.float32, device=device) if reduce else None
     ch = torch.empty((B, S), dtype=torch.int32, device=device) if chosen else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     with torch.cuda.device(device):
-        _lib.check(lib.loco_decoder_score(p(rows), rows.stride(0) if rows.shape[0] > 1 else V, p(targets), B, S, V, IGNORE_INDEX, p(lp), p(ch), p(seq),
-                                          p(cnt), p(loss), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "loco_decoder_score")
+        _lib.check(lib.loco_decoder_score(_ptr(rows), rows.stride(0) if rows.shape[0] > 1 else V, _ptr(targets), B, S, V, IGNORE_INDEX, _ptr(lp), _ptr(ch),
+                                          _ptr(seq), _ptr(cnt), _ptr(loss), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "loco_decoder_score")
     return lp, seq, cnt, (loss.reshape(()) if loss is not None else None), ch
 
 
@@ -274,43 +263,29 @@ class DecoderRuntime:
         self.enc = encoder
         self.lib = encoder._lib
         self._workspace = None
+        self.last_lengths = None  # after generate: i32 [B] on the host, every row's length
 
     def max_batch(self) -> int:
         return int(self.lib.loco_decoder_max_batch())
 
-    def workspace(self, B, T, S, device):
-        need = int(self.lib.loco_decoder_workspace_bytes(self.enc._handle, B, T, S))
+    def _grown(self, need, device):
+        """The workspace, replaced by one of ``need`` bytes when it is smaller or on another device."""
         if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
             self._workspace = None
             self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
         return self._workspace
 
+    def workspace(self, B, T, S, device):
+        return self._grown(int(self.lib.loco_decoder_workspace_bytes(self.enc._handle, B, T, S)), device)
+
     @staticmethod
     def _stream(device):
         return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
-    def forward(self, enc_out, frames, ids, output_hidden_states=False):
-        B, T, _ = enc_out.shape
-        S = ids.shape[1]
-        if S > MAX_TEXT_POSITIONS:
-            raise ValueError(f"decoder_input_ids of {S} tokens exceed max_text_positions = {MAX_TEXT_POSITIONS}")
-        device = enc_out.device
-        ws = self.workspace(B, T, S, device)
-        vocab = self.enc._decoder_vocab
-        logits = torch.empty((B, S, vocab), dtype=torch.float32, device=device)
-        hs, hs_ptrs = None, None
-        if output_hidden_states:
-            hs = [torch.empty((B, S, HIDDEN), dtype=torch.float32, device=device) for _ in range(self.enc._decoder_layers + 1)]
-            hs_ptrs = (C.c_void_p * len(hs))(*[t.data_ptr() for t in hs])
-        _lib.check(self.lib.loco_decoder_forward(
-            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
-            C.c_void_p(ids.data_ptr()), S, C.c_void_p(logits.data_ptr()), hs_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
-            self._stream(device)), "loco_decoder_forward")
-        return logits, (tuple(hs) if hs is not None else None)
-
-    def forward_attn(self, enc_out, frames, ids, output_hidden_states=False):
-        """``forward`` through loco_decoder_forward_attn: (logits, hidden states or None, self-attention P, cross-attention P), the
-        last two tuples of one fp32 tensor per layer, [B, 12, S, S] and [B, 12, S, T_enc]."""
+    def _teacher_forced(self, entry, enc_out, frames, ids, output_hidden_states, probs):
+        """The teacher-forced pass through the entry point ``entry`` (loco_decoder_forward or loco_decoder_forward_attn): allocates the
+        logits, the hidden states when asked for and, with ``probs``, the per-layer self- and cross-attention probabilities that
+        loco_decoder_forward_attn also takes."""
         B, T, _ = enc_out.shape
         S = ids.shape[1]
         if S > MAX_TEXT_POSITIONS:
@@ -323,33 +298,35 @@ class DecoderRuntime:
         if output_hidden_states:
             hs = [torch.empty((B, S, HIDDEN), dtype=torch.float32, device=device) for _ in range(layers + 1)]
             hs_ptrs = (C.c_void_p * len(hs))(*[t.data_ptr() for t in hs])
-        self_p = tuple(torch.empty((B, 12, S, S), dtype=torch.float32, device=device) for _ in range(layers))
-        cross_p = tuple(torch.empty((B, 12, S, T), dtype=torch.float32, device=device) for _ in range(layers))
-        arr = lambda ts: (C.c_void_p * layers)(*[t.data_ptr() for t in ts])  # noqa: E731
-        _lib.check(self.lib.loco_decoder_forward_attn(
-            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
-            C.c_void_p(ids.data_ptr()), S, C.c_void_p(logits.data_ptr()), hs_ptrs, arr(self_p), arr(cross_p), C.c_void_p(ws.data_ptr()), ws.numel(),
-            self._stream(device)), "loco_decoder_forward_attn")
-        return logits, (tuple(hs) if hs is not None else None), self_p, cross_p
+        attn = ()
+        if probs:
+            attn = (tuple(torch.empty((B, 12, S, S), dtype=torch.float32, device=device) for _ in range(layers)),
+                    tuple(torch.empty((B, 12, S, T), dtype=torch.float32, device=device) for _ in range(layers)))
+        _lib.check(getattr(self.lib, entry)(self.enc._handle, _ptr(enc_out), _ptr(frames), B, T, _ptr(ids), S, _ptr(logits), hs_ptrs,
+                         *[(C.c_void_p * layers)(*[t.data_ptr() for t in ts]) for ts in attn], _ptr(ws), ws.numel(), self._stream(device)),
+                   entry)
+        return (logits, (tuple(hs) if hs is not None else None)) + attn
+
+    def forward(self, enc_out, frames, ids, output_hidden_states=False):
+        return self._teacher_forced("loco_decoder_forward", enc_out, frames, ids, output_hidden_states, False)
+
+    def forward_attn(self, enc_out, frames, ids, output_hidden_states=False):
+        """``forward`` through loco_decoder_forward_attn: (logits, hidden states or None, self-attention P, cross-attention P), the
+        last two tuples of one fp32 tensor per layer, [B, 12, S, S] and [B, 12, S, T_enc]."""
+        return self._teacher_forced("loco_decoder_forward_attn", enc_out, frames, ids, output_hidden_states, True)
 
     def align(self, enc_out, frames, ids, counts, heads=None, pairs=0, return_attention=False):
         """loco_decoder_align: (start i32 [B, S], end i32 [B, S], A f32 [B, S, T] or None), all on the device, nothing read back."""
         B, T, _ = enc_out.shape
         S = ids.shape[1]
         device = enc_out.device
-        need = int(self.lib.loco_decoder_align_workspace_bytes(self.enc._handle, B, T, S))
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        ws = self._workspace
+        ws = self._grown(int(self.lib.loco_decoder_align_workspace_bytes(self.enc._handle, B, T, S)), device)
         start = torch.empty((B, S), dtype=torch.int32, device=device)
         end = torch.empty((B, S), dtype=torch.int32, device=device)
         A = torch.empty((B, S, T), dtype=torch.float32, device=device) if return_attention else None
         _lib.check(self.lib.loco_decoder_align(
-            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
-            C.c_void_p(ids.data_ptr()), S, C.c_void_p(counts.data_ptr()), heads, pairs, C.c_void_p(A.data_ptr()) if A is not None else None,
-            C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), self._stream(device)),
-            "loco_decoder_align")
+            self.enc._handle, _ptr(enc_out), _ptr(frames), B, T, _ptr(ids), S, _ptr(counts), heads, pairs, _ptr(A), _ptr(start), _ptr(end),
+            _ptr(ws), ws.numel(), self._stream(device)), "loco_decoder_align")
         return start, end, A
 
     def generate(self, enc_out, frames, max_length, return_logits=False):
@@ -364,9 +341,8 @@ class DecoderRuntime:
         steps = torch.zeros((max_length - 1, B, vocab), dtype=torch.float32, device=device) if return_logits else None
         n = C.c_int32(0)
         _lib.check(self.lib.loco_decoder_generate(
-            self.enc._handle, C.c_void_p(enc_out.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, B, T,
-            max_length, C.c_void_p(tokens.data_ptr()), C.c_void_p(lengths.data_ptr()), C.byref(n), C.c_void_p(steps.data_ptr()) if steps is not None else None,
-            C.c_void_p(ws.data_ptr()), ws.numel(), self._stream(device)), "loco_decoder_generate")
+            self.enc._handle, _ptr(enc_out), _ptr(frames), B, T, max_length, _ptr(tokens), _ptr(lengths), C.byref(n), _ptr(steps),
+            _ptr(ws), ws.numel(), self._stream(device)), "loco_decoder_generate")
         S = int(n.value)
         ids = tokens[:, :S].to(torch.long).to(device)
         self.last_lengths = lengths
@@ -431,7 +407,7 @@ class DecoderPool:
         self._score_rounds = []             # (first step, log-probabilities [k, slots]) likewise
 
     def _ws(self):
-        return C.c_void_p(self.workspace.data_ptr())
+        return _ptr(self.workspace)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -454,8 +430,8 @@ class DecoderPool:
         out = first.enc_out
         frames = first.frames[first.clip:] if first.frames is not None else None
         _lib.check(self.lib.loco_decoder_pool_admit(
-            self.enc._handle, *self._shape, n, ids, C.c_void_p(out[first.clip].data_ptr()), out.stride(0),
-            rows, C.c_void_p(frames.data_ptr()) if frames is not None else None, caps, self._ws(), self.workspace.numel(), self._stream()),
+            self.enc._handle, *self._shape, n, ids, _ptr(out[first.clip]), out.stride(0),
+            rows, _ptr(frames), caps, self._ws(), self.workspace.numel(), self._stream()),
             "loco_decoder_pool_admit")
         for r, it in zip(slot_ids, items):
             self.entries[r] = (it, self.steps)
@@ -478,14 +454,13 @@ class DecoderPool:
 
     def step(self, logits=None):
         max_pos, max_frames, _ = self.bounds()
-        _lib.check(self.lib.loco_decoder_pool_step(self.enc._handle, *self._shape, max_pos, max_frames,
-                                                   C.c_void_p(logits.data_ptr()) if logits is not None else None, self._ws(), self.workspace.numel(),
+        _lib.check(self.lib.loco_decoder_pool_step(self.enc._handle, *self._shape, max_pos, max_frames, _ptr(logits), self._ws(), self.workspace.numel(),
                                                    self._stream()), "loco_decoder_pool_step")
         self.steps += 1
 
     def poll(self):
         """(status, lengths) of every slot after the work enqueued so far (waits for the stream)."""
-        _lib.check(self.lib.loco_decoder_pool_poll(self.enc._handle, *self._shape, C.c_void_p(self.block.data_ptr()), self._ws(), self.workspace.numel(),
+        _lib.check(self.lib.loco_decoder_pool_poll(self.enc._handle, *self._shape, _ptr(self.block), self._ws(), self.workspace.numel(),
                                                    self._stream()), "loco_decoder_pool_poll")
         torch.cuda.current_stream(self.device).synchronize()
         b = self.block.tolist()
@@ -497,7 +472,7 @@ class DecoderPool:
         status, lengths = self.poll()
         done = [r for r in range(self.slots) if self.entries[r] is not None and status[r] == 2]
         for r in done:
-            _lib.check(self.lib.loco_decoder_pool_read(self.enc._handle, *self._shape, r, C.c_void_p(self.tokens[r].data_ptr()), self._ws(),
+            _lib.check(self.lib.loco_decoder_pool_read(self.enc._handle, *self._shape, r, _ptr(self.tokens[r]), self._ws(),
                                                        self.workspace.numel(), self._stream()), "loco_decoder_pool_read")
         if done:
             torch.cuda.current_stream(self.device).synchronize()

@@ -31,7 +31,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .synth import (CONV_DIM, CONV_KERNEL, FFN, HEAD_DIM, HEADS, HIDDEN, LAYERS, POS_CONV_GROUPS, POS_CONV_K, REL_MAX)
+from .holders import _Ref, _register, _WeightHolder
+from .synth import (CONV_DIM, CONV_KERNEL, FFN, HEAD_DIM, HEADS, HIDDEN, LAYERS, MAX_TEXT_POSITIONS, POS_CONV_GROUPS, POS_CONV_K, REL_MAX)
 
 PAD_TOKEN_ID = 1
 MAX_SPEECH_POSITIONS = 4000
@@ -64,18 +65,6 @@ class BaseModelOutput:
         return iter(self.to_tuple())
 
 
-def _register(root: nn.Module, dotted: str, shape, init: float = 0.0):
-    """Create nested containers so that root.state_dict() yields the HF key `dotted`."""
-    parts = dotted.split(".")
-    mod = root
-    for name in parts[:-1]:
-        if not hasattr(mod, name):
-            mod.add_module(name, nn.Module())
-        mod = getattr(mod, name)
-    p = nn.Parameter(torch.full(tuple(shape), float(init)), requires_grad=False)
-    mod.register_parameter(parts[-1], p)
-
-
 def sinusoid_table(rows: int, dim: int = HIDDEN) -> torch.Tensor:
     """HF SpeechT5SinusoidalPositionalEmbedding.get_embedding (modeling_speecht5.py:305-321), same torch
     expression so that the table is bit-identical to the one HF builds at module init (weights, not hot path)."""
@@ -85,32 +74,6 @@ def sinusoid_table(rows: int, dim: int = HIDDEN) -> torch.Tensor:
     tab = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1).view(rows, -1)
     tab[PAD_TOKEN_ID, :] = 0
     return tab
-
-
-class _WeightHolder(nn.Module):
-    """A sub-module (prenet / wrapped_encoder) that only owns HF-named parameters."""
-
-    def __init__(self, owner_ref):
-        super().__init__()
-        self._owner_ref = owner_ref
-
-    def _mark_dirty(self):
-        owner = self._owner_ref()
-        if owner is not None:
-            owner._weights_dirty = True
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        sd = self._translate(dict(state_dict))
-        res = super().load_state_dict(sd, strict=strict, assign=assign)
-        self._mark_dirty()
-        return res
-
-    def _translate(self, sd):
-        return sd
-
-    def _apply(self, fn, recurse=True):
-        self._mark_dirty()
-        return super()._apply(fn, recurse)
 
 
 class SpeechT5SpeechEncoderPrenetMI355X(_WeightHolder):
@@ -254,16 +217,6 @@ class ForwardTicket:
                 slot.ticket = None
 
 
-class _Ref:
-    """weak-ish back reference that nn.Module does not register as a child."""
-
-    def __init__(self):
-        self.obj = None
-
-    def __call__(self):
-        return self.obj
-
-
 class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
     """Drop-in for ``SpeechT5ForSpeechToText(...).speecht5.encoder`` (HF modeling_speecht5.py:1325-1358)."""
 
@@ -368,7 +321,6 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
                                                  C.c_void_p(tab.data_ptr()), shape, 2), "sinusoid table")
             self._sin_rows = rows
         if self._weights_dirty and self._extra_weights:
-            from .decoder import MAX_TEXT_POSITIONS
             tab = sinusoid_table(MAX_TEXT_POSITIONS + PAD_TOKEN_ID + 1).contiguous()  # HF's decoder table, bit for bit (452 rows)
             _lib.check(self._lib.loco_set_weight(self._handle, b"decoder.prenet.embed_positions.weights", C.c_void_p(tab.data_ptr()),
                                                  (C.c_int64 * 2)(tab.shape[0], HIDDEN), 2), "decoder position table")
@@ -713,406 +665,3 @@ def bind_attention_outputs(lib, handle, layers: int, B: int, T: int, device) -> 
         ptrs = (C.c_void_p * layers)(*[t.data_ptr() for t in probs])
         _lib.check(lib.loco_set_attention_outputs(handle, ptrs, layers), "loco_set_attention_outputs")
     return probs
-
-
-def _decoder_layer_names(layer: int):
-    from .decoder import decoder_layer_keys
-    return decoder_layer_keys(layer)
-
-
-class _SpeechT5Core(nn.Module):
-    def __init__(self, encoder, decoder=None):
-        super().__init__()
-        self.encoder = encoder
-        if decoder is not None:
-            self.decoder = decoder
-
-
-class SpeechT5ForSpeechToTextMI355X(nn.Module):
-    """HF's SpeechT5ForSpeechToText as the reference uses it: ``.speecht5.encoder`` (the embedding path), and -- when decoder
-    weights are loaded (``decoder_layers > 0``) -- ``.speecht5.decoder`` / ``.text_decoder_postnet`` with ``forward(...,
-    decoder_input_ids=...)`` and greedy ``generate`` (decoder.py).  An encoder-only model is exactly what it was."""
-
-    def __init__(self, layers: int = LAYERS, precision: str = "f16x3", decoder_layers: int = 0, vocab_size: Optional[int] = None):
-        super().__init__()
-        encoder = SpeechT5EncoderWithSpeechPrenetMI355X(layers, precision)
-        decoder = None
-        if decoder_layers:
-            from . import decoder as dec
-            ref = _Ref()
-            ref.obj = encoder
-            decoder, postnet = dec.make_decoder_modules(ref, decoder_layers, vocab_size or dec.TEXT_VOCAB)
-            encoder._extra_weights = [("decoder.", decoder), ("text_decoder_postnet.", postnet)]
-            encoder._decoder_layers = decoder_layers
-            encoder._decoder_vocab = vocab_size or dec.TEXT_VOCAB
-            self._decoder_runtime = dec.DecoderRuntime(encoder)
-        self.speecht5 = _SpeechT5Core(encoder, decoder)
-        if decoder is not None:
-            self.text_decoder_postnet = postnet
-        self.eval()
-
-    @property
-    def has_decoder(self) -> bool:
-        return hasattr(self, "text_decoder_postnet")
-
-    def _require_decoder(self, what: str):
-        if not self.has_decoder:
-            why = getattr(self, "_no_decoder_reason", None)
-            raise RuntimeError(f"{what} needs the decoder, and this model was loaded without one: speecht5.decoder.* and "
-                               "text_decoder_postnet.lm_head.weight are missing (from_pretrained on a full speech-to-text checkpoint, or "
-                               "from_state_dicts(..., decoder_state_dict=, postnet_state_dict=))" + (f" -- {why}" if why else ""))
-
-    def _encode(self, input_values, attention_mask):
-        out = self.speecht5.encoder(input_values=input_values, attention_mask=attention_mask)
-        return out.last_hidden_state, self.speecht5.encoder.last_frames
-
-    def _encode_with_attentions(self, input_values, attention_mask):
-        out = self.speecht5.encoder(input_values=input_values, attention_mask=attention_mask, output_attentions=True)
-        return out.last_hidden_state, self.speecht5.encoder.last_frames, out.attentions
-
-    @torch.no_grad()
-    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                decoder_input_ids: Optional[torch.Tensor] = None, output_hidden_states: Optional[bool] = None,
-                labels: Optional[torch.Tensor] = None, output_attentions: Optional[bool] = None, **kwargs):
-        """``model(**audios, decoder_input_ids=ids)``: teacher-forced logits [B, S, vocab] and ``encoder_last_hidden_state``
-        (``output_hidden_states=True``: also the 7 ``decoder_hidden_states``).  Causal self-attention over the ids as given (no
-        decoder attention mask, as in the reference's calls); cross-attention over each clip's valid encoder frames.
-
-        ``labels`` [B, S] (token ids, -100 = not counted): also ``loss``, HF's mean cross-entropy over the counted labels, and
-        ``token_logprobs`` [B, S].  Without ``decoder_input_ids`` the decoder reads the labels shifted right (decoder.shift_tokens_right),
-        as HF does; with both, the given ids are read and the loss is taken against ``labels``.
-
-        ``output_attentions=True``: also ``decoder_attentions`` (6 x [B, 12, S, S], key j visible to query i iff j <= i),
-        ``cross_attentions`` (6 x [B, 12, S, T_enc], key j visible iff it is a valid frame of its clip) and ``encoder_attentions`` (the
-        encoder's own flag), fp32, masked entries exactly 0; formed by launches of their own (csrc/decoder_probs.hip), so logits
-        and hidden states are the same bits with and without the flag."""
-        for k in kwargs:
-            if k in ("decoder_attention_mask", "past_key_values", "encoder_outputs", "use_cache"):
-                raise NotImplementedError(f"forward({k}=...) is not implemented")
-            raise TypeError(f"forward() got an unexpected keyword argument '{k}'")
-        self._require_decoder("forward(labels=...)" if labels is not None and decoder_input_ids is None else "forward(decoder_input_ids=...)")
-        if decoder_input_ids is None and labels is None:
-            raise ValueError("You have to specify `decoder_input_ids` (for embeddings alone call model.speecht5.encoder)")
-        from . import decoder as dec
-        targets = None
-        if labels is not None:  # on the host, before any launch
-            host = dec.check_labels(labels, int(input_values.shape[0]), self.speecht5.encoder._decoder_vocab,
-                                    decoder_input_ids.shape if decoder_input_ids is not None else None)
-            if decoder_input_ids is None:
-                decoder_input_ids = dec.shift_tokens_right(host)
-            targets = host.to(torch.int32)
-        enc_attn = self_attn = cross_attn = None
-        if output_attentions:
-            enc_out, frames, enc_attn = self._encode_with_attentions(input_values, attention_mask)
-        else:
-            enc_out, frames = self._encode(input_values, attention_mask)
-        if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != enc_out.shape[0]:
-            raise ValueError(f"decoder_input_ids must be [batch, tokens] with batch {enc_out.shape[0]}, got {tuple(decoder_input_ids.shape)}")
-        ids = decoder_input_ids.to(device=enc_out.device, dtype=torch.int32).contiguous()
-        with torch.cuda.device(enc_out.device):
-            if output_attentions:
-                logits, hidden, self_attn, cross_attn = self._decoder_runtime.forward_attn(enc_out, frames, ids, bool(output_hidden_states))
-            else:
-                logits, hidden = self._decoder_runtime.forward(enc_out, frames, ids, bool(output_hidden_states))
-            loss = logprobs = None
-            if targets is not None:
-                logprobs, _, _, loss, _ = dec.score_logits(self.speecht5.encoder._lib, logits, targets.to(enc_out.device).contiguous(), *ids.shape)
-        return dec.Seq2SeqLMOutput(logits=logits, encoder_last_hidden_state=enc_out, decoder_hidden_states=hidden, loss=loss, token_logprobs=logprobs,
-                                   decoder_attentions=self_attn, cross_attentions=cross_attn, encoder_attentions=enc_attn)
-
-    @torch.no_grad()
-    def align(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
-              alignment_heads=None, return_attention: bool = False):
-        """Where in the audio each token of the transcripts ``labels`` [B, S] was spoken: a decoder.TokenAlignment with ``start_frames`` /
-        ``end_frames`` i32 [B, S] (encoder frames, end exclusive, -1 where the label is -100) and ``start_times`` / ``end_times`` in seconds
-        (frames x 320 / 16000, the conv stack's stride; its receptive-field offset is ignored).  -100 may only pad the end of a row.
-
-        One teacher-forced pass on the labels shifted right; the mean of the cross-attention probabilities over ``alignment_heads``
-        ((layer, head) pairs; None = all 72) is the soft alignment A [B, S, T_enc] (``return_attention=True`` hands it out), and a
-        monotone DTW over -A from (0, 0) to (n_b - 1, frames_b - 1) -- on the device, in double -- gives every token its frames."""
-        self._require_decoder("align()")
-        if labels is None:
-            raise ValueError("align() needs labels")
-        from . import decoder as dec
-        enc = self.speecht5.encoder
-        host = dec.check_labels(labels, int(input_values.shape[0]), enc._decoder_vocab)
-        counts = dec.alignment_counts(host)
-        heads, pairs = dec.check_alignment_heads(alignment_heads, enc._decoder_layers)
-        enc_out, frames = self._encode(input_values, attention_mask)
-        return self._align_encoded(enc_out, frames, host, counts, heads, pairs, return_attention)
-
-    def _align_encoded(self, enc_out, frames, labels_host, counts, heads, pairs, return_attention):
-        from . import decoder as dec
-        device = enc_out.device
-        ids = dec.shift_tokens_right(labels_host).to(device=device, dtype=torch.int32).contiguous()
-        with torch.cuda.device(device):
-            start, end, A = self._decoder_runtime.align(enc_out, frames, ids, counts.to(device).contiguous(), heads, pairs, return_attention)
-            seconds = lambda f: torch.where(f < 0, -1.0, f.to(torch.float32) * dec.FRAME_SECONDS).to(torch.float32)  # noqa: E731
-            return dec.TokenAlignment(start_frames=start, end_frames=end, start_times=seconds(start), end_times=seconds(end), attention=A)
-
-    @torch.no_grad()
-    def align_many(self, batches, labels, pack: int = 8, alignment_heads=None, return_attention: bool = False):
-        """Token timestamps of a corpus, built the way ``score_many`` is: ``batches`` is what ``generate_many`` takes, ``labels`` one
-        1-D LongTensor per utterance in input order (no -100 needed: each row is padded to its pack's longest).  The batches are
-        encoded ``pack`` at a time through ``forward_packed``; each pack's clips go through ONE ``align`` pass on the packed output and
-        its frame counts.  Returns a list, in input order, of decoder.TokenAlignment whose fields are the utterance's own 1-D slices
-        (``attention`` [len, T of its pack]).  An utterance's A is that of ``align`` on its own batch up to the fp32 summation order
-        of the packed encoder and of the decoder's products; its path is the DTW of that A."""
-        from . import decoder as dec
-        self._require_decoder("align_many()")
-        batches = [b for b in batches if b["input_values"].shape[0]]
-        labels = list(labels)
-        total = sum(int(b["input_values"].shape[0]) for b in batches)
-        if len(labels) != total:
-            raise ValueError(f"align_many: {len(labels)} label rows for {total} utterances")
-        if int(pack) < 1:
-            raise ValueError("pack must be >= 1")
-        enc = self.speecht5.encoder
-        heads, pairs = dec.check_alignment_heads(alignment_heads, enc._decoder_layers)
-        hosts = []
-        for u, lab in enumerate(labels):
-            if not torch.is_tensor(lab) or lab.dim() != 1:
-                raise ValueError(f"align_many: labels[{u}] must be a 1-D tensor of token ids")
-            hosts.append(dec.check_labels(lab[None], 1, enc._decoder_vocab)[0])
-            dec.alignment_counts(hosts[-1][None])
-        results, u0 = [], 0
-        for g0 in range(0, len(batches), int(pack)):
-            group = batches[g0:g0 + int(pack)]
-            ticket = enc.forward_packed_async(group)
-            ticket.result()
-            out, _ = ticket.packed_output()
-            n = int(out.shape[0])
-            rows = hosts[u0:u0 + n]
-            S = max(int(r.shape[0]) for r in rows)
-            lab = torch.full((n, S), dec.IGNORE_INDEX, dtype=torch.long)
-            for i, r in enumerate(rows):
-                lab[i, :r.shape[0]] = r
-            al = self._align_encoded(out, enc.last_frames, lab, dec.alignment_counts(lab), heads, pairs, return_attention)
-            for i, r in enumerate(rows):
-                k = int(r.shape[0])
-                results.append(dec.TokenAlignment(start_frames=al.start_frames[i, :k], end_frames=al.end_frames[i, :k], start_times=al.start_times[i, :k],
-                                                  end_times=al.end_times[i, :k], attention=al.attention[i, :k] if al.attention is not None else None))
-            u0 += n
-        return results
-
-    @torch.no_grad()
-    def score(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
-        """How likely the model finds the transcripts ``labels`` [B, S] (-100 = not counted) for these clips: decoder.TranscriptScores
-        with ``token_logprobs`` [B, S], ``sequence_logprob`` [B], ``tokens`` [B] and ``loss`` -- ``forward(labels=...)``'s pass, without
-        handing the logits out."""
-        self._require_decoder("score()")
-        if labels is None:
-            raise ValueError("score() needs labels")
-        from . import decoder as dec
-        host = dec.check_labels(labels, int(input_values.shape[0]), self.speecht5.encoder._decoder_vocab)
-        enc_out, frames = self._encode(input_values, attention_mask)
-        return self._score_encoded(enc_out, frames, host)
-
-    def _score_encoded(self, enc_out, frames, labels_host):
-        from . import decoder as dec
-        device = enc_out.device
-        ids = dec.shift_tokens_right(labels_host).to(device=device, dtype=torch.int32).contiguous()
-        with torch.cuda.device(device):
-            logits, _ = self._decoder_runtime.forward(enc_out, frames, ids)
-            lp, seq, cnt, loss, _ = dec.score_logits(self.speecht5.encoder._lib, logits, labels_host.to(device=device, dtype=torch.int32).contiguous(),
-                                                     *ids.shape)
-        return dec.TranscriptScores(token_logprobs=lp, sequence_logprob=seq, tokens=cnt, loss=loss)
-
-    @torch.no_grad()
-    def score_many(self, batches, labels, pack: int = 8):
-        """Scores of a corpus: ``batches`` is what ``generate_many`` takes, ``labels`` one 1-D LongTensor per utterance in input order.
-        The batches are encoded ``pack`` at a time through ``forward_packed``; each pack's clips go through ONE teacher-forced
-        decoder pass on the packed output and its frame counts, their labels padded with -100 to the pack's longest, and are scored
-        in one launch.  Returns a list, in input order, of (``token_logprobs`` 1-D of the utterance's own length, its sum 0-d), both
-        on the device.  An utterance's scores are those of ``score`` on its own batch up to the fp32 summation order of the packed
-        encoder and of the decoder's products, whatever ``pack`` is; the scoring kernel itself adds nothing to that (a row's
-        log-probability is a function of the row's logits alone)."""
-        from . import decoder as dec
-        self._require_decoder("score_many()")
-        batches = [b for b in batches if b["input_values"].shape[0]]
-        labels = list(labels)
-        total = sum(int(b["input_values"].shape[0]) for b in batches)
-        if len(labels) != total:
-            raise ValueError(f"score_many: {len(labels)} label rows for {total} utterances")
-        if int(pack) < 1:
-            raise ValueError("pack must be >= 1")
-        enc = self.speecht5.encoder
-        hosts = []
-        for u, lab in enumerate(labels):
-            if not torch.is_tensor(lab) or lab.dim() != 1:
-                raise ValueError(f"score_many: labels[{u}] must be a 1-D tensor of token ids")
-            hosts.append(dec.check_labels(lab[None], 1, enc._decoder_vocab)[0])
-        results, u0 = [], 0
-        for g0 in range(0, len(batches), int(pack)):
-            group = batches[g0:g0 + int(pack)]
-            ticket = enc.forward_packed_async(group)
-            ticket.result()
-            out, _ = ticket.packed_output()
-            n = int(out.shape[0])
-            rows = hosts[u0:u0 + n]
-            S = max(int(r.shape[0]) for r in rows)
-            lab = torch.full((n, S), dec.IGNORE_INDEX, dtype=torch.long)
-            for i, r in enumerate(rows):
-                lab[i, :r.shape[0]] = r
-            sc = self._score_encoded(out, enc.last_frames, lab)
-            for i, r in enumerate(rows):
-                results.append((sc.token_logprobs[i, :r.shape[0]], sc.sequence_logprob[i]))
-            u0 += n
-        return results
-
-    @torch.no_grad()
-    def generate(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
-                 max_new_tokens: Optional[int] = None, return_logits: bool = False, return_dict_in_generate: bool = False,
-                 output_scores: bool = False, **kwargs):
-        """Greedy search as HF's ``generate`` runs it for this model: LongTensor [B, S] starting with decoder_start_token_id 2, a
-        row that has emitted </s> (2) is filled with <pad> (1), S = the longest row or ``max_length`` (total, start token included;
-        ``max_new_tokens`` counts the tokens after it).  ``return_logits=True``: also the logits [S - 1, B, vocab] each step chose from.
-
-        ``return_dict_in_generate=True``: a decoder.GreedySearchOutput whose ``sequences`` are those ids; with ``output_scores=True``
-        it also carries ``scores`` (the S - 1 step logits [B, vocab]), ``token_logprobs`` [B, S - 1] and ``sequence_logprobs`` [B].
-        ``output_scores`` alone changes nothing, as in HF."""
-        from . import decoder as dec
-        dec.check_generate_kwargs(kwargs)
-        self._require_decoder("generate()")
-        n = dec.resolve_max_length(max_length, max_new_tokens)
-        enc_out, frames = self._encode(input_values, attention_mask)
-        with_scores = bool(return_dict_in_generate) and bool(output_scores)
-        with torch.cuda.device(enc_out.device):
-            rt = self._decoder_runtime
-            res = rt.generate(enc_out, frames, n, return_logits or with_scores)
-            if not return_dict_in_generate:
-                return res
-            ids, steps = res if (return_logits or with_scores) else (res, None)
-            out = dec.GreedySearchOutput(sequences=ids)
-            if with_scores:
-                B, S = ids.shape
-                # targets: the returned ids, -100 from each row's length on (the host holds ids' lengths already)
-                cols = torch.arange(1, S)[None, :]
-                targets = torch.where(cols < rt.last_lengths[:, None].long(), ids[:, 1:].cpu(), torch.tensor(dec.IGNORE_INDEX)).to(torch.int32)
-                by_row = steps.permute(1, 0, 2).contiguous()  # [B, S - 1, V]: a row's steps form one sequence
-                lp, seq, _, _, _ = dec.score_logits(self.speecht5.encoder._lib, by_row, targets.to(enc_out.device).contiguous(), B, S - 1)
-                out.scores, out.token_logprobs, out.sequence_logprobs = tuple(steps[t] for t in range(S - 1)), lp, seq
-            return (out, steps) if return_logits else out
-
-    @torch.no_grad()
-    def generate_many(self, batches, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, return_logits: bool = False,
-                      pack: int = 8, return_scores: bool = False, **kwargs):
-        """Greedy transcripts of a corpus: ``batches`` is what ``pack_batches`` takes (reference batches of ``input_values`` /
-        ``attention_mask``), ``max_length`` an int or one int per utterance (total length, start token included).  The batches are
-        encoded ``pack`` at a time through ``forward_packed`` -- every clip keeps its own batch's padded length -- and decoded in a
-        pool of ``slots`` decoder rows in which a row that ends hands its slot to the next utterance (decoder.DecoderPool).
-
-        Returns a list, in input order, of 1-D LongTensors (host): <s> ... up to and including </s>, or the utterance's cap of tokens
-        for a row that never ended -- row u of ``generate(**batch_k, max_length=cap_u)`` without its trailing <pad>, up to the fp32
-        summation order of the packed encoder and of the attention's key splits.  An utterance's result does not depend on the
-        utterances decoded beside it.  ``return_logits=True``: (ids, logits) with one [len - 1, vocab] device tensor per utterance.
-        ``return_scores=True``: (ids, scores) with one [len - 1] device tensor per utterance, the log-probability of every generated
-        token (both: (ids, logits, scores))."""
-        from . import decoder as dec
-        dec.check_generate_kwargs(kwargs)
-        self._require_decoder("generate_many()")
-        batches = list(batches)
-        sizes = [int(b["input_values"].shape[0]) for b in batches]
-        total = sum(sizes)
-        caps = dec.resolve_caps(total, max_length, max_new_tokens)
-        if int(pack) < 1:
-            raise ValueError("pack must be >= 1")
-        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
-        if not 1 <= int(slots) <= most:
-            raise ValueError(f"generate_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
-        extras = int(bool(return_logits)) + int(bool(return_scores))
-        if total == 0:
-            return ([],) * (1 + extras) if extras else []
-        enc = self.speecht5.encoder
-        lib = enc._lib
-        device = enc._device()
-        T_cap = max(int(lib.loco_output_frames(int(b["input_values"].shape[1]))) for b in batches if b["input_values"].shape[0])
-        if T_cap < 1:
-            raise ValueError("input shorter than one encoder frame (400 samples)")
-        pool = None
-        results, key, nxt = {}, 0, 0
-        batches = [b for b in batches if b["input_values"].shape[0]]
-        with torch.cuda.device(device):
-            while nxt < len(batches) or (pool is not None and pool.busy):
-                if nxt < len(batches) and (pool is None or len(pool.waiting) < int(slots)):
-                    ticket = enc.forward_packed_async(batches[nxt:nxt + int(pack)])
-                    nxt += int(pack)
-                    ticket.result()
-                    out, spans = ticket.packed_output()
-                    frames = enc.last_frames
-                    if pool is None:  # after the first forward: the handle exists and carries the decoder's weights
-                        pool = dec.DecoderPool(enc, min(int(slots), total), T_cap, max(caps), device,
-                                               return_logits=return_logits, return_scores=return_scores)
-                    items = []
-                    for b0, nb, t in spans:
-                        for c in range(b0, b0 + nb):
-                            items.append(dec.PoolItem(key=key, enc_out=out, frames=frames, clip=c, rows=t, cap=caps[key]))
-                            key += 1
-                    pool.submit(items)
-                    continue
-                for k, *rest in pool.round():
-                    results[k] = rest
-        out = [[results[k][0] for k in range(total)]]
-        if return_logits:
-            out.append([results[k][1] for k in range(total)])
-        if return_scores:
-            out.append([results[k][2] for k in range(total)])
-        return tuple(out) if extras else out[0]
-
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):
-        """``SpeechT5ForSpeechToText.from_pretrained(...)`` of the fine-tuned script (…finetuned…py:95) for a checkpoint ON
-        DISK: a directory holding ``model.safetensors`` / ``pytorch_model.bin`` (or their sharded index), one such file, or a hub
-        name that is already in the local HuggingFace cache -- nothing is ever downloaded.  Keeps ``speecht5.encoder.prenet.*``
-        and ``speecht5.encoder.wrapped_encoder.*`` (either spelling of the weight-normed positional conv) and, when the file has
-        them, ``speecht5.decoder.*`` and ``text_decoder_postnet.*`` (the tied embedding / lm_head pair may be present once); takes
-        the layer counts from the keys, and fails BY NAME on anything the encoder needs and the file lacks
-        (load_state_dict(strict=True)).  The decoder is kept only when the file holds a COMPLETE one (checkpoint_map.decoder_problem):
-        a file with the encoder and stray or partial decoder tensors gives the encoder-only model it always gave, and ``generate`` /
-        ``decoder_input_ids`` then raise with the name of the first decoder tensor that is missing or misshapen."""
-        import re
-        from . import checkpoint_map
-        checkpoint_map.check_hf_config(str(pretrained_model_name_or_path))
-        pre, enc = checkpoint_map.load_hf_checkpoint(str(pretrained_model_name_or_path))
-        ids = [int(m_.group(1)) for m_ in (re.match(r"layers\.(\d+)\.", k) for k in enc) if m_]
-        if not ids:
-            raise KeyError(f"{pretrained_model_name_or_path}: no speecht5.encoder.wrapped_encoder.layers.N.* tensors")
-        dec_sd, post_sd = checkpoint_map.load_hf_decoder(str(pretrained_model_name_or_path))
-        problem = checkpoint_map.decoder_problem(dec_sd, post_sd)
-        if problem is not None:  # no (complete) decoder in the file: the encoder-only model this call has always returned
-            model = cls.from_state_dicts(pre, enc, layers=max(ids) + 1, precision=precision)
-            model._no_decoder_reason = f"{pretrained_model_name_or_path}: {problem}"
-            return model
-        known = {"prenet.embed_tokens.weight"} | {"wrapped_decoder." + n for l in range(64) for n, _, _ in _decoder_layer_names(l)}
-        dec_sd = {k: v for k, v in dec_sd.items() if k in known}  # e.g. a stray wrapped_decoder.layer_norm of another architecture
-        return cls.from_state_dicts(pre, enc, layers=max(ids) + 1, precision=precision, decoder_state_dict=dec_sd,
-                                    postnet_state_dict={k: v for k, v in post_sd.items() if k == "lm_head.weight"})
-
-    @classmethod
-    def from_state_dicts(cls, prenet_state_dict, encoder_state_dict, layers: int = LAYERS, precision: str = "f16x3",
-                         decoder_state_dict=None, postnet_state_dict=None):
-        """What the base script does after from_pretrained (…base…py:98-100), minus the hub download.  With ``decoder_state_dict``
-        (keys ``prenet.embed_tokens.weight``, ``wrapped_decoder.layers.N.*``) and / or ``postnet_state_dict`` (``lm_head.weight``)
-        the model also decodes; of the tied pair embed_tokens / lm_head one may be absent (it is taken from the other)."""
-        import re
-        dec_layers, vocab = 0, None
-        if decoder_state_dict is not None or postnet_state_dict is not None:
-            decoder_state_dict = dict(decoder_state_dict or {})
-            postnet_state_dict = dict(postnet_state_dict or {})
-            emb, head = decoder_state_dict.get("prenet.embed_tokens.weight"), postnet_state_dict.get("lm_head.weight")
-            if emb is None and head is None:
-                raise KeyError("decoder weights without prenet.embed_tokens.weight or lm_head.weight (the tied pair: one of them is needed)")
-            decoder_state_dict.setdefault("prenet.embed_tokens.weight", head)
-            postnet_state_dict.setdefault("lm_head.weight", emb)
-            ids = [int(m_.group(1)) for m_ in (re.match(r"wrapped_decoder\.layers\.(\d+)\.", k) for k in decoder_state_dict) if m_]
-            if not ids:
-                raise KeyError("decoder_state_dict: no wrapped_decoder.layers.N.* tensors")
-            dec_layers, vocab = max(ids) + 1, int(decoder_state_dict["prenet.embed_tokens.weight"].shape[0])
-        model = cls(layers, precision, decoder_layers=dec_layers, vocab_size=vocab)
-        model.speecht5.encoder.wrapped_encoder.load_state_dict(encoder_state_dict)
-        model.speecht5.encoder.prenet.load_state_dict(prenet_state_dict)
-        if dec_layers:
-            as_t = lambda d: {k: (v if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in d.items()}  # noqa: E731
-            model.speecht5.decoder.load_state_dict(as_t(decoder_state_dict))
-            model.text_decoder_postnet.load_state_dict(as_t(postnet_state_dict))
-        return model

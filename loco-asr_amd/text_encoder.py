@@ -19,7 +19,9 @@ from torch import nn
 
 from . import _lib
 from .encoder import (HIDDEN, LAYERS, BaseModelOutput, SpeechT5EncoderMI355X, SpeechT5EncoderWithSpeechPrenetMI355X,
-                      _Ref, _SpeechT5Core, _WeightHolder, bind_attention_outputs)
+                      bind_attention_outputs)
+from .holders import _Ref, _WeightHolder
+from .speech_to_text import _SpeechT5Core
 
 VOCAB_SIZE = 81           # SpeechT5Config.vocab_size
 MAX_TEXT_POSITIONS = 450  # SpeechT5Config.max_text_positions

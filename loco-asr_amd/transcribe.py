@@ -24,7 +24,7 @@ import torch
 
 from . import synth
 from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID
-from .encoder import SpeechT5ForSpeechToTextMI355X
+from .speech_to_text import SpeechT5ForSpeechToTextMI355X
 
 
 def load_tokenizer(path):

@@ -2,7 +2,8 @@
 """Bit-for-bit comparison of the existing decoder entry points between two builds of this repository (a parent checkout and this
 tree, each with its own libloco_asr.so): loco_decoder_generate (ids and step logits) and loco_decoder_begin + loco_decoder_step on
 GENERATE["b7_len40_30s"], and loco_decoder_forward (logits and the 7 hidden states) on TEACHER_FORCED[3] of
-tests/decoder_sweep_cases.py, 12 + 6 layers.  One process per tree, since a process loads one library:
+tests/decoder_sweep_cases.py, 12 + 6 layers; then the model's Python surface (forward with labels and attentions, score, align, score_many,
+align_many, generate_many, generate with scores) on the 2 + 2 layer model of the pool tests.  One process per tree, since a process loads one library:
 
     python tools/decoder_parent_compare.py dump PARENT_TREE out/parent
     python tools/decoder_parent_compare.py dump . out/new
@@ -56,12 +57,65 @@ def dump(root, outdir):
                                                 torch.from_numpy(tids).to(torch.int32).cuda(), True)
     torch.cuda.synchronize()
     save("forward_logits", logits), save("forward_hidden", torch.stack(hs))
+    del model
+    dump_small(la, save)
     print("dumped", sorted(os.listdir(outdir)), "from", root)
+
+
+def dump_small(la, save):
+    """The model's Python surface on the 2 + 2 layer model and six clips of tests/test_gpu_corpus_walk.py: forward with every
+    output, score, align, their corpus forms, generate_many and generate with scores."""
+    import torch
+    import decoder_pool_cases as pc
+    synth = la.synth
+    t = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
+    pre, enc = synth.split_state_dict(synth.encoder_state_dict(0, pc.ENC_LAYERS))
+    dec, post = synth.split_decoder_state_dict(synth.decoder_state_dict(pc.DEC_SEED, layers=pc.DEC_LAYERS))
+    model = la.SpeechT5ForSpeechToTextMI355X.from_state_dicts(t(pre), t(enc), layers=pc.ENC_LAYERS, decoder_state_dict=t(dec),
+                                                              postnet_state_dict=t(post)).to("cuda")
+    oc = pc.oracle_clips(synth)
+    batches = [dict(input_values=torch.from_numpy(x).cuda(), attention_mask=torch.from_numpy(m).cuda()) for x, m in pc.pairs(synth, oc[0:4] + oc[10:12])]
+    g = torch.Generator().manual_seed(3)
+    labels = []
+    for n in (5, 1, 9, 12, 2, 7):
+        row = torch.randint(4, 81, (n,), generator=g)
+        row[-1] = 2
+        labels.append(row)
+    b, lab = batches[1], torch.full((2, 12), -100)
+    lab[0, :9], lab[1] = labels[2], labels[3]
+    out = model(**b, labels=lab, output_attentions=True, output_hidden_states=True)
+    for name in ("logits", "encoder_last_hidden_state", "loss", "token_logprobs"):
+        save("small_forward_" + name, getattr(out, name))
+    for name in ("decoder_hidden_states", "decoder_attentions", "cross_attentions", "encoder_attentions"):
+        save("small_forward_" + name, torch.stack(getattr(out, name)))
+    sc = model.score(**b, labels=lab)
+    for name in ("token_logprobs", "sequence_logprob", "tokens", "loss"):
+        save("small_score_" + name, getattr(sc, name))
+    al = model.align(**b, labels=lab, return_attention=True)
+    for name in ("start_frames", "end_frames", "start_times", "end_times", "attention"):
+        save("small_align_" + name, getattr(al, name))
+    for u, (lp, total) in enumerate(model.score_many(batches, labels, pack=2)):
+        save(f"small_score_many_{u}_token_logprobs", lp), save(f"small_score_many_{u}_sum", total)
+    for u, al in enumerate(model.align_many(batches, labels, pack=2, return_attention=True)):
+        for name in ("start_frames", "end_frames", "start_times", "end_times", "attention"):
+            save(f"small_align_many_{u}_{name}", getattr(al, name))
+    ids, logits, scores = model.generate_many(batches, max_length=[3, 9, 2, 17, 5, 40], slots=3, return_logits=True, return_scores=True)
+    for u in range(6):
+        save(f"small_generate_many_{u}_ids", ids[u]), save(f"small_generate_many_{u}_logits", logits[u]), save(f"small_generate_many_{u}_scores", scores[u])
+    gen = model.generate(**b, return_dict_in_generate=True, output_scores=True, max_length=12)
+    save("small_generate_sequences", gen.sequences), save("small_generate_scores", torch.stack(gen.scores))
+    save("small_generate_token_logprobs", gen.token_logprobs), save("small_generate_sequence_logprobs", gen.sequence_logprobs)
+    save("small_generate_last_lengths", model._decoder_runtime.last_lengths)
+    torch.cuda.synchronize()
 
 
 def compare(a, b):
     ok = True
-    for f in sorted(os.listdir(a)):
+    for f in sorted(set(os.listdir(a)) | set(os.listdir(b))):
+        if not (os.path.exists(os.path.join(a, f)) and os.path.exists(os.path.join(b, f))):
+            print(f, "MISSING on one side")
+            ok = False
+            continue
         x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
         same = x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
         print(f, x.shape, "bit-identical" if same else "DIFFERENT")
