@@ -1091,7 +1091,11 @@ hipError_t launch_gemm_split(const GemmSplitArgs& a, hipStream_t s) {
 // x -> (hi, lo) fp16 planes, n % 4 == 0
 __global__ void split_f16_kernel(const float* __restrict__ x, _Float16* __restrict__ hi, _Float16* __restrict__ lo, long n4, float scale) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i] * scale;
+        f32x4 v = reinterpret_cast<const f32x4*>(x)[i] * scale;
+        // hi and lo must derive from the SAME fp32 value (split_f16_2pairs, loco_kernels.h): left to itself hipcc folds the multiply into
+        // v_fma_mix*_f16 and measures lo from fp16(scale x + 0), not from the hi it stores -- for x = -0 that is +0 and lo came out as -0
+        // where (_Float16)(x - (float)hi) is +0; for a scale that is no power of two hi itself could differ by an ulp.  Pinned, as there.
+        asm volatile("" : "+v"(v));
         h4 a, b;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
