@@ -53,6 +53,7 @@ __global__ __launch_bounds__(256) void conv0_moments_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < kConv0Moments; ++i) {
         double s = acc[i];
+        // wave_sum's butterfly, open-coded: the helper changes this kernel's code (profiles/decoder_rules_refactor_isa.txt)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if (lane == 0) red[wave][i] = s;

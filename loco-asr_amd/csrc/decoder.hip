@@ -7,7 +7,9 @@
 //   dec_select_kernel      argmax of the step's logits + finished / pad bookkeeping + append to the token buffer
 // One decode step is weight- and KV-bandwidth-bound (226 MB of fp32 weights for 2 * 226 M * B FLOP): nothing here uses the matrix
 // cores.  No kernel allocates, synchronises or depends on the host; all are capturable.
-#include "loco_kernels.h"
+// What these kernels share with the slot pool, the scores and the probabilities (argmax, score product, softmax tile, position
+// rule) is decoder_common.h's; the wave reductions are loco_kernels.h's.
+#include "decoder_common.h"
 
 namespace loco {
 
@@ -17,12 +19,6 @@ constexpr int kSkinnyThreads = 256;
 constexpr int kSkinnyMT = 4;   // activation rows held in registers per pass
 constexpr int kSkinnyNC = 2;   // weight rows (output columns) per wave
 constexpr int kSkinnyKC = 256; // k elements per wave-wide 16-byte load
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // fixed butterfly: the same order in every run
-    return v;
-}
 
 // A wave owns kSkinnyNC weight rows and every ks-th 256-element chunk of K: lane l holds elements 4l .. 4l+3 of a chunk (one
 // coalesced 1 KiB load per weight row and chunk), multiplies them into kSkinnyMT activation rows (A is at most 64 x 3072 floats: it
@@ -133,17 +129,12 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnArgs a) {
     if (unit >= units) return;  // whole waves leave: no barrier below
     const int sp = (int)(unit % a.nsplit);
     const long row = unit / a.nsplit;
-    const int i = (int)(row % a.Sq);
-    const int h = (int)((row / a.Sq) % kHeads);
-    const int b = (int)(row / ((long)a.Sq * kHeads));
-    int nvis = a.kcount ? min(a.kcount[b], a.Tk) : a.Tk;
-    if (a.causal) nvis = min(nvis, i + a.causal_offset + 1);
+    const auto [i, h, b] = dec_attn_row(row, a.Sq);
+    const int nvis = dec_visible_keys(a.kcount, b, a.Tk, a.causal, i, a.causal_offset);
     const int j_begin = sp * a.keys_per_split, j_end = min(nvis, j_begin + a.keys_per_split);
 
     const float* qp = a.q + (long)b * a.sq + (long)i * a.ldq + h * kHeadDim;
-    f32x4 q[kHeadDim / 4];
-#pragma unroll
-    for (int d = 0; d < kHeadDim / 4; ++d) q[d] = *reinterpret_cast<const f32x4*>(qp + 4 * d) * a.scale;
+    LOCO_DEC_LOAD_Q(q, qp, a.scale);
     const float* kb = a.k + (long)b * a.sk + h * kHeadDim;
     const float* vb = a.v + (long)b * a.sv + h * kHeadDim;
 
@@ -153,24 +144,9 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnArgs a) {
         float sc = -INFINITY;
         if (j < j_end) {
             const float* kr = kb + (long)j * a.ldk;
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved partial sums of 16 products
-#pragma unroll
-            for (int d = 0; d < kHeadDim / 4; ++d) {
-                const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + 4 * d);
-                acc[0] = fmaf(q[d].x, kv.x, acc[0]);
-                acc[1] = fmaf(q[d].y, kv.y, acc[1]);
-                acc[2] = fmaf(q[d].z, kv.z, acc[2]);
-                acc[3] = fmaf(q[d].w, kv.w, acc[3]);
-            }
-            sc = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            LOCO_DEC_QK(sc, q, kr);
         }
-        float tm = sc;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tm = fmaxf(tm, __shfl_xor(tm, off, 64));
-        const float m_new = fmaxf(m_run, tm);  // finite: lane 0 of every tile holds a visible key
-        const float p = j < j_end ? expf(sc - m_new) : 0.f;
-        const float corr = expf(m_run - m_new);  // exp(-inf) = 0 on the first tile
-        s_run = s_run * corr + wave_sum(p);
+        LOCO_DEC_SOFTMAX_TILE(sc, j < j_end, m_run, s_run, m_new, p, corr);
         o *= corr;
         const int nj = min(64, j_end - j0);
         for (int jj = 0; jj < nj; ++jj) {
@@ -195,9 +171,7 @@ __global__ __launch_bounds__(256) void dec_attention_combine(DecAttnArgs a) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long)a.B * kHeads * a.Sq) return;
-    const int i = (int)(row % a.Sq);
-    const int h = (int)((row / a.Sq) % kHeads);
-    const int b = (int)(row / ((long)a.Sq * kHeads));
+    const auto [i, h, b] = dec_attn_row(row, a.Sq);
     const float* pr = a.part + row * a.nsplit * 66;
     float m = -INFINITY;
     for (int s = 0; s < a.nsplit; ++s) m = fmaxf(m, pr[s * 66]);
@@ -222,17 +196,13 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int32_t* __restric
     const int s = blockIdx.x, b = blockIdx.y;
     const int32_t* row = ids + (long)b * ld_ids;
     int cnt = 0;
-    for (int t = threadIdx.x; t <= s; t += 256) cnt += row[t] != 1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    for (int t = threadIdx.x; t <= s; t += 256) cnt += row[t] != kDecPadToken;
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
     __syncthreads();
     cnt = part[0] + part[1] + part[2] + part[3];
-    const int id = min(max(row[s], 0), vocab - 1);
-    const int pos = min(row[s] != 1 ? cnt + 1 : 1, table_rows - 1);
+    const int pos = dec_embed_row(row[s], row[s] != kDecPadToken, cnt, embed, vocab, table, table_rows, x + ((long)b * S + s) * kHidden);
     if (positions && threadIdx.x == 0) positions[(long)b * S + s] = pos;
-    float* dst = x + ((long)b * S + s) * kHidden;
-    for (int c = threadIdx.x; c < kHidden; c += 256) dst[c] = embed[(long)id * kHidden + c] + table[(long)pos * kHidden + c];
 }
 
 // The step's form: token t of every row from the token buffer; the running non-pad count is kept per position (nonpad[b, t] =
@@ -242,16 +212,16 @@ __global__ __launch_bounds__(256) void dec_embed_step_kernel(const int32_t* __re
                                                              int table_rows, int32_t* __restrict__ nonpad, float* __restrict__ x) {
     const int b = blockIdx.x;
     const int raw = tokens[(long)b * S_max + t];
-    const int cnt = (t == 0 ? 0 : nonpad[(long)b * S_max + t - 1]) + (raw != 1);
+    const bool token = raw != kDecPadToken;
+    const int cnt = (t == 0 ? 0 : nonpad[(long)b * S_max + t - 1]) + token;
     if (threadIdx.x == 0) nonpad[(long)b * S_max + t] = cnt;
-    const int id = min(max(raw, 0), vocab - 1);
-    const int pos = min(raw != 1 ? cnt + 1 : 1, table_rows - 1);
-    float* dst = x + (long)b * kHidden;
-    for (int c = threadIdx.x; c < kHidden; c += 256) dst[c] = embed[(long)id * kHidden + c] + table[(long)pos * kHidden + c];
+    dec_embed_row(raw, token, cnt, embed, vocab, table, table_rows, x + (long)b * kHidden);
 }
 
 // ---- token selection -------------------------------------------------------------------------------------------------------
-// One workgroup, thread b = row b (B <= 64 = one wave).  argmax with the lowest index winning ties (torch.argmax); a finished row
+// One workgroup, thread b = row b (B <= 64 = one wave).  argmax by decoder_common.h's rule in an ascending serial scan: the candidate's
+// index is always above the incumbent's, so argmax_better(v, n, bv, best) reduces to v > bv || (v != v && bv == bv): the scan spells
+// that out (the compiler does not reduce the call).  A finished row
 // takes <pad>; a row that emits <eos> is finished from the next step on (finished[b, p] = row b is finished once position p is
 // written: a step reads position t and writes t + 1, so it can be replayed); state[0] = rows still unfinished after this step.
 __global__ __launch_bounds__(64) void dec_select_kernel(const float* __restrict__ logits, int vocab, int B, int32_t* __restrict__ tokens,
@@ -265,7 +235,7 @@ __global__ __launch_bounds__(64) void dec_select_kernel(const float* __restrict_
         float bv = l[0];
         for (int n = 1; n < vocab; ++n) {
             const float v = l[n];
-            if (v > bv || (v != v && bv == bv)) {  // the first NaN wins, as in torch
+            if (v > bv || (v != v && bv == bv)) {  // argmax_better(v, n, bv, best) with n > best
                 bv = v;
                 best = n;
             }

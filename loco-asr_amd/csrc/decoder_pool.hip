@@ -7,8 +7,8 @@
 //                       slots that are not open
 //   pool_select_kernel  argmax of the open slots, append, finish on </s> or at the cap, advance
 // A slot that is not open reads and writes nothing of its own in a step: its row is zeros in, key counts 0, no cache row, no token.
-// No kernel allocates, synchronises or depends on the host.
-#include "loco_kernels.h"
+// No kernel allocates, synchronises or depends on the host.  A token's position and the argmax are decoder_common.h's rules, as in generate.
+#include "decoder_common.h"
 
 namespace loco {
 
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64) void pool_init_kernel(PoolState p) {
         p.self_count[r] = 0;
         p.cross_count[r] = 0;
         p.kv_row[r] = -1;
-        p.cur[r] = 1;
+        p.cur[r] = kDecPadToken;
         p.cnt[r] = 0;
     }
     if (r < 4) p.poll[r] = 0;
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(64) void pool_admit_kernel(PoolState p, PoolAdmit a
         const int r = a.slot[i];
         p.tokens[(long)r * p.S_max] = start;
         p.cur[r] = start;
-        p.cnt[r] = start != 1;
+        p.cnt[r] = start != kDecPadToken;
         p.pos[r] = 0;
         p.cap[r] = a.cap[i];
         p.frames[r] = min(max(frames ? frames[i] : a.rows[i], 0), a.rows[i]);  // never beyond the rows that were projected
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(64) void pool_admit_kernel(PoolState p, PoolAdmit a
 
 // cur[r] is the token slot r consumes (token pos[r] of its buffer) and cnt[r] the non-pad tokens of its utterance up to and including
 // it: the select kernel keeps both, so this kernel's loads of the slot's state are independent of one another and only the embedding
-// rows wait for them (the chain dec_embed_step_kernel has).  The position rule is dec_embed_kernel's.
+// rows wait for them (the chain dec_embed_step_kernel has).
 __global__ __launch_bounds__(256) void pool_embed_kernel(PoolState p, const float* __restrict__ embed, int vocab, const float* __restrict__ table,
                                                          int table_rows, float* __restrict__ x, int max_pos, int max_frames) {
     const int r = blockIdx.x;
@@ -74,16 +74,7 @@ __global__ __launch_bounds__(256) void pool_embed_kernel(PoolState p, const floa
         p.cross_count[r] = min(frames, max_frames);
         p.kv_row[r] = t;
     }
-    const int id = min(max(raw, 0), vocab - 1);
-    const int pos = min(raw != 1 ? cnt + 1 : 1, table_rows - 1);
-    for (int c = threadIdx.x; c < kHidden; c += 256) dst[c] = embed[(long)id * kHidden + c] + table[(long)pos * kHidden + c];
-}
-
-// a beats b in the argmax: the first NaN wins, as in torch; otherwise the larger value, the lower index on a tie
-__device__ __forceinline__ bool pool_better(float av, int ai, float bv, int bi) {
-    const bool an = av != av, bn = bv != bv;
-    if (an || bn) return an && (!bn || ai < bi);
-    return av > bv || (av == bv && ai < bi);
+    dec_embed_row(raw, raw != kDecPadToken, cnt, embed, vocab, table, table_rows, dst);
 }
 
 // One workgroup of 16 waves, a wave per slot (slots r, r + 16, ...): the lanes share the row's logits and meet in a butterfly, so the
@@ -99,14 +90,9 @@ __global__ __launch_bounds__(1024) void pool_select_kernel(PoolState p, const fl
         float bv = l[bi];
         for (int n = lane + 64; n < vocab; n += 64) {
             const float v = l[n];
-            if (pool_better(v, n, bv, bi)) bv = v, bi = n;
+            if (argmax_better(v, n, bv, bi)) bv = v, bi = n;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (pool_better(ov, oi, bv, bi)) bv = ov, bi = oi;
-        }
+        wave_argmax(bv, bi);
         if (t >= 0) {
             const bool done = bi == eos || t + 2 >= cap || t + 2 >= p.S_max;
             if (lane == 0) {
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(1024) void pool_select_kernel(PoolState p, const fl
                 } else {
                     p.pos[r] = t + 1;
                     p.cur[r] = bi;
-                    p.cnt[r] = cnt + (bi != 1);
+                    p.cnt[r] = cnt + (bi != kDecPadToken);
                 }
             }
             open += !done;

@@ -3,12 +3,13 @@
 //   dec_attention_probs_kernel  P[b,h,i,:] = softmax over the visible keys of scale q.k, exact fp32, masked entries exactly 0
 //   dec_attn_mean_kernel        A[b,s,t] (+)= sum over the selected heads of one layer's P; the last layer multiplies by 1 / pairs
 //   dtw_align_kernel            monotone DTW over -A in double, one workgroup per clip, anti-diagonals; back-pointers in global memory
-// dec_attention_kernel (decoder.hip) never forms P: it is an online-softmax kernel.  The schedule here is the plain one: one wave per P
+// dec_attention_kernel (decoder.hip) never forms P: it is an online-softmax kernel; what the two must agree on (row decode, visible
+// keys, scaled q, the product q . k_j, the tile's max / sum / rescale) is decoder_common.h's.  The schedule here is the plain one: one wave per P
 // row, two passes over the keys, every store instruction one contiguous 256-byte piece of the row.  Each P entry costs its 256-byte key
 // row twice (from L2: the key rows of a head are shared by its S queries), so the kernel is bound by those reads, not by its stores:
 // measured at ~90-100 x the store-byte floor of P (profiles/decoder_attn_cost.json).
 // No kernel allocates, synchronises with the host or uses atomics.
-#include "loco_kernels.h"
+#include "decoder_common.h"
 
 namespace loco {
 
@@ -24,18 +25,11 @@ struct DecProbsArgs {
     float scale;
 };
 
-// q . k_j for this lane's key: dec_attention_kernel's product, term for term (four interleaved partial sums of 16 products)
+// q . k_j as a function: this kernel forms it in two places
 __device__ __forceinline__ float probs_score(const f32x4 (&q)[kHeadDim / 4], const float* kr) {
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int d = 0; d < kHeadDim / 4; ++d) {
-        const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + 4 * d);
-        acc[0] = fmaf(q[d].x, kv.x, acc[0]);
-        acc[1] = fmaf(q[d].y, kv.y, acc[1]);
-        acc[2] = fmaf(q[d].z, kv.z, acc[2]);
-        acc[3] = fmaf(q[d].w, kv.w, acc[3]);
-    }
-    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    float sc;
+    LOCO_DEC_QK(sc, q, kr);
+    return sc;
 }
 
 // One wave per (clip, head, query).  Pass 1: running maximum and sum over the visible keys in tiles of 64 (lane j of a tile owns key
@@ -45,30 +39,18 @@ __global__ __launch_bounds__(256) void dec_attention_probs_kernel(DecProbsArgs a
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long)a.B * kHeads * a.Sq) return;  // whole waves leave: no barrier below
-    const int i = (int)(row % a.Sq);
-    const int h = (int)((row / a.Sq) % kHeads);
-    const int b = (int)(row / ((long)a.Sq * kHeads));
-    int nvis = a.kcount ? max(0, min(a.kcount[b], a.Tk)) : a.Tk;
-    if (a.causal) nvis = min(nvis, i + 1);
+    const auto [i, h, b] = dec_attn_row(row, a.Sq);
+    const int nvis = dec_visible_keys(a.kcount, b, a.Tk, a.causal, i, 0);
 
     const float* qp = a.q + (long)b * a.sq + (long)i * a.ldq + h * kHeadDim;
-    f32x4 q[kHeadDim / 4];
-#pragma unroll
-    for (int d = 0; d < kHeadDim / 4; ++d) q[d] = *reinterpret_cast<const f32x4*>(qp + 4 * d) * a.scale;
+    LOCO_DEC_LOAD_Q(q, qp, a.scale);
     const float* kb = a.k + (long)b * a.sk + h * kHeadDim;
 
     float m_run = -INFINITY, s_run = 0.f;
     for (int j0 = 0; j0 < nvis; j0 += 64) {
         const int j = j0 + lane;
         const float sc = j < nvis ? probs_score(q, kb + (long)j * a.ldk) : -INFINITY;
-        float tm = sc;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tm = fmaxf(tm, __shfl_xor(tm, off, 64));
-        const float m_new = fmaxf(m_run, tm);  // lane 0 of every tile holds a visible key
-        float p = j < nvis ? expf(sc - m_new) : 0.f;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) p += __shfl_xor(p, off, 64);  // fixed butterfly
-        s_run = s_run * expf(m_run - m_new) + p;  // exp(-inf) = 0 on the first tile
+        LOCO_DEC_SOFTMAX_TILE(sc, j < nvis, m_run, s_run, m_new, p, corr);
         m_run = m_new;
     }
     float* pr = a.P + row * (long)a.Tk;  // 64-bit: B * 12 * Sq * Tk passes 2^31

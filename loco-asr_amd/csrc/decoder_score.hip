@@ -3,23 +3,16 @@
 //   token_logprob_kernel  one wave per row of logits: log_softmax(row)[target], the target given or the row's argmax
 //   score_reduce_kernel   per sequence the sum and the count of its valid positions; loss = -(sum of sums) / (sum of counts)
 // A row's log-probability is a pure function of its V numbers, bit for bit: the lanes walk the row lane-strided in a fixed order and
-// meet in xor butterflies whose two operands every lane pair adds (or compares) symmetrically, so all 64 lanes hold the same value
-// and nothing depends on the row's place, on M or on the other rows.  The reduction's order depends on (B, S) only.  No atomics;
-// neither kernel allocates, synchronises or depends on the host.
+// meet in xor butterflies (loco_kernels.h; the argmax's, by the decode step's rule, in decoder_common.h) whose two operands every lane
+// pair adds (or compares) symmetrically, so all 64 lanes hold the same value and nothing depends on the row's place, on M or on the
+// other rows.  The reduction's order depends on (B, S) only.  No atomics; neither kernel allocates, synchronises or depends on the host.
 #include <climits>
 
-#include "loco_kernels.h"
+#include "decoder_common.h"
 
 namespace loco {
 
 namespace {
-
-// a beats b in the argmax: the first NaN wins, as in torch; otherwise the larger value, the lower index on a tie (dec_select_kernel)
-__device__ __forceinline__ bool score_better(float av, int ai, float bv, int bi) {
-    const bool an = av != av, bn = bv != bv;
-    if (an || bn) return an && (!bn || ai < bi);
-    return av > bv || (av == bv && ai < bi);
-}
 
 // 256 threads = 4 waves = 4 rows.  Lane l reads columns l, l + 64, ... < V and never another.  -inf entries add exp(-inf) = 0; a row
 // whose maximum is +inf or -inf gives inf - inf = NaN and a NaN entry a NaN sum, as torch.log_softmax does.
@@ -45,19 +38,13 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restr
     for (int n = lane; n < V; n += 64) {
         const float v = x[n];
         mx = fmaxf(mx, v);
-        if (score_better(v, n, bv, bi)) bv = v, bi = n;
+        if (argmax_better(v, n, bv, bi)) bv = v, bi = n;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (score_better(ov, oi, bv, bi)) bv = ov, bi = oi;
-    }
+    mx = wave_max(mx);
+    wave_argmax(bv, bi);
     float sum = 0.f;
     for (int n = lane; n < V; n += 64) sum += expf(x[n] - mx);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    sum = wave_sum(sum);
     if (!targets) target = bi;
     // a label outside [0, V) is never an index: the row is NaN and counts, so the loss says so
     const float xt = (target >= 0 && target < V) ? x[target] : NAN;
@@ -85,11 +72,8 @@ __global__ __launch_bounds__(1024) void score_reduce_kernel(const float* __restr
             const bool valid = !targets || targets[i] != ignore_index;
             if (valid) s += (double)logprob[i], c += 1;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s += __shfl_xor(s, off, 64);
-            c += __shfl_xor(c, off, 64);
-        }
+        s = wave_sum(s);
+        c = wave_sum(c);
         if (lane == 0) {
             if (seq_logprob) seq_logprob[b] = (float)s;
             if (seq_count) seq_count[b] = c;

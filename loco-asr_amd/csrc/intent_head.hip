@@ -17,8 +17,10 @@
 #include <stdint.h>
 
 #include "../../include/loco_asr.h"
+#include "loco_kernels.h"
 
 namespace {
+using loco::wave_max, loco::wave_sum;
 
 constexpr int D = 768;       // embedding size
 constexpr int C = 101;       // classes
@@ -30,17 +32,6 @@ thread_local char g_head_err[256];
 struct Part {  // per (b, split)
     float m, l, s;  // running max, sum exp, sum alpha*dalpha (backward)
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // Where a clip's frames come from.  Padded: x [B, T, 768] as the reference's collate_fn builds it.  Ragged: clips laid end to end
 // in store [rows, 768], batch entry b is clip idx[b] (offsets in rows, 64-bit), and its frames t >= lengths[idx[b]] are the zeros

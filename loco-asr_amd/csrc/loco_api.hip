@@ -97,7 +97,6 @@ struct DecoderW {
     int32_t* host_state = nullptr;  // pinned: loco_decoder_generate reads the device's "rows still open" word through it
 };
 constexpr int kDecMaxPositions = 450;  // SpeechT5Config.max_text_positions; HF's table has max_text_positions + pad_token_id + 1 = 452 rows
-constexpr int kDecStartToken = 2, kDecEosToken = 2, kDecPadToken = 1;
 
 // Profiling buckets, named after the kernel that runs in them (the two precision modes have their own attention and
 // positional-conv buckets: the f16x3 positional conv IS a gemm_f16x3_dma_kernel launch, but keeps a bucket of its own because
@@ -2014,11 +2013,23 @@ void make_dec_plan(int layers, int B, int T, int S, DecPlan& p) {
     p.total = o;
 }
 
-int dec_check(const loco_encoder* e, const char* fn, int B, int T, int S, const void* ws, size_t bytes, DecPlan& p) {
+#define DEC_TRY(expr)           \
+    do {                        \
+        const int rc_ = (expr); \
+        if (rc_) return rc_;    \
+    } while (0)
+
+// what every decoder entry asks of its handle first (dec_check, pool_check)
+int dec_handle_check(const loco_encoder* e, const char* fn) {
     if (!e) return fail(LOCO_E_INVALID, "%s: null encoder", fn);
     if (!e->finalized || !e->dec.ready)
         return fail(LOCO_E_STATE, "%s: the handle has no decoder weights (decoder.prenet.*, decoder.wrapped_decoder.*, text_decoder_postnet.*) or "
                                   "loco_finalize_weights has not run", fn);
+    return LOCO_OK;
+}
+
+int dec_check(const loco_encoder* e, const char* fn, int B, int T, int S, const void* ws, size_t bytes, DecPlan& p) {
+    DEC_TRY(dec_handle_check(e, fn));
     if (B <= 0 || T <= 0 || S <= 0) return fail(LOCO_E_INVALID, "%s: B, T_enc and the sequence length must be positive", fn);
     if (S > kDecMaxPositions) return fail(LOCO_E_INVALID, "%s: %d positions exceed max_text_positions = %d", fn, S, kDecMaxPositions);
     if (!ws) return fail(LOCO_E_INVALID, "%s: null workspace", fn);
@@ -2046,12 +2057,6 @@ int dec_attention(hipStream_t s, const float* q, long ldq, long sq, const float*
                                  1.0f, scratch, s));
     return LOCO_OK;
 }
-
-#define DEC_TRY(expr)           \
-    do {                        \
-        const int rc_ = (expr); \
-        if (rc_) return rc_;    \
-    } while (0)
 
 // one decode step: token t of every row in, token t + 1 out; B rows through the weight-streaming GEMM
 int dec_step(loco_encoder* e, const DecPlan& p, char* ws, int t, float* logits_out, hipStream_t s) {
@@ -2087,12 +2092,19 @@ int dec_step(loco_encoder* e, const DecPlan& p, char* ws, int t, float* logits_o
     return LOCO_OK;
 }
 
+// the plan's key counts of the cross-attention: the caller's frame counts, or T_enc for every clip
+int dec_set_frames(const DecPlan& p, char* ws, const int32_t* enc_frames, hipStream_t s) {
+    int32_t* frames = reinterpret_cast<int32_t*>(ws + p.off_frames);
+    if (enc_frames)
+        HIP_TRY(hipMemcpyAsync(frames, enc_frames, (size_t)p.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    else  // no frame counts: every encoder row is a key
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(frames), p.T, (size_t)p.B, s));
+    return LOCO_OK;
+}
+
 int dec_begin(loco_encoder* e, const DecPlan& p, char* ws, const float* enc_out, const int32_t* enc_frames, hipStream_t s) {
     auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    if (enc_frames)
-        HIP_TRY(hipMemcpyAsync(I(p.off_frames), enc_frames, (size_t)p.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    else  // no frame counts: every encoder row is a key
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(I(p.off_frames)), p.T, (size_t)p.B, s));
+    DEC_TRY(dec_set_frames(p, ws, enc_frames, s));
     HIP_TRY(launch_dec_begin(I(p.off_tokens), p.B, p.S, kDecStartToken, kDecPadToken, I(p.off_lengths), I(p.off_state), s));
     return dec_cross_kv(e, p, ws, enc_out, s);
 }
@@ -2142,10 +2154,7 @@ int dec_forward_walk(loco_encoder* e, const DecPlan& p, char* ws, const float* e
     float *x0 = F(p.off_x0), *x1 = F(p.off_x1), *tmp = F(p.off_tmp), *q = F(p.off_q), *ctx = F(p.off_ctx), *ffn = F(p.off_ffn), *scr = F(p.off_attn);
     const int M = B * S;
     const long ld_cross = (long)p.L * 2 * kHidden, ld_self = 2 * kHidden;
-    if (enc_frames)
-        HIP_TRY(hipMemcpyAsync(I(p.off_frames), enc_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    else  // no frame counts: every encoder row is a key
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(I(p.off_frames)), T_enc, (size_t)B, s));
+    DEC_TRY(dec_set_frames(p, ws, enc_frames, s));
     DEC_TRY(dec_cross_kv(e, p, ws, enc_out, s));
     HIP_TRY(launch_dec_embed(decoder_input_ids, S, d.embed, d.vocab, d.pos_tab, d.pos_rows, x0, B, S, nullptr, s));
     for (int l = 0; l < p.L; ++l) {
@@ -2402,10 +2411,7 @@ PoolState pool_state(const PoolPlan& p, char* ws) {
 }
 
 int pool_check(const loco_encoder* e, const char* fn, int slots, int T, int S, const void* ws, size_t bytes, PoolPlan& p) {
-    if (!e) return fail(LOCO_E_INVALID, "%s: null encoder", fn);
-    if (!e->finalized || !e->dec.ready)
-        return fail(LOCO_E_STATE, "%s: the handle has no decoder weights (decoder.prenet.*, decoder.wrapped_decoder.*, text_decoder_postnet.*) or "
-                                  "loco_finalize_weights has not run", fn);
+    DEC_TRY(dec_handle_check(e, fn));
     if (slots <= 0 || T <= 0) return fail(LOCO_E_INVALID, "%s: slots and T_cap must be positive", fn);
     if (slots > kSkinnyMaxM) return fail(LOCO_E_INVALID, "%s: %d slots exceed the decode step's limit of %d rows", fn, slots, kSkinnyMaxM);
     if (S < 2 || S > kDecMaxPositions)

@@ -163,6 +163,19 @@ __device__ __forceinline__ float wave_max_nonneg(float v) {
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
     return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
+// Sum / maximum over the wave's 64 lanes (all active, all left with the result): the xor butterfly with steps 32, 16, ..., 1, whose
+// order is part of the result -- many tests compare bits -- and is written down here only.  T: float, double or int.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 __device__ __forceinline__ void range_commit(float* slot, float amax, unsigned seen) {
     if (!slot) return;
     const unsigned bits = __float_as_uint(wave_max_nonneg(amax));  // non-negative floats order like their bit patterns; NaN never enters (fmaxf)
@@ -309,6 +322,7 @@ hipError_t launch_resample(const float* x, int B, long n_in, long x_stride, cons
                            long y_stride, hipStream_t s);
 
 // text decoder (decoder.hip)
+constexpr int kDecStartToken = 2, kDecEosToken = 2, kDecPadToken = 1;  // SpeechT5Config: decoder_start_token_id, eos_token_id, pad_token_id
 constexpr int kSkinnyMaxM = 64;        // rows of the weight-streaming GEMM (and clips of one decode step)
 constexpr int kDecAttnMaxSplit = 64;   // key splits of one decoder attention launch
 // C[m,n] = epi(sum_k A[m,k] W[n,k] + bias[n]) (+ R[m,n]); K % 256 == 0, lda / ldw % 4 == 0; columns n >= nsplit go to
@@ -361,7 +375,7 @@ hipError_t launch_pool_embed(const PoolState& p, const float* embed, int vocab, 
 hipError_t launch_pool_select(const PoolState& p, const float* logits, int vocab, int eos, hipStream_t s);
 
 // ---- decoder scores (decoder_score.hip) ----
-// logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (dec_select_kernel's rule) when targets is
+// logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (decoder_common.h's rule) when targets is
 // null; 0 where targets[m] == ignore_index, NaN for another target outside [0, V); chosen (optional) [M] = the target used
 hipError_t launch_token_logprob(const float* logits, long ld, const int32_t* targets, long M, int V, int ignore_index, float* logprob,
                                 int32_t* chosen, hipStream_t s);

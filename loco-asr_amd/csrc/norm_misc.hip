@@ -4,12 +4,6 @@
 
 namespace loco {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // y = (x - mean) * rsqrt(var + eps) * gamma + beta, biased variance, two-pass over registers
 // (HF nn.LayerNorm sites: modeling_speecht5.py:501,1023,1025,1276).  NV4 = dim / 256.
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
@@ -107,8 +101,7 @@ __global__ __launch_bounds__(256) void mask_count_kernel(const int32_t* __restri
     } else {
         for (long i = i0 + threadIdx.x; i < i1; i += 256) n += m[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(&frames[b], (part[0] + part[1]) + (part[2] + part[3]));
@@ -327,8 +320,7 @@ __global__ __launch_bounds__(256) void fold_pos_conv_kernel(const float* __restr
         const double x = v[(long)e * kPosK + tap];
         ss += x * x;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    ss = wave_sum(ss);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = ss;
     __syncthreads();
     const float norm = (float)sqrt(part[0] + part[1] + part[2] + part[3]);
@@ -399,8 +391,7 @@ hipError_t launch_sinusoid_table(float* tab, int rows, hipStream_t s) {
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
     float m = 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));
 }
 

@@ -3,7 +3,11 @@
 tree, each with its own libloco_asr.so): loco_decoder_generate (ids and step logits) and loco_decoder_begin + loco_decoder_step on
 GENERATE["b7_len40_30s"], and loco_decoder_forward (logits and the 7 hidden states) on TEACHER_FORCED[3] of
 tests/decoder_sweep_cases.py, 12 + 6 layers; then the model's Python surface (forward with labels and attentions, score, align, score_many,
-align_many, generate_many, generate with scores) on the 2 + 2 layer model of the pool tests.  One process per tree, since a process loads one library:
+align_many, generate_many, generate with scores) on the 2 + 2 layer model of the pool tests; then three operator-level blocks that reach
+the rules the decoder's kernels share (csrc/decoder_common.h) on inputs the model never produces: loco_decoder_score's argmax path on
+rows with ties, NaN and infinities, loco_op_decoder_attention beside loco_op_decoder_attention_probs around the tile and split
+boundaries, and loco_decoder_pool_* with a free, a finishing and a full-length slot in one step.  One process per tree, since a process
+loads one library:
 
     python tools/decoder_parent_compare.py dump PARENT_TREE out/parent
     python tools/decoder_parent_compare.py dump . out/new
@@ -58,7 +62,7 @@ def dump(root, outdir):
     torch.cuda.synchronize()
     save("forward_logits", logits), save("forward_hidden", torch.stack(hs))
     del model
-    dump_small(la, save)
+    dump_ops(dump_small(la, save), save)
     print("dumped", sorted(os.listdir(outdir)), "from", root)
 
 
@@ -107,6 +111,103 @@ def dump_small(la, save):
     save("small_generate_token_logprobs", gen.token_logprobs), save("small_generate_sequence_logprobs", gen.sequence_logprobs)
     save("small_generate_last_lengths", model._decoder_runtime.last_lengths)
     torch.cuda.synchronize()
+    return model
+
+
+def dump_ops(model, save):
+    """Operator-level blocks: every one small, all inputs drawn from a seeded CPU generator."""
+    import torch
+    lib, h = model.speecht5.encoder._lib, model.speecht5.encoder._handle
+    p = lambda tn: C.c_void_p(tn.data_ptr()) if tn is not None else None  # noqa: E731
+    st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    g = torch.Generator().manual_seed(29)
+    inf, nan = float("inf"), float("nan")
+    # loco_decoder_score with targets = NULL: the row's argmax and its log-probability.  V = 130: a lane holds up to three columns.
+    for V in (1, 81, 130):
+        base = torch.randn((8, V), generator=g)
+        rows = [base[0].clone() for _ in range(8)]  # row 0: a plain row
+        rows[1][:] = 0.75                           # all entries equal
+        rows[2] = base[2].clamp(max=1.0)            # equal maxima at columns 5 and 70
+        rows[3] = base[3].clone()                   # NaN at 3 and at 40
+        rows[4] = base[4].clone()                   # NaN beside +inf
+        rows[5][:] = -inf                           # all -inf
+        rows[6] = base[6].clone()                   # +inf in the last column
+        rows[7] = base[7].clone()                   # -inf but for one column
+        for col, val in ((5, 2.5), (70, 2.5)):
+            if col < V:
+                rows[2][col] = val
+        for col in (3, 40):
+            if col < V:
+                rows[3][col] = nan
+        for col, val in ((9, inf), (10, nan), (11, inf)):
+            if col < V:
+                rows[4][col] = val
+        rows[6][V - 1] = inf
+        rows[7][:V - 1] = -inf
+        x = torch.stack(rows).cuda()
+        lp, ch = torch.empty(8, device="cuda"), torch.empty(8, dtype=torch.int32, device="cuda")
+        sl, cnt, loss = torch.empty(1, device="cuda"), torch.empty(1, dtype=torch.int32, device="cuda"), torch.empty(1, device="cuda")
+        assert lib.loco_decoder_score(p(x), V, None, 1, 8, V, -100, p(lp), p(ch), p(sl), p(cnt), p(loss), st()) == 0
+        torch.cuda.synchronize()
+        for name, v in (("chosen", ch), ("logprob", lp), ("seq_logprob", sl), ("seq_count", cnt), ("loss", loss)):
+            save(f"op_score_V{V}_{name}", v)
+    # the attention and the probabilities kernel on the same q, k: tiles of 64 keys, two key splits at (Sq, Tk) = (1, 300)
+    B = 2
+    for Sq in (1, 3):
+        for Tk in (1, 63, 64, 65, 300):
+            q = torch.randn((B, Sq, 768), generator=g).cuda()
+            k = torch.randn((B, Tk, 768), generator=g).cuda()
+            v = torch.randn((B, Tk, 768), generator=g).cuda()
+            need = int(lib.loco_decoder_attention_scratch_bytes(B, Sq, Tk))
+            scr = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+            for ci, counts in enumerate(((0, Tk), (Tk - 1, 1))):
+                kc = torch.tensor(counts, dtype=torch.int32).cuda()
+                for causal in (0, 1):
+                    tag = f"Sq{Sq}_Tk{Tk}_kc{ci}_c{causal}"
+                    for off in sorted({0, max(Tk - Sq, 0)} if causal else {0}):
+                        out = torch.empty((B, Sq, 768), device="cuda")
+                        assert lib.loco_op_decoder_attention(p(q), p(k), p(v), p(kc), p(out), B, Sq, Tk, causal, off, 0.125, p(scr), scr.numel(), st()) == 0
+                        save(f"op_attn_{tag}_off{off}", out)
+                    P = torch.empty((B, 12, Sq, Tk), device="cuda")
+                    assert lib.loco_op_decoder_attention_probs(p(q), p(k), p(kc), p(P), B, Sq, Tk, causal, 768, Sq * 768, 768, Tk * 768, 0.125, st()) == 0
+                    save(f"op_probs_{tag}", P)
+    # loco_decoder_pool_* on the 2-layer model
+    T, S = 20, 8
+    enc = torch.randn((3, T, 768), generator=g).cuda()
+
+    def pool(tag, slots, admits):
+        """admits: {step: (slot ids, clip of enc, rows, frames or None, caps)}; steps until no slot is open"""
+        need = int(lib.loco_decoder_pool_workspace_bytes(h, slots, T, S))
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        block = torch.zeros(4 + 2 * slots, dtype=torch.int32).pin_memory()
+        toks = torch.zeros((slots, S), dtype=torch.int32).pin_memory()
+        assert lib.loco_decoder_pool_init(h, slots, T, S, p(ws), need, st()) == 0
+        logits, blocks = [], []
+        for step in range(2 * S):
+            if step in admits:
+                ids, clip, rows, frames, caps = admits[step]
+                n = len(ids)
+                fr = torch.tensor(frames, dtype=torch.int32).cuda() if frames is not None else None
+                assert lib.loco_decoder_pool_admit(h, slots, T, S, n, (C.c_int32 * n)(*ids), p(enc[clip]), T * 768, (C.c_int32 * n)(*rows), p(fr),
+                                                   (C.c_int32 * n)(*caps), p(ws), need, st()) == 0
+            lg = torch.empty((slots, 81), device="cuda")
+            assert lib.loco_decoder_pool_step(h, slots, T, S, S - 2, T, p(lg), p(ws), need, st()) == 0
+            assert lib.loco_decoder_pool_poll(h, slots, T, S, p(block), p(ws), need, st()) == 0
+            torch.cuda.synchronize()
+            logits.append(lg), blocks.append(block.clone())
+            if int(block[0]) == 0 and step >= max(admits):
+                break
+        for r in range(slots):
+            assert lib.loco_decoder_pool_read(h, slots, T, S, r, p(toks[r]), p(ws), need, st()) == 0
+        torch.cuda.synchronize()
+        lengths = blocks[-1][4 + slots:].tolist()
+        for r in range(slots):
+            toks[r, lengths[r]:] = -1  # beyond the utterance the buffer is the workspace's own
+        save(f"op_pool_{tag}_logits", torch.stack(logits)), save(f"op_pool_{tag}_poll", torch.stack(blocks)), save(f"op_pool_{tag}_tokens", toks)
+
+    pool("one_slot_cap2", 1, {0: ([0], 0, [T], None, [2])})
+    # step 0 sees slot 0 finishing (cap 2), slot 1 free and slot 2 on its way to the full length; slot 1 is admitted while slot 2 goes on
+    pool("three_slots", 3, {0: ([0, 2], 0, [T, 13], None, [2, S]), 1: ([1], 2, [T], [17], [4])})
 
 
 def compare(a, b):
