@@ -588,6 +588,63 @@ int loco_decoder_pool_poll(loco_encoder* enc, int32_t slots, int32_t T_cap, int3
 int loco_decoder_pool_read(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t slot, int32_t* tokens, const void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- decoder sampling: temperature / top-k / top-p on the device, N hypotheses per utterance in the slot pool ----------------------
+ * The rule, for a row of logits l[0..V) (csrc/decoder_sample.hip, one definition):
+ *   1. z_i = l_i / temperature, an fp32 division (HF's TemperatureLogitsWarper)
+ *   2. top_k (0 = off, clamped to V): i survives iff fewer than top_k columns have z_j > z_i; ties at the threshold all survive
+ *      (TopKLogitsWarper)
+ *   3. top_p (1 = off), over the survivors with p = softmax(z) over them: A_i = the sum of p_j over survivors with z_j <= z_i; i is
+ *      kept iff A_i > 1 - top_p, or i is the row's argmax (TopPLogitsWarper with min_tokens_to_keep = 1).  Equal logits are kept or
+ *      dropped together.
+ *   4. u = (x0 >> 8) * 2^-24 in [0, 1), x0 the first word of the Philox4x32-10 block with key (seed & 0xffffffff, seed >> 32) and
+ *      counter (utterance, hypothesis, t, 0); t = the index in its token buffer of the token being written (the first sampled token
+ *      has t = 1).  Nothing else feeds the generator.
+ *   5. over the kept columns in ascending index, w_i = expf(z_i - max z), Z their sum: the token is the first kept index whose
+ *      inclusive prefix sum exceeds u * Z, the last kept index if rounding leaves none.  The order of the additions depends on V alone;
+ *      the fp32 terms of this sum and of step 3's are added in double.
+ *   6. a row with a NaN, a +inf maximum or nothing but -inf: its argmax (the first NaN wins, the lowest index on a tie)
+ *   7. a greedy row: the argmax of the raw logits, the token loco_decoder_pool_step appends
+ * A row's token is a pure function of its V logits, the config and its counter, bit for bit.
+ *   loco_op_sample_tokens   the rule alone.  logits f32 (device), row m at logits + m * ld, ld >= V, columns >= V never read;
+ *               counters u32 [M, 3] (device) = (utterance, hypothesis, t) of every row; greedy NULL or i32 [M] (device), nonzero = rule 7;
+ *               tokens i32 [M] (device).  For tests, each NULL or: keep i32 [M, V] (1 = the draw ran over the column; for a row of
+ *               rule 6 or 7 the argmax alone), uniform f32 [M] (u of every row).  One launch, asynchronous.
+ *   loco_decoder_pool_admit_samples   loco_decoder_pool_admit for n clips with `copies` hypotheses each: slot_ids i32 [n * copies]
+ *               (HOST, distinct), clip i's hypotheses in slot_ids[i * copies .. (i + 1) * copies).  enc_out, clip_stride, enc_rows [n],
+ *               enc_frames [n] (DEVICE or NULL), caps [n] as there, per clip.  utterances u32 [n] and hypotheses u32 [n * copies] (HOST) are
+ *               the counter's first two words; greedy NULL (every slot draws) or i32 [n * copies] (HOST), nonzero = rule 7.  A clip's
+ *               cross k|v is projected once, into its first slot, and copied on the device into the others: the same bytes as
+ *               projected there.  One read-back of the slots' status (one stream synchronisation) per call.
+ *   loco_decoder_pool_step_sample    loco_decoder_pool_step's launches with the sampling select kernel in the greedy one's place: the
+ *               same bounds, end / cap / advance rules and poll block.  step_tokens NULL or i32 [slots] (device): the token each
+ *               live slot appended, -100 for the others.  A slot admitted by loco_decoder_pool_admit is greedy here.
+ * Which slots of a pool draw is kept by the handle, per workspace address (the greedy entry points enqueue what they always did, so
+ * they cannot mark a slot on the device), from loco_decoder_pool_admit_samples until the slot is admitted again or
+ * loco_decoder_pool_init runs on that workspace.  The entry (16 bytes) outlives the workspace: freeing a workspace does not tell the
+ * handle, so a slot that finished still counts as drawing, and the entry goes with loco_decoder_pool_init on that address (which must
+ * precede any reuse of the memory as a pool) or with loco_destroy.  The mask is an argument of the select launch, read on the host
+ * when loco_decoder_pool_step_sample is called: a captured graph of that call replays the mask of the moment of capture, so admit
+ * before capturing and capture again after an admission that changes which slots draw.  (utterance, hypothesis) of every slot live
+ * in the workspace, after every region of a greedy pool.  loco_decoder_pool_step on a pool that holds such a slot: LOCO_E_STATE.
+ * Errors: a config whose struct_size is not sizeof(loco_sample_config), a temperature that is not finite or not > 0, top_k < 0, top_p
+ * outside (0, 1]: LOCO_E_INVALID naming the field; n * copies > slots and everything loco_decoder_pool_admit / _step refuse, alike. */
+typedef struct loco_sample_config {
+    uint32_t struct_size; /* sizeof(loco_sample_config) */
+    float temperature;
+    int32_t top_k;        /* 0 = off */
+    float top_p;          /* 1 = off */
+    uint64_t seed;
+} loco_sample_config;
+int loco_op_sample_tokens(const float* logits, int64_t ld, int32_t M, int32_t V, const loco_sample_config* config, const uint32_t* counters,
+                          const int32_t* greedy, int32_t* tokens, int32_t* keep, float* uniform, void* stream);
+int loco_decoder_pool_admit_samples(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, int32_t copies, const int32_t* slot_ids,
+                                    const float* enc_out, int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps,
+                                    const uint32_t* utterances, const uint32_t* hypotheses, const int32_t* greedy, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int loco_decoder_pool_step_sample(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames,
+                                  const loco_sample_config* config, float* step_logits, int32_t* step_tokens, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
 /* ---- decoder scores: log-probabilities of a transcript's tokens, per-sequence sums, the labels= loss --------------------------------
  * loco_decoder_score turns logits (loco_decoder_forward's [B, S, V], or a block of step logits) into what a transcript is judged by.
  * Stateless: no handle, no workspace.  Asynchronous, reads no host memory, two launches on `stream`; it can be captured like a step.

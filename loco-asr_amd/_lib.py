@@ -29,7 +29,13 @@ class KernelStat(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class SampleConfig(C.Structure):
+    """loco_sample_config: ``struct_size`` must be ``ctypes.sizeof(SampleConfig)``."""
+    _fields_ = [("struct_size", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
 _vp, _i32, _i64, _sz, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
+_u32p = C.POINTER(C.c_uint32)
 
 # name -> (restype, argtypes); exactly the symbols of include/loco_asr.h
 SIGNATURES = {
@@ -124,6 +130,10 @@ SIGNATURES = {
     "loco_decoder_pool_step": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_decoder_pool_poll": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_decoder_pool_read": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "loco_op_sample_tokens": (C.c_int, [_vp, _i64, _i32, _i32, C.POINTER(SampleConfig), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "loco_decoder_pool_admit_samples": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _i64, C.POINTER(_i32), _vp, C.POINTER(_i32),
+                                                  _u32p, _u32p, C.POINTER(_i32), _vp, _sz, _vp]),
+    "loco_decoder_pool_step_sample": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(SampleConfig), _vp, _vp, _vp, _sz, _vp]),
     "loco_decoder_score": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),

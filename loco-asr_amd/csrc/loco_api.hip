@@ -191,6 +191,9 @@ struct loco_encoder {
     int text_pe_rows = 0;
     bool speech_ready = false;    // set by loco_finalize_weights when the speech prenet weights were supplied
     DecoderW dec;                 // text decoder (optional)
+    // decoder pools that hold slots which sample: (workspace, bit r = slot r draws).  On the host because loco_decoder_pool_admit and
+    // loco_decoder_pool_step enqueue what they always did: neither can mark a slot on the device.  Single caller, as the pool itself.
+    std::vector<std::pair<const void*, unsigned long long>> pool_sampled;
     std::map<std::string, std::vector<int64_t>> dec_shapes;  // shapes of the decoder tensors as loaded (the vocabulary is theirs)
     // concurrency inside one forward: a batch may run as two half-batches on two streams (loco_set_streams).  The side stream and
     // its events are created on first use under side_mu; forwards in flight together serialise their second halves on it.
@@ -2367,7 +2370,7 @@ namespace {
 struct PoolPlan {
     int slots, T, S, L;
     size_t off_poll, off_pos, off_cap, off_frames, off_counts, off_tokens, off_nonpad, off_cross, off_self, off_x0, off_x1, off_tmp, off_q, off_ctx,
-        off_ffn, off_logits, off_attn, total;
+        off_ffn, off_logits, off_attn, off_sample, total;
 };
 
 void make_pool_plan(int layers, int slots, int T, int S, PoolPlan& p) {
@@ -2396,6 +2399,7 @@ void make_pool_plan(int layers, int slots, int T, int S, PoolPlan& p) {
     p.off_ffn = take((size_t)slots * kFfn * f);
     p.off_logits = take((size_t)slots * 128 * f);
     p.off_attn = take(dec_pool_attention_scratch_bytes(slots, T > S ? T : S));
+    p.off_sample = take((size_t)2 * slots * sizeof(uint32_t));  // (utterance, hypothesis) of every slot: after every region a greedy pool has
     p.total = o;
 }
 
@@ -2422,83 +2426,43 @@ int pool_check(const loco_encoder* e, const char* fn, int slots, int T, int S, c
     return LOCO_OK;
 }
 
-}  // namespace
-
-size_t loco_decoder_pool_workspace_bytes(const loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max) {
-    if (!e || slots <= 0 || slots > kSkinnyMaxM || T_cap <= 0 || S_max < 2 || S_max > kDecMaxPositions) return 0;
-    if (!loco_has_decoder(e)) return 0;
-    PoolPlan p;
-    make_pool_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, p);
-    return p.total;
+// bit r: slot r of the pool in `ws` draws (0: the handle knows no such pool)
+unsigned long long pool_sampled_slots(const loco_encoder* e, const void* ws) {
+    for (const auto& it : e->pool_sampled)
+        if (it.first == ws) return it.second;
+    return 0;
 }
 
-int loco_decoder_pool_init(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, void* workspace, size_t workspace_bytes, void* stream) {
-    PoolPlan p;
-    DEC_TRY(pool_check(e, "loco_decoder_pool_init", slots, T_cap, S_max, workspace, workspace_bytes, p));
-    HIP_TRY(launch_pool_init(pool_state(p, static_cast<char*>(workspace)), (hipStream_t)stream));
+// mask 0 forgets the pool
+void pool_sampled_set(loco_encoder* e, const void* ws, unsigned long long mask) {
+    auto& v = e->pool_sampled;
+    for (size_t i = 0; i < v.size(); ++i)
+        if (v[i].first == ws) {
+            if (mask) v[i].second = mask;
+            else v.erase(v.begin() + i);
+            return;
+        }
+    if (mask) v.emplace_back(ws, mask);
+}
+
+// what loco_decoder_pool_admit and loco_decoder_pool_admit_samples ask of clip i of n
+int pool_admit_check(const char* fn, int T_cap, int S_max, int n, int i, int rows, int cap, int64_t clip_stride) {
+    if (rows < 1 || rows > T_cap)
+        return fail(LOCO_E_INVALID, "%s: clip %d has %d encoder rows, the pool holds 1 .. T_cap = %d per slot", fn, i, rows, T_cap);
+    if (n > 1 && clip_stride < (int64_t)rows * kHidden)  // clips would overlap in enc_out
+        return fail(LOCO_E_INVALID, "%s: clip stride %lld is shorter than clip %d's %d rows", fn, (long long)clip_stride, i, rows);
+    if (cap < 2 || cap > S_max) return fail(LOCO_E_INVALID, "%s: clip %d has cap %d, outside 2 .. S_max = %d", fn, i, cap, S_max);
     return LOCO_OK;
 }
 
-int loco_decoder_pool_admit(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, const int32_t* slot_ids, const float* enc_out,
-                            int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    const char* fn = "loco_decoder_pool_admit";
-    PoolPlan p;
-    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
-    if (n <= 0 || n > slots) return fail(LOCO_E_INVALID, "%s: %d clips for a pool of %d slots", fn, n, slots);
-    if (!slot_ids || !enc_out || !enc_rows || !caps) return fail(LOCO_E_INVALID, "%s: null argument", fn);
-    if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
-        return fail(LOCO_E_INVALID, "%s: enc_out and the clip stride must be 16-byte aligned", fn);
-    PoolAdmit a{};
-    a.n = n;
-    unsigned long long seen = 0;
-    for (int i = 0; i < n; ++i) {
-        if (slot_ids[i] < 0 || slot_ids[i] >= slots) return fail(LOCO_E_INVALID, "%s: slot %d of a pool of %d slots", fn, slot_ids[i], slots);
-        if (seen >> slot_ids[i] & 1) return fail(LOCO_E_INVALID, "%s: slot %d is named twice", fn, slot_ids[i]);
-        seen |= 1ull << slot_ids[i];
-        if (enc_rows[i] < 1 || enc_rows[i] > T_cap)
-            return fail(LOCO_E_INVALID, "%s: clip %d has %d encoder rows, the pool holds 1 .. T_cap = %d per slot", fn, i, enc_rows[i], T_cap);
-        if (n > 1 && clip_stride < (int64_t)enc_rows[i] * kHidden)  // clips would overlap in enc_out
-            return fail(LOCO_E_INVALID, "%s: clip stride %lld is shorter than clip %d's %d rows", fn, (long long)clip_stride, i, enc_rows[i]);
-        if (caps[i] < 2 || caps[i] > S_max) return fail(LOCO_E_INVALID, "%s: clip %d has cap %d, outside 2 .. S_max = %d", fn, i, caps[i], S_max);
-        a.slot[i] = slot_ids[i], a.cap[i] = caps[i], a.rows[i] = enc_rows[i];
-    }
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
-    const PoolState st = pool_state(p, ws);
-    // a slot that is open may not be overwritten: the slots' status is read back (the one place the pool waits for the stream; the
-    // caller admits after a poll, when the stream is idle anyway)
-    std::vector<int32_t> status(slots);
-    HIP_TRY(hipMemcpyAsync(status.data(), st.status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i)
-        if (status[slot_ids[i]] == kPoolOpen) return fail(LOCO_E_STATE, "%s: slot %d is open (its utterance has not finished)", fn, slot_ids[i]);
-    // cross-attention k|v of every layer, one exact-fp32 product per clip into the slot's own region: the rows of a clip are the same
-    // bits whichever clips are admitted beside it
-    const int N = p.L * 2 * kHidden;
-    for (int i = 0; i < n; ++i)
-        DEC_TRY(run_gemm(e, s, enc_out + (size_t)i * clip_stride, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0,
-                         reinterpret_cast<float*>(ws + p.off_cross) + (size_t)slot_ids[i] * T_cap * N, N, enc_rows[i], N, kHidden, kEpiNone));
-    HIP_TRY(launch_pool_admit(st, a, enc_frames, kDecStartToken, s));
-    return LOCO_OK;
-}
-
-int loco_decoder_pool_step(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames, float* step_logits,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "loco_decoder_pool_step";
-    PoolPlan p;
-    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
-    if (max_pos < 0 || max_pos + 1 >= S_max) return fail(LOCO_E_INVALID, "%s: position bound %d writes token %d of a buffer of %d", fn, max_pos, max_pos + 1, S_max);
-    if (max_frames < 1 || max_frames > T_cap) return fail(LOCO_E_INVALID, "%s: frame bound %d is outside 1 .. T_cap = %d", fn, max_frames, T_cap);
+// The step up to its logits, for loco_decoder_pool_step and loco_decoder_pool_step_sample: the embedding of every open slot's token,
+// the layers, the lm_head.  The caller's select kernel follows.
+int pool_step_walk(loco_encoder* e, const PoolPlan& p, char* ws, const PoolState& st, int max_pos, int max_frames, float* logits, hipStream_t s) {
     const DecoderW& d = e->dec;
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
-    const PoolState st = pool_state(p, ws);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     float *x0 = F(p.off_x0), *x1 = F(p.off_x1), *tmp = F(p.off_tmp), *q = F(p.off_q), *ctx = F(p.off_ctx), *ffn = F(p.off_ffn), *scr = F(p.off_attn);
-    float* logits = step_logits ? step_logits : F(p.off_logits);
     const long ld_cross = (long)p.L * 2 * kHidden, ld_self = 2 * kHidden;
-    const int B = slots;
+    const int B = p.slots;
     HIP_TRY(launch_pool_embed(st, d.embed, d.vocab, d.pos_tab, d.pos_rows, x0, max_pos, max_frames, s));
     for (int l = 0; l < p.L; ++l) {
         const DecLayerW& lw = d.L[l];
@@ -2519,7 +2483,185 @@ int loco_decoder_pool_step(loco_encoder* e, int32_t slots, int32_t T_cap, int32_
         DEC_TRY(run_ln(e, s, tmp, lw.final_ln.w, lw.final_ln.b, x0, B, kHidden));
     }
     DEC_TRY(run_skinny(s, x0, WB{d.lm_head, nullptr}, nullptr, logits, B, d.vocab, kHidden, kEpiNone));
-    HIP_TRY(launch_pool_select(st, logits, d.vocab, kDecEosToken, s));
+    return LOCO_OK;
+}
+
+// the bounds a step's launches are sized by (loco_decoder_pool_step, loco_decoder_pool_step_sample)
+int pool_step_bounds_check(const char* fn, int T_cap, int S_max, int max_pos, int max_frames) {
+    if (max_pos < 0 || max_pos + 1 >= S_max) return fail(LOCO_E_INVALID, "%s: position bound %d writes token %d of a buffer of %d", fn, max_pos, max_pos + 1, S_max);
+    if (max_frames < 1 || max_frames > T_cap) return fail(LOCO_E_INVALID, "%s: frame bound %d is outside 1 .. T_cap = %d", fn, max_frames, T_cap);
+    return LOCO_OK;
+}
+
+int sample_config_check(const loco_sample_config* c, const char* fn, SampleRule& rule) {
+    if (!c) return fail(LOCO_E_INVALID, "%s: null loco_sample_config", fn);
+    if (c->struct_size != sizeof(loco_sample_config))
+        return fail(LOCO_E_INVALID, "%s: loco_sample_config.struct_size = %u, this library's is %zu", fn, c->struct_size, sizeof(loco_sample_config));
+    if (!(c->temperature > 0.f) || !std::isfinite(c->temperature))
+        return fail(LOCO_E_INVALID, "%s: loco_sample_config.temperature = %g must be finite and > 0", fn, (double)c->temperature);
+    if (c->top_k < 0) return fail(LOCO_E_INVALID, "%s: loco_sample_config.top_k = %d must be >= 0 (0 = off)", fn, c->top_k);
+    if (!(c->top_p > 0.f && c->top_p <= 1.f))
+        return fail(LOCO_E_INVALID, "%s: loco_sample_config.top_p = %g is outside (0, 1] (1 = off)", fn, (double)c->top_p);
+    rule = SampleRule{c->temperature, c->top_k, c->top_p, (uint32_t)(c->seed & 0xffffffffu), (uint32_t)(c->seed >> 32)};
+    return LOCO_OK;
+}
+
+}  // namespace
+
+size_t loco_decoder_pool_workspace_bytes(const loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max) {
+    if (!e || slots <= 0 || slots > kSkinnyMaxM || T_cap <= 0 || S_max < 2 || S_max > kDecMaxPositions) return 0;
+    if (!loco_has_decoder(e)) return 0;
+    PoolPlan p;
+    make_pool_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, p);
+    return p.total;
+}
+
+int loco_decoder_pool_init(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, void* workspace, size_t workspace_bytes, void* stream) {
+    PoolPlan p;
+    DEC_TRY(pool_check(e, "loco_decoder_pool_init", slots, T_cap, S_max, workspace, workspace_bytes, p));
+    HIP_TRY(launch_pool_init(pool_state(p, static_cast<char*>(workspace)), (hipStream_t)stream));
+    pool_sampled_set(e, workspace, 0);
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_admit(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, const int32_t* slot_ids, const float* enc_out,
+                            int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_admit";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (n <= 0 || n > slots) return fail(LOCO_E_INVALID, "%s: %d clips for a pool of %d slots", fn, n, slots);
+    if (!slot_ids || !enc_out || !enc_rows || !caps) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
+        return fail(LOCO_E_INVALID, "%s: enc_out and the clip stride must be 16-byte aligned", fn);
+    PoolAdmit a{};
+    a.n = n;
+    unsigned long long seen = 0;
+    for (int i = 0; i < n; ++i) {
+        if (slot_ids[i] < 0 || slot_ids[i] >= slots) return fail(LOCO_E_INVALID, "%s: slot %d of a pool of %d slots", fn, slot_ids[i], slots);
+        if (seen >> slot_ids[i] & 1) return fail(LOCO_E_INVALID, "%s: slot %d is named twice", fn, slot_ids[i]);
+        seen |= 1ull << slot_ids[i];
+        DEC_TRY(pool_admit_check(fn, T_cap, S_max, n, i, enc_rows[i], caps[i], clip_stride));
+        a.slot[i] = slot_ids[i], a.cap[i] = caps[i], a.rows[i] = enc_rows[i];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    // a slot that is open may not be overwritten: the slots' status is read back (the one place the pool waits for the stream; the
+    // caller admits after a poll, when the stream is idle anyway)
+    std::vector<int32_t> status(slots);
+    HIP_TRY(hipMemcpyAsync(status.data(), st.status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i)
+        if (status[slot_ids[i]] == kPoolOpen) return fail(LOCO_E_STATE, "%s: slot %d is open (its utterance has not finished)", fn, slot_ids[i]);
+    // cross-attention k|v of every layer, one exact-fp32 product per clip into the slot's own region: the rows of a clip are the same
+    // bits whichever clips are admitted beside it
+    const int N = p.L * 2 * kHidden;
+    for (int i = 0; i < n; ++i)
+        DEC_TRY(run_gemm(e, s, enc_out + (size_t)i * clip_stride, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0,
+                         reinterpret_cast<float*>(ws + p.off_cross) + (size_t)slot_ids[i] * T_cap * N, N, enc_rows[i], N, kHidden, kEpiNone));
+    HIP_TRY(launch_pool_admit(st, a, enc_frames, kDecStartToken, s));
+    pool_sampled_set(e, workspace, pool_sampled_slots(e, workspace) & ~seen);  // these slots are greedy from here on
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_step(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames, float* step_logits,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_step";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    DEC_TRY(pool_step_bounds_check(fn, T_cap, S_max, max_pos, max_frames));
+    if (pool_sampled_slots(e, workspace))
+        return fail(LOCO_E_STATE, "%s: the pool holds slots admitted to sample (mask 0x%llx); step it with loco_decoder_pool_step_sample", fn,
+                    pool_sampled_slots(e, workspace));
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    float* logits = step_logits ? step_logits : reinterpret_cast<float*>(ws + p.off_logits);
+    DEC_TRY(pool_step_walk(e, p, ws, st, max_pos, max_frames, logits, s));
+    HIP_TRY(launch_pool_select(st, logits, e->dec.vocab, kDecEosToken, s));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_admit_samples(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t n, int32_t copies, const int32_t* slot_ids,
+                                    const float* enc_out, int64_t clip_stride, const int32_t* enc_rows, const int32_t* enc_frames, const int32_t* caps,
+                                    const uint32_t* utterances, const uint32_t* hypotheses, const int32_t* greedy, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_admit_samples";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    if (n <= 0 || copies <= 0 || (int64_t)n * copies > slots)
+        return fail(LOCO_E_INVALID, "%s: %d clips x %d copies for a pool of %d slots", fn, n, copies, slots);
+    if (!slot_ids || !enc_out || !enc_rows || !caps || !utterances || !hypotheses) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
+        return fail(LOCO_E_INVALID, "%s: enc_out and the clip stride must be 16-byte aligned", fn);
+    PoolAdmitSamples a{};
+    a.n = n * copies, a.copies = copies;
+    unsigned long long seen = 0, draws = 0;
+    for (int i = 0; i < n; ++i) {
+        DEC_TRY(pool_admit_check(fn, T_cap, S_max, n, i, enc_rows[i], caps[i], clip_stride));
+        for (int c = 0; c < copies; ++c) {
+            const int k = i * copies + c, r = slot_ids[k];
+            if (r < 0 || r >= slots) return fail(LOCO_E_INVALID, "%s: slot %d of a pool of %d slots", fn, r, slots);
+            if (seen >> r & 1) return fail(LOCO_E_INVALID, "%s: slot %d is named twice", fn, r);
+            seen |= 1ull << r;
+            if (!(greedy && greedy[k])) draws |= 1ull << r;
+            a.slot[k] = r, a.cap[k] = caps[i], a.rows[k] = enc_rows[i], a.utterance[k] = utterances[i], a.hypothesis[k] = hypotheses[k];
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    // as loco_decoder_pool_admit: an open slot may not be overwritten; one read-back, one wait for the stream, for the whole call
+    std::vector<int32_t> status(slots);
+    HIP_TRY(hipMemcpyAsync(status.data(), st.status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < a.n; ++k)
+        if (status[a.slot[k]] == kPoolOpen) return fail(LOCO_E_STATE, "%s: slot %d is open (its utterance has not finished)", fn, a.slot[k]);
+    // a clip's cross k|v: loco_decoder_pool_admit's product into the first slot, then copies of those bytes into the siblings' regions
+    const int N = p.L * 2 * kHidden;
+    float* cross = reinterpret_cast<float*>(ws + p.off_cross);
+    for (int i = 0; i < n; ++i) {
+        float* first = cross + (size_t)a.slot[i * copies] * T_cap * N;
+        DEC_TRY(run_gemm(e, s, enc_out + (size_t)i * clip_stride, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0, first, N, enc_rows[i], N, kHidden,
+                         kEpiNone));
+        for (int c = 1; c < copies; ++c)
+            HIP_TRY(hipMemcpyAsync(cross + (size_t)a.slot[i * copies + c] * T_cap * N, first, (size_t)enc_rows[i] * N * sizeof(float),
+                                   hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(launch_pool_admit_samples(st, a, enc_frames, kDecStartToken, reinterpret_cast<uint32_t*>(ws + p.off_sample), s));
+    pool_sampled_set(e, workspace, (pool_sampled_slots(e, workspace) & ~seen) | draws);
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_step_sample(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames,
+                                  const loco_sample_config* config, float* step_logits, int32_t* step_tokens, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    const char* fn = "loco_decoder_pool_step_sample";
+    PoolPlan p;
+    DEC_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    DEC_TRY(pool_step_bounds_check(fn, T_cap, S_max, max_pos, max_frames));
+    SampleRule rule;
+    DEC_TRY(sample_config_check(config, fn, rule));
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(p, ws);
+    float* logits = step_logits ? step_logits : reinterpret_cast<float*>(ws + p.off_logits);
+    DEC_TRY(pool_step_walk(e, p, ws, st, max_pos, max_frames, logits, s));
+    HIP_TRY(launch_pool_sample_select(st, reinterpret_cast<const uint32_t*>(ws + p.off_sample), pool_sampled_slots(e, workspace), rule, logits,
+                                      e->dec.vocab, kDecEosToken, step_tokens, -100, s));  // -100: the ignore_index loco_decoder_score's callers pass
+    return LOCO_OK;
+}
+
+int loco_op_sample_tokens(const float* logits, int64_t ld, int32_t M, int32_t V, const loco_sample_config* config, const uint32_t* counters,
+                          const int32_t* greedy, int32_t* tokens, int32_t* keep, float* uniform, void* stream) {
+    const char* fn = "loco_op_sample_tokens";
+    if (!logits || !counters || !tokens) return fail(LOCO_E_INVALID, "%s: null logits, counters or tokens", fn);
+    if (M < 1 || V < 1) return fail(LOCO_E_INVALID, "%s: M = %d and V = %d must both be >= 1", fn, M, V);
+    if (ld < V) return fail(LOCO_E_INVALID, "%s: row stride ld = %lld < V = %d", fn, (long long)ld, V);
+    SampleRule rule;
+    DEC_TRY(sample_config_check(config, fn, rule));
+    HIP_TRY(launch_sample_tokens(logits, (long)ld, M, V, rule, counters, greedy, tokens, keep, uniform, (hipStream_t)stream));
     return LOCO_OK;
 }
 

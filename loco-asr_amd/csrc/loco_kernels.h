@@ -374,6 +374,29 @@ hipError_t launch_pool_embed(const PoolState& p, const float* embed, int vocab, 
                              int max_frames, hipStream_t s);
 hipError_t launch_pool_select(const PoolState& p, const float* logits, int vocab, int eos, hipStream_t s);
 
+// ---- decoder sampling (decoder_sample.hip) ----
+// temperature > 0, top_k >= 0 (0 = off), top_p in (0, 1] (1 = off), the Philox key = the seed's low and high word
+struct SampleRule {
+    float temperature;
+    int top_k;
+    float top_p;
+    uint32_t key0, key1;
+};
+// tokens[m] = the rule's token for row m of logits (ld >= V; columns >= V are never read) with the Philox counter counters[m] =
+// (utterance, hypothesis, t); greedy (optional) [M]: nonzero = the row's argmax.  keep (optional) i32 [M, V], uniform (optional) f32 [M].
+hipError_t launch_sample_tokens(const float* logits, long ld, int M, int V, const SampleRule& rule, const uint32_t* counters, const int32_t* greedy,
+                                int32_t* tokens, int32_t* keep, float* uniform, hipStream_t s);
+struct PoolAdmitSamples {  // by value: at most 64 slots; slot i holds a hypothesis of clip i / copies
+    int n, copies;
+    int32_t slot[kSkinnyMaxM], cap[kSkinnyMaxM], rows[kSkinnyMaxM];
+    uint32_t utterance[kSkinnyMaxM], hypothesis[kSkinnyMaxM];
+};
+// ids u32 [slots, 2] on the device: (utterance, hypothesis) of every slot admitted this way
+hipError_t launch_pool_admit_samples(const PoolState& p, const PoolAdmitSamples& a, const int32_t* frames, int start, uint32_t* ids, hipStream_t s);
+// launch_pool_select for a pool whose slots r with bit r of `sampled` set draw by the rule; step_tokens (optional) i32 [slots]
+hipError_t launch_pool_sample_select(const PoolState& p, const uint32_t* ids, unsigned long long sampled, const SampleRule& rule, const float* logits,
+                                     int vocab, int eos, int32_t* step_tokens, int ignore_index, hipStream_t s);
+
 // ---- decoder scores (decoder_score.hip) ----
 // logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (decoder_common.h's rule) when targets is
 // null; 0 where targets[m] == ignore_index, NaN for another target outside [0, V); chosen (optional) [M] = the target used

@@ -7,8 +7,9 @@ the C ABI's ``loco_decoder_*`` entry points (include/loco_asr.h).
 ``SpeechT5DecoderWithTextPrenetMI355X`` (``.prenet``, ``.wrapped_decoder``) and ``SpeechT5TextDecoderPostnetMI355X`` only own
 parameters, so that ``load_state_dict`` of HF's dicts works; every FLOP runs in the HIP kernels of csrc/decoder.hip (the decode step)
 and the library's exact-fp32 GEMM / LayerNorm (the teacher-forced pass); csrc/decoder_probs.hip forms the attention probabilities of
-``output_attentions=True`` and the token timestamps of ``align``.  Greedy search only: beam search, sampling, prefixes and a
-decoder attention mask raise by name.  Scores -- the ``labels=`` loss, per-token and per-transcript log-probabilities -- come from
+``output_attentions=True`` and the token timestamps of ``align``.  ``generate`` / ``generate_many`` are greedy search only: beam search,
+sampling keywords, prefixes and a decoder attention mask raise by name.  Sampling has entry points of its own, ``sample`` / ``sample_many``
+(temperature, top-k, top-p; csrc/decoder_sample.hip draws in the slot pool).  Scores -- the ``labels=`` loss, per-token and per-transcript log-probabilities -- come from
 ``loco_decoder_score`` (csrc/decoder_score.hip) on the logits of either path.
 """
 from __future__ import annotations
@@ -119,6 +120,59 @@ class GreedySearchOutput:
     scores: Optional[Tuple[torch.Tensor, ...]] = None
     token_logprobs: Optional[torch.Tensor] = None
     sequence_logprobs: Optional[torch.Tensor] = None
+
+
+@dataclass
+class SampleOutput:
+    """What ``sample`` returns: ``sequences`` [B * N, S] in HF's num_return_sequences layout (clip b's hypotheses in rows b * N ..
+    b * N + N - 1, <pad> after </s>), ``seed`` the Philox seed that was used; with ``return_scores=True`` also ``token_logprobs``
+    [B * N, S - 1] (entry t = the model's log P(sequences[:, t + 1]), 0 at the <pad> columns) and ``sequence_logprobs`` [B * N]."""
+    sequences: torch.Tensor = None
+    token_logprobs: Optional[torch.Tensor] = None
+    sequence_logprobs: Optional[torch.Tensor] = None
+    seed: int = None
+
+
+class SampledHypotheses(list):
+    """``sample_many``'s hypotheses, ``hyps[u][h]``; ``seed`` is the Philox seed that was used."""
+    seed = None
+
+
+class SampledResults(tuple):
+    """``sample_many``'s (hypotheses, logits and / or scores); ``seed`` as on the hypotheses."""
+    seed = None
+
+
+MAX_RETURN_SEQUENCES = 64
+
+
+def check_sample_args(num_return_sequences, temperature, top_k, top_p, seed):
+    """(N, a _lib.SampleConfig) of checked sampling arguments; ValueError naming the offender.  ``seed=None`` draws 63 bits from
+    torch's default CPU generator (``torch.manual_seed`` makes the call reproducible)."""
+    try:
+        n = operator.index(num_return_sequences)
+    except TypeError:
+        raise ValueError(f"num_return_sequences must be an integer in 1 .. {MAX_RETURN_SEQUENCES}, got {num_return_sequences!r}") from None
+    if not 1 <= n <= MAX_RETURN_SEQUENCES:
+        raise ValueError(f"num_return_sequences = {n} is outside 1 .. {MAX_RETURN_SEQUENCES}")
+    t = float(temperature)
+    if not (t > 0 and t != float("inf")):
+        raise ValueError(f"temperature = {temperature} must be finite and > 0")
+    try:
+        k = operator.index(top_k)
+    except TypeError:
+        raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}") from None
+    if not 0 <= k < 2 ** 31:
+        raise ValueError(f"top_k = {k} must be >= 0 (0 = off)")
+    p = float(top_p)
+    if not 0 < p <= 1:
+        raise ValueError(f"top_p = {top_p} is outside (0, 1] (1 = off)")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+    seed = operator.index(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed = {seed} is outside 0 .. 2^64 - 1")
+    return n, _lib.SampleConfig(C.sizeof(_lib.SampleConfig), t, k, p, seed)
 
 
 def decoder_layer_keys(layer: int):
@@ -368,13 +422,17 @@ def resolve_caps(n: int, max_length=None, max_new_tokens=None):
 @dataclass
 class PoolItem:
     """One utterance waiting for a slot: clip ``clip`` of ``enc_out`` [B, T, 768] (a packed forward's output), of which ``rows`` rows
-    belong to its own reference batch; ``frames`` i32 [B] on the device."""
+    belong to its own reference batch; ``frames`` i32 [B] on the device.  In a pool that samples the item is hypothesis
+    ``hypothesis`` of utterance ``utterance`` (the random numbers' counter), ``greedy`` = it takes the argmax all the same."""
     key: int
     enc_out: torch.Tensor
     frames: torch.Tensor
     clip: int
     rows: int
     cap: int
+    utterance: int = 0
+    hypothesis: int = 0
+    greedy: bool = True
 
 
 class DecoderPool:
@@ -382,11 +440,16 @@ class DecoderPool:
     utterance.  Owns the workspace and the pinned poll block.  The host keeps an exact bound on every slot's position (the steps
     enqueued since its admission, at most cap - 2), so a step's launches are sized without reading the device; the device is looked at
     every ``poll_steps`` steps (8, as loco_decoder_generate does), when finished rows are collected and waiting ones admitted.
-    Single caller, one stream, as DecoderRuntime."""
+    Single caller, one stream, as DecoderRuntime.
+
+    ``sample`` (a _lib.SampleConfig, decoder.check_sample_args) makes it the sampling pool: items are admitted through
+    loco_decoder_pool_admit_samples -- the hypotheses of one utterance that fit the free slots together, the rest later -- and stepped
+    through loco_decoder_pool_step_sample; scores are the model's log P of the token each step appended."""
 
     def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False,
-                 return_scores: bool = False):
+                 return_scores: bool = False, sample=None):
         self.enc, self.lib = encoder, encoder._lib
+        self.sample = sample
         self.slots, self.T_cap, self.S_max = int(slots), int(T_cap), int(S_max)
         self.device = device
         self.poll_steps = int(poll_steps)
@@ -436,7 +499,48 @@ class DecoderPool:
         for r, it in zip(slot_ids, items):
             self.entries[r] = (it, self.steps)
 
+    def admit_samples(self, slot_ids, groups):
+        """``groups``: per clip its waiting hypotheses, equally many for every clip; the clips consecutive in ONE encoder output."""
+        first, copies = groups[0][0], len(groups[0])
+        assert all(len(g) == copies and it.enc_out is first.enc_out and it.clip == first.clip + i and it.utterance == g[0].utterance
+                   for i, g in enumerate(groups) for it in g)
+        n, flat = len(groups), [it for g in groups for it in g]
+        i32, u32 = lambda vs: (C.c_int32 * len(vs))(*vs), lambda vs: (C.c_uint32 * len(vs))(*vs)  # noqa: E731
+        out = first.enc_out
+        frames = first.frames[first.clip:] if first.frames is not None else None
+        _lib.check(self.lib.loco_decoder_pool_admit_samples(
+            self.enc._handle, *self._shape, n, copies, i32(slot_ids), _ptr(out[first.clip]), out.stride(0), i32([g[0].rows for g in groups]),
+            _ptr(frames), i32([g[0].cap for g in groups]), u32([g[0].utterance for g in groups]), u32([it.hypothesis for it in flat]),
+            i32([int(it.greedy) for it in flat]), self._ws(), self.workspace.numel(), self._stream()), "loco_decoder_pool_admit_samples")
+        for r, it in zip(slot_ids, flat):
+            self.entries[r] = (it, self.steps)
+
+    def _siblings(self, at):
+        """How many waiting items from ``at`` on are hypotheses of one utterance (one clip of one encoder output)."""
+        w, n = self.waiting, 1
+        while at + n < len(w) and w[at + n].enc_out is w[at].enc_out and w[at + n].clip == w[at].clip and w[at + n].utterance == w[at].utterance:
+            n += 1
+        return n
+
+    def _fill_samples(self):
+        free = [r for r in range(self.slots) if self.entries[r] is None]
+        while free and self.waiting:
+            head, whole = self.waiting[0], self._siblings(0)
+            copies = min(whole, len(free))
+            groups, taken = [self.waiting[:copies]], copies
+            # further clips of the same encoder output whose hypotheses are as many and fit as well: one call, one wait for the stream
+            while copies == whole and taken < len(self.waiting) and taken + copies <= len(free):
+                nxt = self.waiting[taken]
+                if nxt.enc_out is not head.enc_out or nxt.clip != head.clip + len(groups) or self._siblings(taken) != copies:
+                    break
+                groups.append(self.waiting[taken:taken + copies])
+                taken += copies
+            self.admit_samples(free[:taken], groups)
+            del self.waiting[:taken], free[:taken]
+
     def _fill(self):
+        if self.sample is not None:
+            return self._fill_samples()
         free = [r for r in range(self.slots) if self.entries[r] is None]
         while free and self.waiting:
             run = [self.waiting[0]]
@@ -452,8 +556,14 @@ class DecoderPool:
         max_pos = max(min(done, it.cap - 2) for it, done in live)
         return max_pos, max(it.rows for it, _ in live), max(it.cap - 1 - done for it, done in live)
 
-    def step(self, logits=None):
+    def step(self, logits=None, tokens=None):
         max_pos, max_frames, _ = self.bounds()
+        if self.sample is not None:  # ``tokens``: i32 [slots] on the device, the token every live slot appended (-100: none)
+            _lib.check(self.lib.loco_decoder_pool_step_sample(self.enc._handle, *self._shape, max_pos, max_frames, C.byref(self.sample), _ptr(logits),
+                                                              _ptr(tokens), self._ws(), self.workspace.numel(), self._stream()),
+                       "loco_decoder_pool_step_sample")
+            self.steps += 1
+            return
         _lib.check(self.lib.loco_decoder_pool_step(self.enc._handle, *self._shape, max_pos, max_frames, _ptr(logits), self._ws(), self.workspace.numel(),
                                                    self._stream()), "loco_decoder_pool_step")
         self.steps += 1
@@ -508,10 +618,13 @@ class DecoderPool:
         if self.return_logits:
             self._rounds.append((self.steps, lg))
         first = self.steps
+        drawn = self.sample is not None and self.return_scores
+        tok = torch.empty((k, self.slots), dtype=torch.int32, device=self.device) if drawn else None
         for j in range(k):
-            self.step(lg[j] if lg is not None else None)
+            self.step(lg[j] if lg is not None else None, *((tok[j],) if drawn else ()))
         if self.return_scores:  # the round's block in one launch: every row against its own argmax, the token the step appended
-            self._score_rounds.append((first, score_logits(self.lib, lg, None, k, self.slots, reduce=False)[0]))
+            # (a pool that samples: against the token it appended, on the raw logits -- the model's log P, not the warped distribution's)
+            self._score_rounds.append((first, score_logits(self.lib, lg, tok, k, self.slots, reduce=False)[0]))
         return self.collect()
 
     def drain(self):

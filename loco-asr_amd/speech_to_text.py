@@ -1,6 +1,7 @@
 """``SpeechT5ForSpeechToTextMI355X``: HuggingFace's speech-to-text model over the speech encoder (encoder.py) and, when decoder
 weights are loaded, the text decoder (decoder.py) -- ``forward(decoder_input_ids= / labels=)``, ``generate``, ``score``, ``align`` and
-their corpus forms ``generate_many`` / ``score_many`` / ``align_many``, which share one walk over the corpus (``corpus_packs``)."""
+their corpus forms ``generate_many`` / ``score_many`` / ``align_many``, which share one walk over the corpus (``corpus_packs``);
+``sample`` / ``sample_many`` draw n-best lists in ``generate_many``'s slot pool."""
 from __future__ import annotations
 
 import itertools
@@ -316,6 +317,19 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         extras = int(bool(return_logits)) + int(bool(return_scores))
         if total == 0:
             return ([],) * (1 + extras) if extras else []
+        results = self._decode_corpus(batches, caps, slots, pack, return_logits, return_scores)
+        out = [[results[k][0] for k in range(total)]]
+        if return_logits:
+            out.append([results[k][1] for k in range(total)])
+        if return_scores:
+            out.append([results[k][2] for k in range(total)])
+        return tuple(out) if extras else out[0]
+
+    def _decode_corpus(self, batches, caps, slots, pack, return_logits, return_scores, copies=1, sample=None, greedy_first=False, first_utterance=0):
+        """The walk ``generate_many`` and ``sample_many`` share over checked arguments: encode ``pack`` batches at a time, decode in one
+        pool.  {utterance * copies + hypothesis: [ids, logits or None, scores when asked for]}; ``sample`` (a _lib.SampleConfig) makes
+        the pool draw ``copies`` hypotheses per utterance, of which hypothesis 0 is the argmax path with ``greedy_first``."""
+        total = len(caps)
         enc = self.speecht5.encoder
         lib = enc._lib
         device = enc._device()
@@ -323,7 +337,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         if T_cap < 1:
             raise ValueError("input shorter than one encoder frame (400 samples)")
         pool = None
-        results, key, nxt = {}, 0, 0
+        results, u, nxt = {}, 0, 0
         batches = [b for b in batches if b["input_values"].shape[0]]
         with torch.cuda.device(device):
             while nxt < len(batches) or (pool is not None and pool.busy):
@@ -331,23 +345,104 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                     out, spans, frames, ticket = self._encode_pack(batches[nxt:nxt + int(pack)])
                     nxt += int(pack)
                     if pool is None:  # after the first forward: the handle exists and carries the decoder's weights
-                        pool = dec.DecoderPool(enc, min(int(slots), total), T_cap, max(caps), device,
-                                               return_logits=return_logits, return_scores=return_scores)
+                        pool = dec.DecoderPool(enc, min(int(slots), total * copies), T_cap, max(caps), device,
+                                               return_logits=return_logits, return_scores=return_scores, sample=sample)
                     items = []
                     for b0, nb, t in spans:
                         for c in range(b0, b0 + nb):
-                            items.append(dec.PoolItem(key=key, enc_out=out, frames=frames, clip=c, rows=t, cap=caps[key]))
-                            key += 1
+                            for h in range(copies):
+                                items.append(dec.PoolItem(key=u * copies + h, enc_out=out, frames=frames, clip=c, rows=t, cap=caps[u],
+                                                          utterance=first_utterance + u, hypothesis=h,
+                                                          greedy=sample is None or (bool(greedy_first) and h == 0)))
+                            u += 1
                     pool.submit(items)
                     continue
                 for k, *rest in pool.round():
                     results[k] = rest
-        out = [[results[k][0] for k in range(total)]]
-        if return_logits:
-            out.append([results[k][1] for k in range(total)])
-        if return_scores:
-            out.append([results[k][2] for k in range(total)])
-        return tuple(out) if extras else out[0]
+        return results
+
+    @torch.no_grad()
+    def sample_many(self, batches, num_return_sequences: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
+                    greedy_first: bool = False, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, pack: int = 8,
+                    return_logits: bool = False, return_scores: bool = False, first_utterance: int = 0):
+        """``num_return_sequences`` sampled transcripts of every utterance of a corpus -- an n-best list for ``score_many`` to rescore,
+        or for confidence by agreement.  ``batches``, ``max_length`` (an int or one per utterance), ``slots`` and ``pack`` are
+        ``generate_many``'s; the N hypotheses of an utterance are N rows of the same slot pool.  Each token is drawn on the device
+        (csrc/decoder_sample.hip): logits / ``temperature``, ``top_k`` (0 = off; ties at the threshold survive), ``top_p`` (1 = off;
+        HF's TopPLogitsWarper, equal logits kept or dropped together), then one draw from the softmax of what is kept.  The uniform
+        behind a draw is a Philox4x32-10 block keyed by ``seed`` with the counter (utterance, hypothesis, token index): a hypothesis
+        does not depend on the hypotheses decoded beside it, on ``slots`` or on the admission order, bit for bit.  The utterance index
+        is ``first_utterance`` + the utterance's position in the call.  ``seed=None`` draws a 63-bit seed from torch's default CPU
+        generator, so ``torch.manual_seed`` makes a call reproducible; the seed used is ``.seed`` of the result.
+        ``greedy_first=True``: hypothesis 0 is the argmax path, ``generate_many``'s transcript.
+
+        Returns ``hyps`` with ``hyps[u][h]`` a 1-D LongTensor (host), <s> ... </s> or the cap.  ``return_logits=True``: (hyps, logits)
+        with ``logits[u][h]`` [len - 1, vocab] on the device, the raw logits each token was drawn from; ``return_scores=True``: (hyps,
+        scores) with ``scores[u][h]`` [len - 1] on the device, the model's log P of every token (of the unwarped distribution); both:
+        (hyps, logits, scores)."""
+        self._require_decoder("sample_many()")
+        n, config = dec.check_sample_args(num_return_sequences, temperature, top_k, top_p, seed)
+        batches = list(batches)
+        sizes = [int(b["input_values"].shape[0]) for b in batches]
+        total = sum(sizes)
+        caps = dec.resolve_caps(total, max_length, max_new_tokens)
+        if int(pack) < 1:
+            raise ValueError("pack must be >= 1")
+        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
+        if not 1 <= int(slots) <= most:
+            raise ValueError(f"sample_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        if not 0 <= int(first_utterance) <= 2 ** 32 - 1 - total:
+            raise ValueError(f"sample_many: first_utterance = {first_utterance} leaves no room for {total} utterances below 2^32")
+        results = self._decode_corpus(batches, caps, slots, pack, return_logits, return_scores, copies=n, sample=config,
+                                      greedy_first=greedy_first, first_utterance=int(first_utterance)) if total else {}
+        out = []
+        for field in range(1 + int(bool(return_logits)) + int(bool(return_scores))):
+            src = field if field == 0 or return_logits else 2  # a round's result: [ids, logits or None, scores when asked for]
+            out.append([[results[u * n + h][src] for h in range(n)] for u in range(total)])
+        hyps = dec.SampledHypotheses(out[0])
+        hyps.seed = int(config.seed)
+        if len(out) == 1:
+            return hyps
+        res = dec.SampledResults([hyps] + out[1:])
+        res.seed = hyps.seed
+        return res
+
+    @torch.no_grad()
+    def sample(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, num_return_sequences: int = 1,
+               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None, greedy_first: bool = False,
+               max_length: Optional[int] = None, max_new_tokens: Optional[int] = None, slots: int = 64, return_scores: bool = False):
+        """``sample_many`` for one batch, in HF's ``num_return_sequences`` layout: a decoder.SampleOutput whose ``sequences`` are
+        LongTensor [B * N, S] on the inputs' device -- clip b's hypotheses in rows b * N .. b * N + N - 1, <pad> (1) after </s>, S the
+        longest row -- and whose ``seed`` is the seed used.  The rows are ``sample_many``'s hypotheses for the same seed (utterance
+        index = the clip's row in the batch): the same pool, the same kernel.  ``return_scores=True``: also ``token_logprobs``
+        [B * N, S - 1], exactly 0 at the <pad> columns, and ``sequence_logprobs`` [B * N], as decoder.GreedySearchOutput's."""
+        self._require_decoder("sample()")
+        if attention_mask is None:
+            attention_mask = torch.ones(input_values.shape, dtype=torch.int32, device=input_values.device)
+        res = self.sample_many([dict(input_values=input_values, attention_mask=attention_mask)], num_return_sequences=num_return_sequences,
+                               temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, greedy_first=greedy_first,
+                               max_length=dec.resolve_max_length(max_length, max_new_tokens), slots=slots, pack=1, return_logits=bool(return_scores))
+        hyps, logits = res if return_scores else (res, None)
+        rows = [h for per in hyps for h in per]
+        device = input_values.device
+        S = max((int(r.shape[0]) for r in rows), default=1)
+        seqs = torch.full((len(rows), S), dec.PAD_TOKEN_ID, dtype=torch.long)
+        for i, r in enumerate(rows):
+            seqs[i, :r.shape[0]] = r
+        out = dec.SampleOutput(sequences=seqs.to(device), seed=res.seed)
+        if return_scores and rows and S > 1:
+            # one scoring launch over [B * N, S - 1, V]: the rows' own step logits, the <pad> columns not counted
+            flat = [l for per in logits for l in per]
+            V = self.speecht5.encoder._decoder_vocab
+            block = torch.zeros((len(rows), S - 1, V), dtype=torch.float32, device=flat[0].device)
+            targets = torch.full((len(rows), S - 1), dec.IGNORE_INDEX, dtype=torch.int32)
+            for i, (r, l) in enumerate(zip(rows, flat)):
+                block[i, :l.shape[0]] = l
+                targets[i, :r.shape[0] - 1] = r[1:].to(torch.int32)
+            with torch.cuda.device(block.device):
+                lp, seq, _, _, _ = dec.score_logits(self.speecht5.encoder._lib, block, targets.to(block.device).contiguous(), len(rows), S - 1)
+            out.token_logprobs, out.sequence_logprobs = lp, seq
+        return out
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):

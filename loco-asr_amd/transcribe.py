@@ -6,7 +6,10 @@ end; the <pad> columns behind it get none): ``align`` / ``align_many`` on the ge
 
 Utterances go through the model in the reference's pairs (batch_size 2, corpus order), encoder + ``generate`` per pair.  With
 ``--slots N`` the pairs are encoded ``--pack G`` at a time and decoded in a pool of N decoder rows in which a finished row hands its
-slot to the next utterance (``generate_many``); the lines written are the same.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
+slot to the next utterance (``generate_many``); the lines written are the same.  ``--nbest N`` (with ``--slots``) adds "nbest": N
+sampled transcripts of the utterance (``sample_many``: ``--temperature``, ``--top-k``, ``--top-p``, ``--seed``), each {"ids", "logprob",
+"avg_logprob"} (and "text"), sorted by "logprob", best first.  The line's other fields are then hypothesis 0: the greedy transcript only
+with ``--greedy-first``, a sampled one otherwise.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
 ``--synthetic N`` seeded clips; weights: ``--pretrained DIR`` (a HuggingFace speech-to-text checkpoint directory with the decoder)
 or ``--random-init`` (the deterministic synthetic weights).
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 from . import synth
-from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID
+from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_sample_args
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X
 
 
@@ -129,6 +132,14 @@ def main(argv=None):
     ap.add_argument("--max-length", type=int, default=100, help="total tokens per utterance, start token included (the reference's notebooks: 100)")
     ap.add_argument("--slots", type=int, default=0, help="decode in a pool of N rows with finished rows refilled (1 .. 64); 0 = one generate call per batch")
     ap.add_argument("--pack", type=int, default=8, metavar="G", help="with --slots: batches per packed encoder forward")
+    ap.add_argument("--nbest", type=int, default=0, metavar="N", help="with --slots: also write \"nbest\", N sampled transcripts sorted by logprob (1 .. 64); the "
+                    "line's other fields are then hypothesis 0, which is the greedy transcript ONLY with --greedy-first and a sampled one otherwise")
+    ap.add_argument("--temperature", type=float, default=1.0, help="with --nbest: logits are divided by it before the draw")
+    ap.add_argument("--top-k", type=int, default=0, help="with --nbest: draw among the k most likely tokens (0 = off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="with --nbest: draw within the smallest set of tokens of probability mass >= p (1 = off)")
+    ap.add_argument("--seed", type=int, default=None, help="with --nbest: the random numbers' seed (default: drawn from torch's generator)")
+    ap.add_argument("--greedy-first", action="store_true", help="with --nbest: hypothesis 0 is the greedy transcript, so the line's own fields are what they "
+                    "are without --nbest")
     ap.add_argument("--scores", action="store_true", help="also write \"logprob\" (sum over the generated tokens) and \"avg_logprob\" (per generated token)")
     ap.add_argument("--timestamps", action="store_true", help="also write \"token_times\": [start_s, end_s] of every generated token (cross-attention + DTW)")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
@@ -139,6 +150,15 @@ def main(argv=None):
         raise SystemExit("--batch-size must be >= 1")
     if args.slots < 0 or args.pack < 1:
         raise SystemExit("--slots must be >= 0 and --pack >= 1")
+    if args.nbest and not args.slots:
+        raise SystemExit("--nbest needs --slots: the hypotheses are rows of the decoder pool")
+    if args.nbest < 0:
+        raise SystemExit("--nbest must be >= 0")
+    if args.nbest:  # refused here, before a model is built; one seed for the whole corpus, whatever the windows
+        try:
+            args.seed = int(check_sample_args(args.nbest, args.temperature, args.top_k, args.top_p, args.seed)[1].seed)
+        except ValueError as e:
+            raise SystemExit(f"--nbest / --temperature / --top-k / --top-p / --seed: {e}")
     items = gather_items(args)
     from .feature_extractor import SpeechT5FeatureExtractorMI355X
     processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
@@ -146,8 +166,20 @@ def main(argv=None):
     tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    def write(chunk, ids, scores=None, times=None):
-        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated); ``times``: per row the pairs."""
+    def nbest_records(hyps, sums):
+        """One utterance's "nbest": its hypotheses by log-probability, best first, ties by hypothesis index."""
+        recs = []
+        for h in sorted(range(len(hyps)), key=lambda h: (-sums[h], h)):
+            row = hyps[h].tolist()
+            rec = {"ids": row, "logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)}
+            if tok is not None:
+                rec["text"] = tok.decode(strip_special(row))
+            recs.append(rec)
+        return recs
+
+    def write(chunk, ids, scores=None, times=None, nbest=None):
+        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated); ``times``: per row the pairs;
+        ``nbest``: per row the records of its hypotheses."""
         for i, ((uid, _, _), row) in enumerate(zip(chunk, ids)):
             rec = {"id": uid, "token_ids": row}
             if tok is not None:
@@ -158,6 +190,8 @@ def main(argv=None):
                 rec["avg_logprob"] = total / n
             if times is not None:
                 rec["token_times"] = times[i]
+            if nbest is not None:
+                rec["nbest"] = nbest[i]
             fh.write(json.dumps(rec) + "\n")
 
     try:
@@ -167,7 +201,20 @@ def main(argv=None):
             for w0 in range(0, len(starts), window):
                 chunks = [items[b0:b0 + args.batch_size] for b0 in starts[w0:w0 + window]]
                 feats = [load_batch(chunk, b0, processor, device) for chunk, b0 in zip(chunks, starts[w0:w0 + window])]
-                rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
+                lists = None
+                if args.nbest:  # hypothesis 0 takes generate_many's place; every hypothesis is scored
+                    hyps, hyp_scores = model.sample_many(feats, num_return_sequences=args.nbest, temperature=args.temperature, top_k=args.top_k,
+                                                         top_p=args.top_p, seed=args.seed, greedy_first=args.greedy_first, max_length=args.max_length,
+                                                         slots=args.slots, pack=args.pack, return_scores=True, first_utterance=starts[w0])
+                    flat = torch.cat([t for per in hyp_scores for t in per]).cpu().tolist()  # one read-back per window
+                    ends = np.cumsum([t.shape[0] for per in hyp_scores for t in per]).tolist()
+                    hyp_sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
+                    lists = [nbest_records(per, hyp_sums[u * args.nbest:(u + 1) * args.nbest]) for u, per in enumerate(hyps)]
+                    rows = [per[0] for per in hyps]
+                    if args.scores:
+                        rows = (rows, [per[0] for per in hyp_scores])
+                else:
+                    rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
                 sums = None
                 if args.scores:
                     rows, per_token = rows
@@ -187,7 +234,10 @@ def main(argv=None):
                     times = None
                     if stamps is not None:
                         times, stamps = stamps[:len(chunk)], stamps[len(chunk):]
-                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times)
+                    best = None
+                    if lists is not None:
+                        best, lists = lists[:len(chunk)], lists[len(chunk):]
+                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times, best)
         else:
             for b0 in starts:
                 chunk = items[b0:b0 + args.batch_size]
