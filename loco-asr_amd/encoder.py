@@ -217,8 +217,10 @@ class ForwardTicket:
                 slot.ticket = None
 
 
-class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
-    """Drop-in for ``SpeechT5ForSpeechToText(...).speecht5.encoder`` (HF modeling_speecht5.py:1325-1358)."""
+class _EncoderBase(nn.Module):
+    """Everything a forward through the library needs whatever feeds the 12 layers: the handle and the weights' way to it, the slots
+    of forwards in flight, ``forward`` and ``forward_async``.  A front end -- speech below, text in text_encoder.py -- passes its
+    prenet module to ``__init__`` and implements the hooks at the end of this class; it overrides none of the above."""
 
     # "f16x3" (default): GEMMs and attention products as three fp16 MFMAs per fp32-class product (hi/lo operand split,
     # fp32 accumulate) -- ~1e-6 relative L2 of an fp64 evaluation end to end, 2.4x the speed of "f32";
@@ -229,37 +231,35 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
     # instructions in the GEMMs.
     PRECISIONS = {"f32": 0, "f16x3": 1, "f16x2": 2}
 
-    def __init__(self, layers: int = LAYERS, precision: str = "f16x3"):
+    def __init__(self, prenet: _WeightHolder, layers: int, precision: str, streams: int):
         super().__init__()
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}")
         self.precision = precision
         self._lib = _lib.load()  # raises when the HIP library is missing: no fallback
-        ref = _Ref()
-        self.prenet = SpeechT5SpeechEncoderPrenetMI355X(ref)
-        self.wrapped_encoder = SpeechT5EncoderMI355X(ref, layers)
-        ref.obj = self
+        self.prenet = prenet
+        self.wrapped_encoder = SpeechT5EncoderMI355X(prenet._owner_ref, layers)
+        prenet._owner_ref.obj = self
         self.num_layers = layers
         self._handle = None
         self._handle_device = None
         self._weights_dirty = True
         self._workspace = None
-        self._sin_rows = 0
-        self._taps = None
         # further (key prefix, module) pairs whose tensors go to the same handle: the model's decoder halves (decoder.py); empty for an
         # encoder-only model, which then loads exactly what it always has
         self._extra_weights = []
         self._decoder_layers = 0
         self._decoder_vocab = 0
-        # large batches run as two half-batches on two HIP streams (bit-identical, ~2 % faster: include/loco_asr.h,
-        # loco_set_streams); set to 1 to keep everything on the caller's stream
-        self.streams = 2
+        # speech: large batches run as two half-batches on two HIP streams (bit-identical, ~2 % faster: include/loco_asr.h,
+        # loco_set_streams); 1 keeps everything on the caller's stream (the library runs text that way whatever is set)
+        self.streams = streams
         # Numeric range of precision "f16x3" (include/loco_asr.h): "fp32" = a batch whose activations leave the range the fp16
         # planes represent is run again on the library's exact-fp32 MFMA kernels (the default: a caller never sees NaNs or a
         # silently degraded embedding); "raise" = LocoError instead; "off" = no check and no host synchronisation (the
         # forward stays fully asynchronous; loco_forward_status can still be queried through range_report()).
         self.range_policy = "fp32"
         self.last_range_fallback = False
+        self.last_frames = None
         # forwards in flight (forward_async): slots of (stream, workspace, status block), used round-robin
         self._slots = []
         self._next_slot = 0
@@ -298,33 +298,28 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             self._handle = C.c_void_p(h)
             self._handle_device = device
             self._weights_dirty = True
-            self._sin_rows = 0
 
-    def _sync_weights(self, device: torch.device, min_sin_rows: int):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if self._weights_dirty:
+    def _sync_weights(self, device: torch.device, min_rows: int):
+        dirty = self._weights_dirty
+        if dirty:
             self.drain()  # forwards still in flight on the slots' streams read the planes that are about to be rebuilt
-            for prefix, mod in [("prenet.", self.prenet), ("wrapped_encoder.", self.wrapped_encoder)] + list(self._extra_weights):
+
+        def put(key, t, what="load_state_dict"):
+            t = t.detach()
+            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(device=device, dtype=torch.float32).contiguous()
+            if t.dim() == 0:
+                t = t.reshape(1)
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            _lib.check(self._lib.loco_set_weight(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()), what)
+
+        if dirty:
+            for prefix, mod in self._weight_sources():
                 for name, p in mod.state_dict().items():
-                    t = p.detach()
-                    if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-                        t = t.to(device=device, dtype=torch.float32).contiguous()
-                    shape = (C.c_int64 * t.dim())(*t.shape)
-                    _lib.check(self._lib.loco_set_weight(self._handle, (prefix + name).encode(), C.c_void_p(t.data_ptr()),
-                                                         shape, t.dim()), "load_state_dict")
-            self._sin_rows = 0
-        if self._sin_rows < min_sin_rows:
-            rows = max(MAX_SPEECH_POSITIONS + PAD_TOKEN_ID + 1 + 2, min_sin_rows + 2)
-            tab = sinusoid_table(rows).contiguous()
-            shape = (C.c_int64 * 2)(rows, HIDDEN)
-            _lib.check(self._lib.loco_set_weight(self._handle, b"prenet.pos_sinusoidal_embed.weights",
-                                                 C.c_void_p(tab.data_ptr()), shape, 2), "sinusoid table")
-            self._sin_rows = rows
-        if self._weights_dirty and self._extra_weights:
-            tab = sinusoid_table(MAX_TEXT_POSITIONS + PAD_TOKEN_ID + 1).contiguous()  # HF's decoder table, bit for bit (452 rows)
-            _lib.check(self._lib.loco_set_weight(self._handle, b"decoder.prenet.embed_positions.weights", C.c_void_p(tab.data_ptr()),
-                                                 (C.c_int64 * 2)(tab.shape[0], HIDDEN), 2), "decoder position table")
-        if self._weights_dirty:
+                    put(prefix + name, p)
+        self._load_tables(put, dirty, min_rows)
+        if dirty:
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             _lib.check(self._lib.loco_finalize_weights(self._handle, stream), "finalize_weights")
             self._weights_dirty = False
 
@@ -357,18 +352,9 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             i += 1
         return out
 
-    def _forward_call(self, args, stream):
-        """loco_forward under the module's range policy (include/loco_asr.h, 'numeric range of precision mode f16x3')."""
-        self.last_range_fallback = False
-        if self.range_policy == "off":
-            _lib.check(self._lib.loco_forward(self._handle, *args, stream), "loco_forward")
-            return
-        if self.range_policy not in ("fp32", "raise"):
-            raise ValueError("range_policy must be 'fp32', 'raise' or 'off'")
-        _lib.check(self._lib.loco_set_range_policy(self._handle, 1 if self.range_policy == "fp32" else 0), "set_range_policy")
-        used = C.c_int32(0)
-        _lib.check(self._lib.loco_forward_checked(self._handle, *args, stream, C.byref(used)), "loco_forward")
-        self.last_range_fallback = bool(used.value)
+    def workspace_bytes(self, batch: int, length: int) -> int:
+        self._ensure_handle(self._device())
+        return self._workspace_need(batch, length)
 
     # -- several forwards in flight ----------------------------------------------------------------------------
     def set_inflight(self, k: int):
@@ -393,16 +379,15 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             if slot.ticket is not None:
                 slot.ticket.settle()
 
-    def reserve_workspace(self, batch: int, samples: int):
-        """Size the in-flight slots' workspaces for a [batch, samples] problem at their next (re)allocation: a caller that knows
+    def reserve_workspace(self, batch: int, length: int):
+        """Size the in-flight slots' workspaces for a [batch, length] problem at their next (re)allocation: a caller that knows
         its largest batch (extract.py --pack: the longest pack of a sorted window) avoids growing a multi-GB workspace step by
         step -- every step is a hipMalloc of the new size, and hipFree of the old one synchronises the device."""
-        self._ensure_handle(self._device())
-        self._workspace_floor = max(self._workspace_floor, int(self._lib.loco_workspace_bytes(self._handle, batch, samples)))
+        self._workspace_floor = max(self._workspace_floor, self.workspace_bytes(batch, length))
 
     def _enqueue(self, slot, x, m, out, frames, precision, pack=None, hidden=None):
-        B, L = x.shape
-        need = int(self._lib.loco_workspace_bytes(self._handle, B, L))
+        """One forward on ``slot`` (``_submit``, and the fp32 re-run of its ticket): grow the slot's workspace, then the front end's call."""
+        need = self._workspace_need(*x.shape)
         if slot.workspace is None or slot.workspace.numel() < need:
             t0 = time.perf_counter()
             slot.workspace = None
@@ -411,50 +396,35 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             if self.submit_profile is not None:
                 self.submit_profile["workspace (re)allocations"] = self.submit_profile.get("workspace (re)allocations", 0.0) + 1.0
                 self.submit_profile["workspace allocation, s"] = self.submit_profile.get("workspace allocation, s", 0.0) + time.perf_counter() - t0
-        mp = C.c_void_p(m.data_ptr()) if m is not None else None
-        if pack is None:
-            _lib.check(self._lib.loco_forward_async(
-                self._handle, self.PRECISIONS[precision], C.c_void_p(x.data_ptr()), mp, B, L, C.c_void_p(out.data_ptr()),
-                C.c_void_p(frames.data_ptr()), None, C.c_void_p(slot.workspace.data_ptr()), slot.workspace.numel(),
-                C.c_void_p(slot.stream.cuda_stream), C.c_void_p(slot.status.data_ptr())), "loco_forward_async")
-        else:
-            vl = (C.c_int64 * B)(*pack.valid_len) if pack.valid_len is not None else None
-            hs_ptrs = (C.c_void_p * len(hidden))(*[t.data_ptr() for t in hidden]) if hidden is not None else None
-            _lib.check(self._lib.loco_forward_packed(
-                self._handle, self.PRECISIONS[precision], C.c_void_p(x.data_ptr()), mp, vl, B, L, (C.c_int64 * B)(*pack.pad_len),
-                C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs, C.c_void_p(slot.workspace.data_ptr()),
-                slot.workspace.numel(), C.c_void_p(slot.stream.cuda_stream), C.c_void_p(slot.status.data_ptr())), "loco_forward_packed")
+        self._launch(slot, x, m, out, frames, precision, pack, hidden)
+
+    def _begin(self, device: torch.device, why: str = ""):
+        """What every forward starts with: inference only, a handle on the inputs' device, the parameters there too."""
+        if self.training:
+            raise RuntimeError(f"the MI355X encoder path is inference-only{why}; call .eval()")
+        self._ensure_handle(device)
+        if self._device() != device:
+            raise RuntimeError(f"module parameters are on {self._device()} but input_values on {device}")
+
+    def _begin_async(self, device: torch.device):
+        self._begin(device)
+        if self._weights_dirty:
+            self.drain()  # re-finalising overwrites the weight planes in place: nothing may be reading them
+        if not self._slots:
+            self.set_inflight(2)
 
     @torch.no_grad()
     def forward_async(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **kwargs) -> ForwardTicket:
         """Enqueue one forward on the next slot and return its ticket without waiting; ``ticket.result()`` is the
         BaseModelOutput.  Inputs are read after everything already queued on the CURRENT stream (the H2D copies that made
         them); the slot's previous forward, if still unresolved, is resolved first."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
-        if input_values.dim() != 2:
-            raise ValueError(f"input_values must be [batch, samples], got {tuple(input_values.shape)}")
-        device = input_values.device
-        self._ensure_handle(device)
-        if self._device() != device:
-            raise RuntimeError(f"module parameters are on {self._device()} but input_values on {device}")
-        if self._weights_dirty:
-            self.drain()  # re-finalising overwrites the weight planes in place: nothing may be reading them
-        if not self._slots:
-            self.set_inflight(2)
-        x = input_values
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.to(torch.float32).contiguous()
-        B, L = x.shape
-        T = int(self._lib.loco_output_frames(L))
-        if T < 1:
-            raise ValueError(f"input of {L} samples is shorter than one encoder frame (400 samples)")
-        m = None
-        if attention_mask is not None:
-            if attention_mask.shape != x.shape:
-                raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not match input_values {tuple(x.shape)}")
-            m = attention_mask.to(device=device, dtype=torch.int32).contiguous()
-        return self._submit(x, m, T)
+        self._begin_async(input_values.device)
+        return self._submit(*self._prepare(input_values, attention_mask))
+
+    def forward_packed(self, batches=None, **kwargs):
+        """``forward_packed_async(...).result()``: list of per-batch outputs (speech, ``output_hidden_states=True``: each with the 13
+        hidden states of its batch, HF modeling_speecht5.py:1287-1313; keeps the pack on one stream)."""
+        return self.forward_packed_async(batches, **kwargs).result()
 
     def _submit(self, x, m, T, pack=None, hidden_states=False):
         """Enqueue one (plain or packed) forward on the next slot.  ``out`` / ``frames`` are allocated on the CALLER's current
@@ -500,6 +470,176 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
                            ("workspace + enqueue (C ABI)", t3 - t2), ("forwards", 1.0)):
                 prof[k_] = prof.get(k_, 0.0) + v_
         return ticket
+
+    # -- forward -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
+                return_dict: Optional[bool] = None, **kwargs):
+        """HF's SpeechT5Encoder call.  ``output_attentions=True`` also returns ``attentions``: one fp32 [B, 12, T, T] tensor per
+        layer (softmax over the valid keys, masked keys exactly 0; HF modeling_speecht5.py:930-955), formed by a separate kernel
+        after each layer's attention launch -- ``layers * B * 12 * T^2 * 4`` bytes on the input's device (12 layers of 30 s x 8:
+        10.3 GB); a range fallback re-run overwrites them with its own.  ``return_dict=False`` returns (last_hidden_state,
+        hidden_states, attentions) without the Nones."""
+        device = input_values.device
+        self._begin(device, " (the reference calls it under model.eval() + torch.no_grad())")
+        if self.range_policy not in ("fp32", "raise", "off"):
+            raise ValueError("range_policy must be 'fp32', 'raise' or 'off'")
+        x, m, T = self._prepare(input_values, attention_mask)
+        B, L = x.shape
+        with torch.cuda.device(device):
+            self._sync_weights(device, T + 2)
+            _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS[self.precision]), "set_precision")
+            _lib.check(self._lib.loco_set_streams(self._handle, int(self.streams)), "set_streams")
+            need = self._workspace_need(B, L)
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
+                self._workspace = None
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+            out = torch.empty((B, T, HIDDEN), dtype=torch.float32, device=device)
+            frames = torch.empty((B,), dtype=torch.int32, device=device)
+            hs, hs_ptrs = None, None
+            if output_hidden_states:
+                hs = [torch.empty_like(out) for _ in range(self.num_layers + 1)]
+                hs_ptrs = (C.c_void_p * (self.num_layers + 1))(*[t.data_ptr() for t in hs])
+            attn = None
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            try:
+                if output_attentions:
+                    attn = bind_attention_outputs(self._lib, self._handle, self.num_layers, B, T, device)
+                self.last_range_fallback = False
+                self._forward_call((C.c_void_p(x.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, L,
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs,
+                                    C.c_void_p(self._workspace.data_ptr()), self._workspace.numel()), stream)
+            finally:
+                if attn is not None:
+                    _lib.check(self._lib.loco_set_attention_outputs(self._handle, None, 0))
+        self.last_frames = frames
+        hidden = tuple(hs) if hs is not None else None
+        if return_dict is False:
+            return tuple(v for v in (out, hidden, attn) if v is not None)
+        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=attn)
+
+    # -- what a front end supplies -----------------------------------------------------------------------------
+    def _weight_sources(self):
+        """[(key prefix, module)]: every tensor of each module's state_dict goes to the handle under prefix + its name."""
+        raise NotImplementedError
+
+    def _load_tables(self, put, dirty: bool, min_rows: int):
+        """``put(key, tensor)`` the tables that are no parameters: all of them when ``dirty`` (the other weights have just been
+        loaded and are about to be finalised), otherwise only one that has to grow to ``min_rows`` rows."""
+        raise NotImplementedError
+
+    def _prepare(self, input_values, attention_mask):
+        """Check the inputs of one forward; returns (x [B, L] as the library reads it, i32 mask [B, L] or None, output frames T)."""
+        raise NotImplementedError
+
+    def _workspace_need(self, B: int, L: int) -> int:
+        raise NotImplementedError
+
+    def _launch(self, slot, x, m, out, frames, precision, pack, hidden):
+        """The asynchronous C call alone, on the slot's stream, workspace and status block."""
+        raise NotImplementedError
+
+    def _forward_call(self, args, stream):
+        """The synchronous C call on ``args`` (input, mask, B, L, out, frames, hidden states, workspace, its size) under
+        ``range_policy``, which ``forward`` has validated; sets ``last_range_fallback`` when it ran the batch again in fp32."""
+        raise NotImplementedError
+
+
+class SpeechT5EncoderWithSpeechPrenetMI355X(_EncoderBase):
+    """Drop-in for ``SpeechT5ForSpeechToText(...).speecht5.encoder`` (HF modeling_speecht5.py:1325-1358)."""
+
+    def __init__(self, layers: int = LAYERS, precision: str = "f16x3"):
+        super().__init__(SpeechT5SpeechEncoderPrenetMI355X(_Ref()), layers, precision, streams=2)
+        self._sin_rows = 0
+        self._stage_taps = None  # the dict ``forward(stage_taps=)`` is filling, for the length of that call
+
+    def _weight_sources(self):
+        return [("prenet.", self.prenet), ("wrapped_encoder.", self.wrapped_encoder)] + list(self._extra_weights)
+
+    def _load_tables(self, put, dirty, min_rows):
+        if dirty:
+            self._sin_rows = 0
+        if self._sin_rows < min_rows:
+            rows = max(MAX_SPEECH_POSITIONS + PAD_TOKEN_ID + 1 + 2, min_rows + 2)
+            put("prenet.pos_sinusoidal_embed.weights", sinusoid_table(rows), "sinusoid table")
+            self._sin_rows = rows
+        if dirty and self._extra_weights:  # HF's decoder table, bit for bit (452 rows)
+            put("decoder.prenet.embed_positions.weights", sinusoid_table(MAX_TEXT_POSITIONS + PAD_TOKEN_ID + 1), "decoder position table")
+
+    def _prepare(self, input_values, attention_mask):
+        if input_values.dim() != 2:
+            raise ValueError(f"input_values must be [batch, samples], got {tuple(input_values.shape)}")
+        x = input_values
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.to(torch.float32).contiguous()
+        T = int(self._lib.loco_output_frames(x.shape[1]))
+        if T < 1:
+            raise ValueError(f"input of {x.shape[1]} samples is shorter than one encoder frame (400 samples)")
+        m = None
+        if attention_mask is not None:
+            if attention_mask.shape != x.shape:
+                raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not match input_values {tuple(x.shape)}")
+            m = attention_mask.to(device=x.device, dtype=torch.int32).contiguous()
+        return x, m, T
+
+    def _workspace_need(self, B, L):
+        return int(self._lib.loco_workspace_bytes(self._handle, B, L))
+
+    def _launch(self, slot, x, m, out, frames, precision, pack, hidden):
+        B, L = x.shape
+        mp = C.c_void_p(m.data_ptr()) if m is not None else None
+        if pack is None:
+            _lib.check(self._lib.loco_forward_async(
+                self._handle, self.PRECISIONS[precision], C.c_void_p(x.data_ptr()), mp, B, L, C.c_void_p(out.data_ptr()),
+                C.c_void_p(frames.data_ptr()), None, C.c_void_p(slot.workspace.data_ptr()), slot.workspace.numel(),
+                C.c_void_p(slot.stream.cuda_stream), C.c_void_p(slot.status.data_ptr())), "loco_forward_async")
+        else:
+            vl = (C.c_int64 * B)(*pack.valid_len) if pack.valid_len is not None else None
+            hs_ptrs = (C.c_void_p * len(hidden))(*[t.data_ptr() for t in hidden]) if hidden is not None else None
+            _lib.check(self._lib.loco_forward_packed(
+                self._handle, self.PRECISIONS[precision], C.c_void_p(x.data_ptr()), mp, vl, B, L, (C.c_int64 * B)(*pack.pad_len),
+                C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs, C.c_void_p(slot.workspace.data_ptr()),
+                slot.workspace.numel(), C.c_void_p(slot.stream.cuda_stream), C.c_void_p(slot.status.data_ptr())), "loco_forward_packed")
+
+    def _forward_call(self, args, stream):
+        """loco_forward under the module's range policy (include/loco_asr.h, 'numeric range of precision mode f16x3'), with the
+        stage taps of ``forward(stage_taps=)`` bound for its length."""
+        taps = None
+        if self._stage_taps is not None:
+            B, T, dev = args[2], int(self._lib.loco_output_frames(args[3])), self._handle_device
+            taps = dict(conv_stack=torch.empty((B, T, CONV_DIM), dtype=torch.float32, device=dev),
+                        feature_projection=torch.empty((B, T, HIDDEN), dtype=torch.float32, device=dev),
+                        prenet=torch.empty((B, T, HIDDEN), dtype=torch.float32, device=dev))
+            _lib.check(self._lib.loco_set_taps(self._handle, taps["conv_stack"].data_ptr(),
+                                               taps["feature_projection"].data_ptr(), taps["prenet"].data_ptr()))
+        try:
+            if self.range_policy == "off":
+                _lib.check(self._lib.loco_forward(self._handle, *args, stream), "loco_forward")
+            else:
+                _lib.check(self._lib.loco_set_range_policy(self._handle, 1 if self.range_policy == "fp32" else 0), "set_range_policy")
+                used = C.c_int32(0)
+                _lib.check(self._lib.loco_forward_checked(self._handle, *args, stream, C.byref(used)), "loco_forward")
+                self.last_range_fallback = bool(used.value)
+        finally:
+            if taps is not None:
+                _lib.check(self._lib.loco_set_taps(self._handle, None, None, None))
+        if taps is not None:
+            self._stage_taps.update(taps)
+
+    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
+                return_dict: Optional[bool] = None, stage_taps: Optional[dict] = None, **kwargs):
+        """The shared forward; ``stage_taps``, a dict, is filled with the conv stack's output [B, T, 512], the feature projection and
+        the prenet output [B, T, 768] and ``frames``."""
+        self._stage_taps = stage_taps
+        try:
+            res = super().forward(input_values, attention_mask, output_attentions, output_hidden_states, return_dict)
+        finally:
+            self._stage_taps = None
+        if stage_taps is not None:
+            stage_taps["frames"] = self.last_frames
+        return res
 
     # -- packed forward: several reference batches in one launch sequence (include/loco_asr.h, loco_forward_packed) ------------
     def pack_batches(self, batches, device=None) -> Pack:
@@ -557,14 +697,8 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
         view into the pack's output) is what ``forward`` returns for that batch alone up to the fp32 summation order of the GEMMs
         (<= 5e-6 relative L2).  The batches are NOT merged: GroupNorm statistics, the positional conv's zero padding, sinusoid
         positions and the key mask all follow each clip's own batch (include/loco_asr.h)."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
         device = self._device()
-        self._ensure_handle(device)
-        if self._weights_dirty:
-            self.drain()
-        if not self._slots:
-            self.set_inflight(2)
+        self._begin_async(device)
         pk = packed if packed is not None else self.pack_batches(batches, device)
         if pk.wav.device != device:
             raise RuntimeError(f"module parameters are on {device} but the pack on {pk.wav.device}")
@@ -575,86 +709,6 @@ class SpeechT5EncoderWithSpeechPrenetMI355X(nn.Module):
             raise ValueError(f"a pack holds at most {int(self._lib.loco_max_pack_clips())} clips")
         T = int(self._lib.loco_output_frames(pk.wav.shape[1]))
         return self._submit(pk.wav, pk.mask, T, pk, hidden_states=bool(output_hidden_states))
-
-    def forward_packed(self, batches=None, *, packed=None, output_hidden_states: bool = False):
-        """``forward_packed_async(...).result()``: list of per-batch outputs (``output_hidden_states=True``: each with the 13 hidden
-        states of its batch, HF modeling_speecht5.py:1287-1313; keeps the pack on one stream)."""
-        return self.forward_packed_async(batches, packed=packed, output_hidden_states=output_hidden_states).result()
-
-    def workspace_bytes(self, batch: int, samples: int) -> int:
-        self._ensure_handle(self._device())
-        return int(self._lib.loco_workspace_bytes(self._handle, batch, samples))
-
-    # -- forward -------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
-                return_dict: Optional[bool] = None, stage_taps: Optional[dict] = None, **kwargs):
-        """HF's SpeechT5Encoder call.  ``output_attentions=True`` also returns ``attentions``: one fp32 [B, 12, T, T] tensor per
-        layer (softmax over the valid keys, masked keys exactly 0; HF modeling_speecht5.py:930-955), formed by a separate kernel
-        after each layer's attention launch -- ``layers * B * 12 * T^2 * 4`` bytes on the input's device (12 layers of 30 s x 8:
-        10.3 GB).  ``return_dict=False`` returns (last_hidden_state, hidden_states, attentions) without the Nones."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only (the reference calls it under "
-                               "model.eval() + torch.no_grad()); call .eval()")
-        if input_values.dim() != 2:
-            raise ValueError(f"input_values must be [batch, samples], got {tuple(input_values.shape)}")
-        device = input_values.device
-        self._ensure_handle(device)
-        if self._device() != device:
-            raise RuntimeError(f"module parameters are on {self._device()} but input_values on {device}")
-        x = input_values
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.to(torch.float32).contiguous()
-        B, L = x.shape
-        T = int(self._lib.loco_output_frames(L))
-        if T < 1:
-            raise ValueError(f"input of {L} samples is shorter than one encoder frame (400 samples)")
-        m = None
-        if attention_mask is not None:
-            if attention_mask.shape != x.shape:
-                raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not match input_values {tuple(x.shape)}")
-            m = attention_mask.to(device=device, dtype=torch.int32).contiguous()
-        with torch.cuda.device(device):
-            self._sync_weights(device, T + 2)
-            _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS[self.precision]), "set_precision")
-            _lib.check(self._lib.loco_set_streams(self._handle, int(self.streams)), "set_streams")
-            need = int(self._lib.loco_workspace_bytes(self._handle, B, L))
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-                self._workspace = None
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            out = torch.empty((B, T, HIDDEN), dtype=torch.float32, device=device)
-            frames = torch.empty((B,), dtype=torch.int32, device=device)
-            hs, hs_ptrs = None, None
-            if output_hidden_states:
-                hs = [torch.empty_like(out) for _ in range(self.num_layers + 1)]
-                hs_ptrs = (C.c_void_p * (self.num_layers + 1))(*[t.data_ptr() for t in hs])
-            taps, attn = None, None
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            try:
-                if stage_taps is not None:
-                    taps = dict(conv_stack=torch.empty((B, T, CONV_DIM), dtype=torch.float32, device=device),
-                                feature_projection=torch.empty_like(out), prenet=torch.empty_like(out))
-                    _lib.check(self._lib.loco_set_taps(self._handle, taps["conv_stack"].data_ptr(),
-                                                       taps["feature_projection"].data_ptr(), taps["prenet"].data_ptr()))
-                if output_attentions:
-                    attn = bind_attention_outputs(self._lib, self._handle, self.num_layers, B, T, device)
-                self._forward_call((C.c_void_p(x.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, L,
-                                    C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs,
-                                    C.c_void_p(self._workspace.data_ptr()), self._workspace.numel()), stream)
-            finally:
-                if taps is not None:
-                    _lib.check(self._lib.loco_set_taps(self._handle, None, None, None))
-                if attn is not None:
-                    _lib.check(self._lib.loco_set_attention_outputs(self._handle, None, 0))
-        if stage_taps is not None:
-            stage_taps.update(taps)
-            stage_taps["frames"] = frames
-        self.last_frames = frames
-        hidden = tuple(hs) if hs is not None else None
-        if return_dict is False:
-            return tuple(v for v in (out, hidden, attn) if v is not None)
-        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=attn)
 
 
 def bind_attention_outputs(lib, handle, layers: int, B: int, T: int, device) -> tuple:

@@ -12,14 +12,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _lib
-from .encoder import (HIDDEN, LAYERS, BaseModelOutput, SpeechT5EncoderMI355X, SpeechT5EncoderWithSpeechPrenetMI355X,
-                      bind_attention_outputs)
+from .encoder import HIDDEN, LAYERS, Pack, _EncoderBase
 from .holders import _Ref, _WeightHolder
 from .speech_to_text import _SpeechT5Core
 
@@ -57,60 +55,29 @@ class SpeechT5TextEncoderPrenetMI355X(_WeightHolder):
         return sd
 
 
-class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X):
-    """``forward(input_values=ids [B,T], attention_mask=None, ...) -> BaseModelOutput`` like HF's class of the same name."""
+class SpeechT5EncoderWithTextPrenetMI355X(_EncoderBase):
+    """``forward(input_values=ids [B,T], attention_mask=None, ...) -> BaseModelOutput`` like HF's class of the same name: the text
+    front end of encoder.py's ``_EncoderBase``, which owns ``forward``, ``forward_async`` and everything they share with speech."""
 
     def __init__(self, layers: int = LAYERS, precision: str = "f16x3", vocab_size: int = VOCAB_SIZE,
                  max_text_positions: int = MAX_TEXT_POSITIONS):
-        nn.Module.__init__(self)
-        if precision not in self.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}")
-        self.precision = precision
-        self._lib = _lib.load()  # raises when the HIP library is missing: no fallback
-        ref = _Ref()
-        self.prenet = SpeechT5TextEncoderPrenetMI355X(ref, vocab_size)
-        self.wrapped_encoder = SpeechT5EncoderMI355X(ref, layers)
-        ref.obj = self
-        self.num_layers = layers
+        super().__init__(SpeechT5TextEncoderPrenetMI355X(_Ref(), vocab_size), layers, precision, streams=1)
         self.vocab_size = vocab_size
         self.max_text_positions = max_text_positions
-        self._handle = None
-        self._handle_device = None
-        self._weights_dirty = True
-        self._workspace = None
-        self._sin_rows = 0
-        self._taps = None
-        self.streams = 1
-        self.last_frames = None
-        self.range_policy = "fp32"
-        self.last_range_fallback = False
-        self._slots = []       # forwards in flight (forward_async), as in the speech encoder
-        self._next_slot = 0
-        self.eval()
 
-    def _sync_weights(self, device: torch.device, min_sin_rows: int = 0):
-        if not self._weights_dirty:
-            return
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    def _weight_sources(self):
+        return [("text_prenet.", self.prenet), ("wrapped_encoder.", self.wrapped_encoder)]
 
-        def put(key, t):
-            t = t.detach().to(device=device, dtype=torch.float32).contiguous()
-            if t.dim() == 0:
-                t = t.reshape(1)
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self._lib.loco_set_weight(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()), "load_state_dict")
+    def _load_tables(self, put, dirty, min_rows):
+        if dirty:
+            put("text_prenet.encode_positions.pe", scaled_positional_table(self.max_text_positions))
 
-        for name, p in self.prenet.state_dict().items():
-            put("text_prenet." + name, p)
-        put("text_prenet.encode_positions.pe", scaled_positional_table(self.max_text_positions))
-        for name, p in self.wrapped_encoder.state_dict().items():
-            put("wrapped_encoder." + name, p)
-        _lib.check(self._lib.loco_finalize_weights(self._handle, stream), "finalize_weights")
-        self._weights_dirty = False
+    def _prepare(self, input_values, attention_mask):
+        ids32, m = self._check_ids(input_values, attention_mask)
+        return ids32, m, ids32.shape[1]
 
-    def workspace_bytes(self, batch: int, tokens: int) -> int:
-        self._ensure_handle(self._device())
-        return int(self._lib.loco_text_workspace_bytes(self._handle, batch, tokens))
+    def _workspace_need(self, B, T):
+        return int(self._lib.loco_text_workspace_bytes(self._handle, B, T))
 
     def _check_ids(self, ids, attention_mask):
         if ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
@@ -132,35 +99,30 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
                 raise NotImplementedError("attention_mask must be right padding (ones then zeros), as the tokenizer produces it")
         return ids.to(torch.int32).contiguous(), m
 
-    # -- several batches of transcripts in flight (the reference's text loop is batch_size = 2 as well, …base…py:67-68,79-93) --------
-    def _enqueue(self, slot, ids32, m, out, frames, precision, pack=None, hidden=None):  # pack / hidden: unused (a text pack is an ordinary masked forward)
+    def _launch(self, slot, ids32, m, out, frames, precision, pack, hidden):  # pack / hidden: unused (a text pack is an ordinary masked forward)
         B, T = ids32.shape
-        need = int(self._lib.loco_text_workspace_bytes(self._handle, B, T))
-        if slot.workspace is None or slot.workspace.numel() < need:
-            slot.workspace = None
-            slot.workspace = torch.empty(need, dtype=torch.uint8, device=ids32.device)
         _lib.check(self._lib.loco_forward_text_async(
             self._handle, self.PRECISIONS[precision], C.c_void_p(ids32.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, T,
             C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), None, C.c_void_p(slot.workspace.data_ptr()), slot.workspace.numel(),
             C.c_void_p(slot.stream.cuda_stream), C.c_void_p(slot.status.data_ptr())), "loco_forward_text_async")
 
-    @torch.no_grad()
-    def forward_async(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **kwargs):
-        """Enqueue one text forward on the next slot; ``ticket.result()`` is the BaseModelOutput (see the speech encoder's forward_async)."""
-        from .encoder import ForwardTicket
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
-        device = input_values.device
-        self._ensure_handle(device)
-        if self._device() != device:
-            raise RuntimeError(f"module parameters are on {self._device()} but input_values on {device}")
-        if self._weights_dirty:
-            self.drain()
-        if not self._slots:
-            self.set_inflight(2)
-        ids32, m = self._check_ids(input_values, attention_mask)
-        return self._submit_text(ids32, m)
+    def _forward_call(self, args, stream):
+        """loco_forward_text under the module's range policy (include/loco_asr.h, 'numeric range of precision mode f16x3'): the
+        library has no checked text call, so the status is read here and the batch run again on the exact-fp32 kernels (the
+        re-run rewrites the bound attention buffers too)."""
+        _lib.check(self._lib.loco_forward_text(self._handle, *args, stream), "loco_forward_text")
+        if self.range_policy == "off" or self.precision == "f32":
+            return
+        torch.cuda.current_stream(self._handle_device).synchronize()
+        rc = self._lib.loco_forward_status(self._handle, None, 0)
+        if rc != 0:
+            if self.range_policy == "raise":
+                _lib.check(rc, "loco_forward_text")
+            _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS["f32"]), "set_precision")
+            _lib.check(self._lib.loco_forward_text(self._handle, *args, stream), "loco_forward_text")
+            self.last_range_fallback = True
 
+    # -- several batches of transcripts in one forward (the reference's text loop is batch_size = 2 as well, …base…py:67-68,79-93) ----
     @torch.no_grad()
     def forward_packed_async(self, batches=None, *, packed=None):
         """Several of the reference's text batches (…base…py:79-93: ids padded to the batch's longest transcript with <pad> = 1,
@@ -169,17 +131,10 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
         means here (no GroupNorm, no positional conv: the text prenet is row-wise, positions count from 0 in every row).  A batch
         given as a mapping with ``attention_mask`` (right padding) keeps that mask.  ``ticket.result()`` = one BaseModelOutput per
         batch, ``last_hidden_state`` [B_i, T_i, 768] equal to the batch's own forward up to the fp32 summation order of the GEMMs."""
-        from .encoder import Pack
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
         if not batches:
             raise ValueError("forward_packed: no batches")
         device = self._device()
-        self._ensure_handle(device)
-        if self._weights_dirty:
-            self.drain()
-        if not self._slots:
-            self.set_inflight(2)
+        self._begin_async(device)
         ids_l = [b["input_values"] if hasattr(b, "keys") else b for b in batches]
         msk_l = [b.get("attention_mask") if hasattr(b, "keys") else None for b in batches]
         B, T = sum(int(i.shape[0]) for i in ids_l), max(int(i.shape[1]) for i in ids_l)
@@ -192,96 +147,8 @@ class SpeechT5EncoderWithTextPrenetMI355X(SpeechT5EncoderWithSpeechPrenetMI355X)
             mask[b0:b0 + nb, :t] = 1 if mk is None else mk.to("cpu", torch.int32)
             spans.append((b0, nb, t))
             b0 += nb
-        ids32, m = self._check_ids(ids.to(device), mask.to(device))
-        return self._submit_text(ids32, m, Pack(wav=ids32, mask=m, valid_len=None, pad_len=[], spans=spans))
-
-    def forward_packed(self, batches=None, *, packed=None):
-        return self.forward_packed_async(batches).result()
-
-    def _submit_text(self, ids32, m, pack=None):
-        from .encoder import ForwardTicket
-        device = ids32.device
-        B, T = ids32.shape
-        slot = self._slots[self._next_slot]
-        self._next_slot = (self._next_slot + 1) % len(self._slots)
-        if slot.ticket is not None:
-            slot.ticket.settle()
-        with torch.cuda.device(device):
-            self._sync_weights(device)
-            cur = torch.cuda.current_stream(device)
-            # outputs come from the CALLER's stream (see the speech encoder's _submit): no record_stream duty for consumers
-            out = torch.empty((B, T, HIDDEN), dtype=torch.float32, device=device)
-            frames = torch.empty((B,), dtype=torch.int32, device=device)
-            slot.stream.wait_stream(cur)
-            with torch.cuda.stream(slot.stream):
-                for t_ in (ids32, m, out, frames):
-                    if t_ is not None:
-                        t_.record_stream(slot.stream)
-                ticket = ForwardTicket(self, slot, ids32, m, out, frames, self.precision, pack)
-                self._enqueue(slot, ids32, m, out, frames, self.precision)
-                ticket._done.record(slot.stream)
-        slot.ticket = ticket
-        return ticket
-
-    def forward(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
-                return_dict: Optional[bool] = None, **kwargs):
-        """HF's SpeechT5Encoder call on token ids.  ``output_attentions=True``: one fp32 [B, 12, T, T] tensor per layer, as the
-        speech encoder returns them (``layers * B * 12 * T^2 * 4`` bytes); a range fallback re-run overwrites them with its own."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only; call .eval()")
-        ids = input_values
-        device = ids.device
-        self._ensure_handle(device)
-        if self._device() != device:
-            raise RuntimeError(f"module parameters are on {self._device()} but input_values on {device}")
-        ids32, m = self._check_ids(ids, attention_mask)
-        B, T = ids32.shape
-        with torch.cuda.device(device):
-            self._sync_weights(device)
-            _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS[self.precision]), "set_precision")
-            need = int(self._lib.loco_text_workspace_bytes(self._handle, B, T))
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-                self._workspace = None
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            out = torch.empty((B, T, HIDDEN), dtype=torch.float32, device=device)
-            frames = torch.empty((B,), dtype=torch.int32, device=device)
-            hs, hs_ptrs = None, None
-            if output_hidden_states:
-                hs = [torch.empty_like(out) for _ in range(self.num_layers + 1)]
-                hs_ptrs = (C.c_void_p * (self.num_layers + 1))(*[t.data_ptr() for t in hs])
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            attn = bind_attention_outputs(self._lib, self._handle, self.num_layers, B, T, device) if output_attentions else None
-
-            def launch():
-                _lib.check(self._lib.loco_forward_text(self._handle, C.c_void_p(ids32.data_ptr()),
-                                                       C.c_void_p(m.data_ptr()) if m is not None else None, B, T,
-                                                       C.c_void_p(out.data_ptr()), C.c_void_p(frames.data_ptr()), hs_ptrs,
-                                                       C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), stream),
-                           "loco_forward_text")
-
-            try:
-                launch()
-                # numeric range of precision "f16x3" (include/loco_asr.h): same policy as the speech encoder's
-                self.last_range_fallback = False
-                policy = self.range_policy
-                if policy != "off" and self.precision != "f32":
-                    torch.cuda.current_stream(device).synchronize()
-                    rc = self._lib.loco_forward_status(self._handle, None, 0)
-                    if rc != 0:
-                        if policy == "raise":
-                            _lib.check(rc, "loco_forward_text")
-                        _lib.check(self._lib.loco_set_precision(self._handle, self.PRECISIONS["f32"]), "set_precision")
-                        launch()  # the same batch on the exact-fp32 kernels (it rewrites the bound attention buffers too)
-                        self.last_range_fallback = True
-            finally:
-                if attn is not None:
-                    _lib.check(self._lib.loco_set_attention_outputs(self._handle, None, 0))
-        self.last_frames = frames
-        hidden = tuple(hs) if hs is not None else None
-        if return_dict is False:
-            return tuple(v for v in (out, hidden, attn) if v is not None)
-        return BaseModelOutput(last_hidden_state=out, hidden_states=hidden, attentions=attn)
+        ids32, m, T = self._prepare(ids.to(device), mask.to(device))
+        return self._submit(ids32, m, T, Pack(wav=ids32, mask=m, valid_len=None, pad_len=[], spans=spans))
 
 
 class SpeechT5ForTextToSpeechMI355X(nn.Module):

@@ -181,3 +181,85 @@ def test_text_batches_packed_into_one_forward(tmp_path):
             a, b = pickle.load(f1), pickle.load(f2)
         assert a["id"] == b["id"] and a["embedding"].shape == b["embedding"].shape and (a["target"] == b["target"]).all()
         assert rel_l2(b["embedding"], a["embedding"]) < 5e-6
+
+
+FFN1 = "wrapped_encoder.layers.0.feed_forward.intermediate_dense."
+
+
+def small_text_model(ffn1_factor=None):
+    """A fresh 2-layer text encoder on the GPU and its full state dict (numpy, oracle names); ``ffn1_factor`` scales layer 0's
+    intermediate_dense weight and bias (test_gpu_range.py: x 40000 puts the GELU'd intermediate beyond fp16's 65504)."""
+    sd = la.synth.encoder_state_dict(0, layers=2)
+    if ffn1_factor is not None:
+        for k in (FFN1 + "weight", FFN1 + "bias"):
+            sd[k] = (sd[k] * np.float32(ffn1_factor)).astype(np.float32)
+    _, enc_sd = la.synth.split_state_dict(sd)
+    tsd = la.synth.text_prenet_state_dict(0)
+    tpre = {k[len("text_prenet."):]: torch.from_numpy(np.asarray(v)) for k, v in tsd.items()}
+    model = la.SpeechT5ForTextToSpeechMI355X.from_state_dicts(tpre, {k: torch.from_numpy(v) for k, v in enc_sd.items()}, layers=2).cuda()
+    full = dict(sd)
+    full.update(tsd)
+    return model.speecht5.encoder, full
+
+
+def overflow_case():
+    """The text twin of test_gpu_range.py's overflow model, built once: (encoder, state dict, ids, mask) for ids [2, 9] of lengths
+    [9, 3]."""
+    if "overflow" not in _cache:
+        enc, sd = small_text_model(40000.0)
+        ids, mask = la.synth.token_ids(2, 9, seed=7, lengths=[9, 3])
+        _cache["overflow"] = (enc, sd, ids, mask)
+    return _cache["overflow"]
+
+
+def test_text_overflow_is_detected_and_rerun_in_fp32(oracle):
+    """test_gpu_range.py::test_overflow_is_detected_and_rerun_in_fp32 on the text front end, whose synchronous forward applies the
+    range policy in Python (loco_forward_text, loco_forward_status, the batch again at "f32"): default policy = fp32 re-run and an
+    fp32-class result; 'raise' = LOCO_E_RANGE naming the stage; 'off' = the fp16 planes' output, the status left to the caller; any
+    other policy string is refused."""
+    enc, sd, ids, mask = overflow_case()
+    idt, mt = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda()
+    try:
+        out = enc(idt, attention_mask=mt).last_hidden_state
+        assert enc.last_range_fallback and torch.isfinite(out).all()
+        err = rel_l2(out, oracle.encode_text(ids, mask, sd, dtype=torch.float64))
+        print(f"text overflow case after the fp32 re-run: rel L2 vs fp64 = {err:.2e}")
+        assert err < 1e-5
+        enc.range_policy = "raise"
+        with pytest.raises(la.LocoError, match=r"feed_forward intermediate.*above"):
+            enc(idt, attention_mask=mt)
+        enc.range_policy = "off"
+        y = enc(idt, attention_mask=mt).last_hidden_state
+        torch.cuda.synchronize()
+        assert enc._lib.loco_forward_status(enc._handle, None, 0) == -5
+        assert not enc.last_range_fallback and not torch.isfinite(y).all()
+        enc.range_policy = "fp23"
+        with pytest.raises(ValueError):
+            enc(idt, attention_mask=mt)
+    finally:
+        enc.range_policy = "fp32"
+
+
+def test_text_async_fallback_equals_sync_fallback():
+    """Both re-runs are the same precision-0 launch sequence of the library's text forward: bit-equal outputs."""
+    enc, _, ids, mask = overflow_case()
+    idt, mt = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda()
+    ref = enc(idt, attention_mask=mt).last_hidden_state.clone()
+    assert enc.last_range_fallback
+    t = enc.forward_async(idt, attention_mask=mt)
+    got = t.result().last_hidden_state
+    assert t.used_fp32 and torch.equal(got, ref)
+
+
+def test_reserve_workspace_on_a_fresh_text_encoder():
+    """reserve_workspace before any set_inflight, on an encoder that has run nothing: sized by the TEXT plan, and the forward that
+    follows finds a slot workspace of at least its need and gives the synchronous forward's bits."""
+    enc, _ = small_text_model()
+    enc.reserve_workspace(2, 9)
+    ids, mask = la.synth.token_ids(2, 9, seed=7, lengths=[9, 3])
+    idt, mt = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda()
+    t = enc.forward_async(idt, attention_mask=mt)
+    got = t.result().last_hidden_state
+    need = int(enc._lib.loco_text_workspace_bytes(enc._handle, 2, 9))
+    assert need > 0 and t._slot.workspace.numel() >= need
+    assert not t.used_fp32 and torch.equal(got, enc(idt, attention_mask=mt).last_hidden_state)
