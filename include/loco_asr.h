@@ -702,6 +702,56 @@ size_t loco_dtw_align_workspace_bytes(int32_t B, int32_t S, int32_t T);
 int loco_op_dtw_align(const float* A, int64_t ld, const int32_t* n, const int32_t* frames, int32_t B, int32_t S, int32_t T, int32_t* start,
                       int32_t* end, void* workspace, void* stream);
 
+/* ---- long-form segmentation: a recording cut into utterance-sized pieces at pauses (csrc/segment.hip) --------------------------------
+ * The decoder's rows end at 450 tokens and the model was trained on utterances of seconds, so a 10- or 60-minute recording is cut
+ * before it is encoded.  PARITY UNPINNED: the reference has no counterpart; the rules are pinned by a numpy restatement
+ * (tests/segment_ref.py) that agrees bit for bit on the same db array.  Frames are the encoder's: frame t covers samples
+ * [320 t, 320 t + 400), F = loco_output_frames(n).  Seconds become frames by rounding s * 50 to the nearest integer, ties to even.
+ *   loco_vad_default_params   the defaults of DESIGN.md 8 (struct_size set)
+ *   loco_vad_frames           checks a parameter set on the host and writes frames[5] = max_frames, min_frames, min_silence, min_speech,
+ *               pad.  LOCO_E_INVALID naming the field: a struct_size that is not sizeof(LocoVadParams), a value that is not finite,
+ *               max_segment_s beyond LOCO_VAD_MAX_SEGMENT_S (30 s: about 15 characters a second fill the decoder's 450 positions) or
+ *               below 2 frames, min_segment_s below one frame or not below max_segment_s (the walk would make no progress),
+ *               min_silence_s below one frame, negative min_speech_s / pad_s / margin_db / min_dynamic_db, quantiles outside (0, 1) or
+ *               noise_quantile >= peak_quantile.
+ *   loco_op_frame_energy_db   db[t] = 10 log10(mean of x^2 over frame t + 1e-12) (exactly -120 for a frame of zeros), f32 [F]; one
+ *               wave per frame, a fixed summation order.  n < 400: LOCO_E_INVALID.
+ *   loco_op_vad_segments      ONE recording, one workgroup, nothing read back on the host.  Threshold: histogram of 0.25 dB bins from
+ *               -120 dB (NaN: bin 0); noise / peak = the lower edge of the first bin whose cumulative count reaches ceil(quantile * F);
+ *               peak < abs_floor_db: silent, 0 segments, *threshold_db = +inf; peak - noise < min_dynamic_db: every frame that is not
+ *               NaN is speech, *threshold_db = -inf; otherwise thr = max(abs_floor_db, noise + margin_db), speech = db > thr.
+ *               Clean-up: interior silence runs shorter than min_silence become speech, then speech runs shorter than min_speech become
+ *               silence.  Cuts: from s = 0, the rest is the last segment when F - s <= max_frames; otherwise the next segment starts at c
+ *               in (s + min_frames, s + max_frames]: the centre (a + b) / 2 of the silence run [a, b) that is longest after clipping to
+ *               that window (ties: the later run), or, without one, the first frame of least db in [s + max_frames / 2, s + max_frames]
+ *               (NaN counts as least).  trim: a segment loses leading and trailing silence beyond pad frames; one without a speech frame
+ *               is dropped.  seg_start / seg_end i32 [max_segments] (end exclusive), *count = the number of segments, or minus that
+ *               number when it exceeds max_segments (only the first max_segments are written); all outputs in device memory.
+ *               workspace >= loco_vad_workspace_bytes(F) (0 for F outside 1 .. 2^24).
+ *               Errors, before any launch: null pointers, F outside 1 .. 2^24, max_segments < 1, refused parameters, a workspace
+ *               below loco_vad_workspace_bytes(F) (an operator's argument like any other): LOCO_E_INVALID. */
+#define LOCO_VAD_MAX_SEGMENT_S 30.0
+typedef struct LocoVadParams {
+    uint32_t struct_size; /* sizeof(LocoVadParams) */
+    int32_t trim;         /* 1 */
+    double max_segment_s; /* 20 */
+    double min_segment_s; /* 1 */
+    double min_silence_s; /* 0.3 */
+    double min_speech_s;  /* 0.1 */
+    double pad_s;         /* 0.2 */
+    double noise_quantile; /* 0.10 */
+    double peak_quantile;  /* 0.99 */
+    double margin_db;      /* 10 */
+    double abs_floor_db;   /* -60 */
+    double min_dynamic_db; /* 15 */
+} LocoVadParams;
+void loco_vad_default_params(LocoVadParams* params);
+int loco_vad_frames(const LocoVadParams* params, int32_t* frames);
+size_t loco_vad_workspace_bytes(int64_t F);
+int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream);
+int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
+                         int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,10 +10,13 @@ from ._lib import LIB_PATH, LocoError  # noqa: F401
 from .encoder import BaseModelOutput, Pack, SpeechT5EncoderWithSpeechPrenetMI355X, sinusoid_table  # noqa: F401
 from .feature_extractor import BatchFeature, SpeechT5FeatureExtractorMI355X  # noqa: F401
 from .intent_head import IntentClassifierMI355X  # noqa: F401
+from . import segment  # noqa: F401
+from .segment import LongSegment, LongTranscript, Segments, VadParams  # noqa: F401
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X  # noqa: F401
 from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextToSpeechMI355X,  # noqa: F401
                            scaled_positional_table)
 
 __all__ = ["synth", "LIB_PATH", "LocoError", "BaseModelOutput", "Pack", "SpeechT5EncoderWithSpeechPrenetMI355X",
            "SpeechT5ForSpeechToTextMI355X", "sinusoid_table", "BatchFeature", "SpeechT5FeatureExtractorMI355X", "IntentClassifierMI355X",
-           "SpeechT5EncoderWithTextPrenetMI355X", "SpeechT5ForTextToSpeechMI355X", "scaled_positional_table"]
+           "SpeechT5EncoderWithTextPrenetMI355X", "SpeechT5ForTextToSpeechMI355X", "scaled_positional_table", "segment", "VadParams", "Segments",
+           "LongSegment", "LongTranscript"]

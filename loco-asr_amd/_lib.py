@@ -34,6 +34,13 @@ class SampleConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class LocoVadParams(C.Structure):
+    """LocoVadParams of include/loco_asr.h (long-form segmentation): ``loco_vad_default_params`` fills it."""
+    _fields_ = [("struct_size", C.c_uint32), ("trim", C.c_int32), ("max_segment_s", C.c_double), ("min_segment_s", C.c_double),
+                ("min_silence_s", C.c_double), ("min_speech_s", C.c_double), ("pad_s", C.c_double), ("noise_quantile", C.c_double),
+                ("peak_quantile", C.c_double), ("margin_db", C.c_double), ("abs_floor_db", C.c_double), ("min_dynamic_db", C.c_double)]
+
+
 _vp, _i32, _i64, _sz, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 _u32p = C.POINTER(C.c_uint32)
 
@@ -144,6 +151,11 @@ SIGNATURES = {
     "loco_op_decoder_attention_probs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f, _vp]),
     "loco_dtw_align_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "loco_op_dtw_align": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "loco_vad_default_params": (None, [C.POINTER(LocoVadParams)]),
+    "loco_vad_frames": (C.c_int, [C.POINTER(LocoVadParams), C.POINTER(_i32)]),
+    "loco_vad_workspace_bytes": (_sz, [_i64]),
+    "loco_op_frame_energy_db": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "loco_op_vad_segments": (C.c_int, [_vp, _i64, C.POINTER(LocoVadParams), _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2746,3 +2746,83 @@ int loco_decoder_score(const float* logits, int64_t ld, const int32_t* targets, 
         HIP_TRY(launch_score_reduce(token_logprobs, targets, B, S, ignore_index, seq_logprob, seq_count, loss, (hipStream_t)stream));
     return LOCO_OK;
 }
+
+// ---- long-form segmentation (segment.hip) ----
+void loco_vad_default_params(LocoVadParams* p) {
+    if (!p) return;
+    *p = LocoVadParams{(uint32_t)sizeof(LocoVadParams), 1, 20.0, 1.0, 0.3, 0.1, 0.2, 0.10, 0.99, 10.0, -60.0, 15.0};
+}
+
+int loco_vad_frames(const LocoVadParams* p, int32_t* frames) {
+    const char* fn = "loco_vad_frames";
+    if (!p || !frames) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (p->struct_size != sizeof(LocoVadParams))
+        return fail(LOCO_E_INVALID, "%s: struct_size = %u is not sizeof(LocoVadParams) = %zu", fn, p->struct_size, sizeof(LocoVadParams));
+    const struct { const char* name; double v; } all[] = {
+        {"max_segment_s", p->max_segment_s}, {"min_segment_s", p->min_segment_s}, {"min_silence_s", p->min_silence_s},
+        {"min_speech_s", p->min_speech_s},   {"pad_s", p->pad_s},                 {"noise_quantile", p->noise_quantile},
+        {"peak_quantile", p->peak_quantile}, {"margin_db", p->margin_db},         {"abs_floor_db", p->abs_floor_db},
+        {"min_dynamic_db", p->min_dynamic_db}};
+    for (const auto& f : all)
+        if (!std::isfinite(f.v)) return fail(LOCO_E_INVALID, "%s: %s = %g is not finite", fn, f.name, f.v);
+    if (p->max_segment_s > LOCO_VAD_MAX_SEGMENT_S)
+        return fail(LOCO_E_INVALID, "%s: max_segment_s = %g exceeds %g s, what the decoder's 450 token positions hold at about 15 characters a second",
+                    fn, p->max_segment_s, (double)LOCO_VAD_MAX_SEGMENT_S);
+    for (int i = 1; i < 5; ++i)
+        if (all[i].v < 0.0 || all[i].v > LOCO_VAD_MAX_SEGMENT_S)
+            return fail(LOCO_E_INVALID, "%s: %s = %g is outside 0 .. %g s", fn, all[i].name, all[i].v, (double)LOCO_VAD_MAX_SEGMENT_S);
+    const auto to_frames = [](double s) { return (int32_t)std::nearbyint(s * 50.0); };  // ties to even, as Python's round()
+    const int32_t maxf = to_frames(p->max_segment_s), minf = to_frames(p->min_segment_s), sil = to_frames(p->min_silence_s);
+    if (maxf < 2) return fail(LOCO_E_INVALID, "%s: max_segment_s = %g is below 2 frames (0.04 s)", fn, p->max_segment_s);
+    if (minf < 1) return fail(LOCO_E_INVALID, "%s: min_segment_s = %g is below one frame (0.02 s)", fn, p->min_segment_s);
+    if (minf >= maxf)
+        return fail(LOCO_E_INVALID, "%s: min_segment_s = %g is not below max_segment_s = %g: the walk over cuts would make no progress", fn,
+                    p->min_segment_s, p->max_segment_s);
+    if (sil < 1) return fail(LOCO_E_INVALID, "%s: min_silence_s = %g is below one frame (0.02 s)", fn, p->min_silence_s);
+    if (!(p->noise_quantile > 0.0 && p->noise_quantile < 1.0))
+        return fail(LOCO_E_INVALID, "%s: noise_quantile = %g is outside (0, 1)", fn, p->noise_quantile);
+    if (!(p->peak_quantile > 0.0 && p->peak_quantile < 1.0))
+        return fail(LOCO_E_INVALID, "%s: peak_quantile = %g is outside (0, 1)", fn, p->peak_quantile);
+    if (p->noise_quantile >= p->peak_quantile)
+        return fail(LOCO_E_INVALID, "%s: noise_quantile = %g is not below peak_quantile = %g", fn, p->noise_quantile, p->peak_quantile);
+    if (p->margin_db < 0.0) return fail(LOCO_E_INVALID, "%s: margin_db = %g is negative", fn, p->margin_db);
+    if (p->min_dynamic_db < 0.0) return fail(LOCO_E_INVALID, "%s: min_dynamic_db = %g is negative", fn, p->min_dynamic_db);
+    frames[0] = maxf;
+    frames[1] = minf;
+    frames[2] = sil;
+    frames[3] = to_frames(p->min_speech_s);
+    frames[4] = to_frames(p->pad_s);
+    return LOCO_OK;
+}
+
+size_t loco_vad_workspace_bytes(int64_t F) { return vad_workspace_bytes((long)F); }
+
+int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream) {
+    const char* fn = "loco_op_frame_energy_db";
+    if (!wav || !db) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (n < kVadWindow) return fail(LOCO_E_INVALID, "%s: n = %lld samples is shorter than one frame (400)", fn, (long long)n);
+    if (loco_output_frames(n) > kVadMaxFrames)
+        return fail(LOCO_E_INVALID, "%s: n = %lld samples exceed %ld frames", fn, (long long)n, kVadMaxFrames);
+    HIP_TRY(launch_frame_energy_db(wav, (long)n, db, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
+                         int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_op_vad_segments";
+    if (!db || !params || !seg_start || !seg_end || !count || !threshold_db || !workspace) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (F < 1 || F > kVadMaxFrames) return fail(LOCO_E_INVALID, "%s: F = %lld is outside 1 .. %ld frames", fn, (long long)F, kVadMaxFrames);
+    if (max_segments < 1) return fail(LOCO_E_INVALID, "%s: max_segments = %d must be >= 1", fn, max_segments);
+    int32_t fr[5];
+    if (const int rc = loco_vad_frames(params, fr)) return rc;
+    if (workspace_bytes < vad_workspace_bytes((long)F))
+        return fail(LOCO_E_INVALID, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, vad_workspace_bytes((long)F));
+    const auto rank = [F](double q) {
+        const int64_t k = (int64_t)std::ceil(q * (double)F);
+        return (int)(k < 1 ? 1 : (k > F ? F : k));
+    };
+    VadArgs a{(int)F, fr[0], fr[1], fr[2], fr[3], fr[4], params->trim ? 1 : 0, rank(params->noise_quantile), rank(params->peak_quantile),
+              (float)params->margin_db, (float)params->abs_floor_db, (float)params->min_dynamic_db, max_segments};
+    HIP_TRY(launch_vad_segments(db, a, seg_start, seg_end, count, threshold_db, workspace, (hipStream_t)stream));
+    return LOCO_OK;
+}

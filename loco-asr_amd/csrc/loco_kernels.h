@@ -420,6 +420,25 @@ hipError_t launch_dec_attn_mean(const float* P, float* A, int B, int S, int T, u
 hipError_t launch_dtw_align(const float* A, long ld, const int32_t* n, const int32_t* frames, int B, int S, int T, int32_t* start, int32_t* end,
                             unsigned char* back, hipStream_t s);
 
+// ---- long-form segmentation (segment.hip) ----
+constexpr int kVadHop = 320, kVadWindow = 400;  // the encoder's frame t covers samples [320 t, 320 t + 400)
+constexpr int kVadBins = 512;                   // 0.25 dB bins from -120 dB
+constexpr long kVadMaxFrames = 1L << 24;        // frames of one recording (93 hours)
+constexpr int kVadNormal = 0, kVadSilent = 1, kVadAllSpeech = 2;
+struct VadArgs {  // by value; everything the host derives from LocoVadParams and F
+    int F, max_frames, min_frames, min_silence, min_speech, pad, trim;
+    int k_noise, k_peak;  // ceil(quantile * F), in 1 .. F
+    float margin_db, abs_floor_db, min_dynamic_db;
+    int max_segments;
+};
+// db[t] = 10 log10(mean of x^2 over frame t + 1e-12) for t < (n - 80) / 320; n >= 400
+hipError_t launch_frame_energy_db(const float* wav, long n, float* db, hipStream_t s);
+size_t vad_workspace_bytes(long F);
+// one recording, one workgroup: seg_start / seg_end i32 [max_segments], count i32 [1] (negative: -needed > max_segments), threshold_db
+// f32 [1] (+inf: silent recording, -inf: no usable silence), all on the device; ws >= vad_workspace_bytes(F)
+hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
+                               void* ws, hipStream_t s);
+
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
 }  // namespace loco

@@ -1,0 +1,257 @@
+// Cutting a long recording into utterance-sized segments at pauses, on the device where the waveform lives after resampling
+// (include/loco_asr.h "long-form segmentation").  There is no counterpart in the reference: the rules are this
+// project's own, restated in numpy by tests/segment_ref.py, and every rule below that decides a frame, a run or a cut is integer or
+// exact fp32 arithmetic, so that the two agree bit for bit on the same db array.
+//
+// Frames are the encoder's: frame t covers samples [320 t, 320 t + 400), F = loco_output_frames(n) = (n - 80) / 320.
+//
+//   frame_energy_db_kernel   db[t] = 10 log10(mean(x^2) + 1e-12): one wave per frame, lane l squares samples l, l + 64, ... in that
+//                            order with fmaf, the lanes meet in wave_sum -- a frame's bits do not depend on where it is computed.
+//   vad_segments_kernel      ONE workgroup of 1024 threads per recording.  Parallel across the workgroup: the histogram (LDS integer
+//                            atomics), the speech mask, the run boundaries (chunked count + block scan, three times: raw mask, gaps
+//                            filled, short speech dropped) and each step's scan of its window.  Sequential: the walk over cuts, at
+//                            most F / min(min_frames + 1, max_frames / 2) steps of two or three barriers each.
+// Memory: F bytes of mask, F + 1 run boundaries and F run indices in the workspace (global; read back by other waves of the same
+// workgroup only behind __syncthreads()).  Nothing here is larger than 180 000 frames x 9 bytes for an hour of audio.
+#include <cmath>
+
+#include "loco_kernels.h"
+
+namespace loco {
+
+namespace {
+constexpr int kVadThreads = 1024;
+constexpr int kVadWaves = kVadThreads / 64;
+typedef unsigned long long u64;
+
+__global__ __launch_bounds__(256) void frame_energy_db_kernel(const float* __restrict__ wav, long F, float* __restrict__ db) {
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= F) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const float* x = wav + t * kVadHop;
+    float acc = 0.f;
+#pragma unroll
+    for (int i = lane; i < kVadWindow; i += 64) acc = fmaf(x[i], x[i], acc);
+    const float mean = wave_sum(acc) / (float)kVadWindow;
+    // 10 log10(1e-12) is -120 exactly; log10f's last bit is not relied on for it
+    if (lane == 0) db[t] = mean == 0.f ? -120.f : 10.f * log10f(mean + 1e-12f);
+}
+
+// 0.25 dB bins from -120 dB: the scaling by 4 is exact, so no contraction can move a value across an edge.  NaN: bin 0.
+__device__ __forceinline__ int vad_bin(float v) {
+    if (!(v == v)) return 0;
+    const float t = floorf((v - (-120.f)) * 4.f);
+    return t < 0.f ? 0 : (t > (float)(kVadBins - 1) ? kVadBins - 1 : (int)t);
+}
+
+// floats in a total order as unsigned integers: NaN lowest, then -inf ... -0 < +0 ... +inf
+__device__ __forceinline__ unsigned vad_order_key(float v) {
+    if (!(v == v)) return 0u;
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// maximum of v over the workgroup, the same value in every thread; sh: kVadWaves words of LDS, free again on return
+__device__ __forceinline__ u64 block_max_u64(u64 v, u64* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 u = __shfl_xor(v, o, 64);
+        v = u > v ? u : v;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 r = sh[0];
+#pragma unroll
+    for (int i = 1; i < kVadWaves; ++i) r = sh[i] > r ? sh[i] : r;
+    __syncthreads();
+    return r;
+}
+
+// exclusive prefix sum of v over the workgroup's threads; *total = the sum, in every thread
+__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < kVadWaves; ++i) {
+        if (i < w) base += sh[i];
+        tot += sh[i];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
+// Runs of equal mask values: bnd[r] = first frame of run r (bnd[R] = F), rid[t] = the run frame t lies in.  Returns R.  Thread i owns
+// the frames [i chunk, (i + 1) chunk): it counts the runs that start there, the counts meet in one scan, it writes its frames.
+// Ends with a barrier: bnd and rid are readable by every thread on return.
+__device__ int build_runs(const unsigned char* mask, int F, int32_t* bnd, int32_t* rid, int* sh) {
+    const int chunk = (F + kVadThreads - 1) / kVadThreads;
+    const long c0l = (long)threadIdx.x * chunk;
+    const int c0 = c0l < F ? (int)c0l : F, c1 = c0 + chunk < F ? c0 + chunk : F;
+    int starts = 0;
+    for (int t = c0; t < c1; ++t) starts += (t == 0 || mask[t] != mask[t - 1]) ? 1 : 0;
+    int R;
+    int cur = block_excl_scan(starts, sh, &R) - 1;  // the run frame c0 - 1 lies in
+    for (int t = c0; t < c1; ++t) {
+        if (t == 0 || mask[t] != mask[t - 1]) bnd[++cur] = t;
+        rid[t] = cur;
+    }
+    if (threadIdx.x == 0) bnd[R] = F;
+    __syncthreads();
+    return R;
+}
+
+__global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* __restrict__ db, VadArgs a, int32_t* __restrict__ seg_start,
+                                                                    int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
+                                                                    float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
+    __shared__ int hist[kVadBins];
+    __shared__ int sh_i[kVadWaves];
+    __shared__ u64 sh_q[kVadWaves];
+    __shared__ int sh_mode;
+    __shared__ float sh_thr;
+    const int tid = threadIdx.x, F = a.F;
+
+    // ---- threshold ----
+    for (int i = tid; i < kVadBins; i += kVadThreads) hist[i] = 0;
+    __syncthreads();
+    for (int t = tid; t < F; t += kVadThreads) atomicAdd(&hist[vad_bin(db[t])], 1);
+    __syncthreads();
+    if (tid == 0) {
+        int cum = 0, nb = -1, pb = -1;
+        for (int i = 0; i < kVadBins; ++i) {
+            cum += hist[i];
+            if (nb < 0 && cum >= a.k_noise) nb = i;
+            if (pb < 0 && cum >= a.k_peak) pb = i;
+        }
+        const float noise = -120.f + 0.25f * (float)nb, peak = -120.f + 0.25f * (float)pb;  // exact
+        int mode = kVadNormal;
+        float thr = fmaxf(a.abs_floor_db, noise + a.margin_db);
+        if (peak < a.abs_floor_db) {
+            mode = kVadSilent;
+            thr = INFINITY;
+        } else if (peak - noise < a.min_dynamic_db) {
+            mode = kVadAllSpeech;
+            thr = -INFINITY;
+        }
+        sh_mode = mode;
+        sh_thr = thr;
+        *thr_out = thr;
+        if (mode == kVadSilent) *count = 0;
+    }
+    __syncthreads();
+    const int mode = sh_mode;
+    const float thr = sh_thr;
+    if (mode == kVadSilent) return;  // uniform
+
+    // ---- mask and clean-up ----
+    for (int t = tid; t < F; t += kVadThreads) {
+        const float v = db[t];
+        mask[t] = (mode == kVadAllSpeech ? v == v : v > thr) ? 1 : 0;
+    }
+    __syncthreads();
+    int R = build_runs(mask, F, bnd, rid, sh_i);
+    int m0 = mask[0];
+    for (int r = tid + 1; r < R - 1; r += kVadThreads) {  // interior silence runs shorter than min_silence become speech
+        const int lo = bnd[r], hi = bnd[r + 1];
+        if (((m0 ^ r) & 1) == 0 && hi - lo < a.min_silence)
+            for (int t = lo; t < hi; ++t) mask[t] = 1;
+    }
+    __syncthreads();
+    R = build_runs(mask, F, bnd, rid, sh_i);
+    for (int r = tid; r < R; r += kVadThreads) {  // then speech runs shorter than min_speech become silence
+        const int lo = bnd[r], hi = bnd[r + 1];
+        if (((m0 ^ r) & 1) == 1 && hi - lo < a.min_speech)
+            for (int t = lo; t < hi; ++t) mask[t] = 0;
+    }
+    __syncthreads();
+    R = build_runs(mask, F, bnd, rid, sh_i);
+    m0 = mask[0];
+
+    // ---- the walk over cuts: s, c and n are the same in every thread ----
+    int s = 0, n = 0;
+    while (s < F) {
+        int c = F;
+        if (F - s > a.max_frames) {
+            const int lo = s + a.min_frames + 1, hi = s + a.max_frames;  // the cut's window (s + min, s + max]; hi <= F - 1
+            const int r0 = rid[lo], r1 = rid[hi];
+            u64 best = 0;
+            for (int r = r0 + tid; r <= r1; r += kVadThreads) {
+                if (((m0 ^ r) & 1) == 0) {  // a silence run, clipped to the window: never empty
+                    const int ca = bnd[r] > lo ? bnd[r] : lo, cb = bnd[r + 1] < hi + 1 ? bnd[r + 1] : hi + 1;
+                    const u64 key = ((u64)(unsigned)(cb - ca) << 32) | (unsigned)r;  // longest, ties to the later run
+                    best = key > best ? key : best;
+                }
+            }
+            best = block_max_u64(best, sh_q);
+            if (best) {
+                const int r = (int)(unsigned)(best & 0xffffffffu);
+                const int ca = bnd[r] > lo ? bnd[r] : lo, cb = bnd[r + 1] < hi + 1 ? bnd[r + 1] : hi + 1;
+                c = (ca + cb) / 2;
+            } else {  // no silence in the window: the first frame of least energy in its second half
+                u64 least = 0;
+                for (int t = s + a.max_frames / 2 + tid; t <= hi; t += kVadThreads) {
+                    const u64 key = ~(((u64)vad_order_key(db[t]) << 32) | (unsigned)t);
+                    least = key > least ? key : least;
+                }
+                least = ~block_max_u64(least, sh_q);
+                c = (int)(unsigned)(least & 0xffffffffu);
+            }
+        }
+        int st = s, en = c;
+        bool keep = true;
+        if (a.trim) {
+            const int ra = rid[s], rb = rid[c - 1];
+            const int first = ((m0 ^ ra) & 1) ? s : bnd[ra + 1];
+            const int last = ((m0 ^ rb) & 1) ? c - 1 : bnd[rb] - 1;
+            keep = first < c;
+            st = first - a.pad > s ? first - a.pad : s;
+            en = last + 1 + a.pad < c ? last + 1 + a.pad : c;
+        }
+        if (keep) {
+            if (tid == 0 && n < a.max_segments) {
+                seg_start[n] = st;
+                seg_end[n] = en;
+            }
+            ++n;
+        }
+        s = c;
+    }
+    if (tid == 0) *count = n <= a.max_segments ? n : -n;
+}
+}  // namespace
+
+size_t vad_workspace_bytes(long F) {
+    if (F < 1 || F > kVadMaxFrames) return 0;
+    const size_t mask = ((size_t)F + 15) & ~(size_t)15, bnd = (((size_t)F + 1) * 4 + 15) & ~(size_t)15;
+    return mask + bnd + (size_t)F * 4;
+}
+
+hipError_t launch_frame_energy_db(const float* wav, long n, float* db, hipStream_t s) {
+    if (n < kVadWindow) return hipErrorInvalidValue;
+    const long F = (n - (kVadWindow - kVadHop)) / kVadHop;  // 320 (F - 1) + 399 <= n - 1
+    hipLaunchKernelGGL(frame_energy_db_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, wav, F, db);
+    return hipGetLastError();
+}
+
+hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
+                               void* ws, hipStream_t s) {
+    if (a.F < 1 || a.F > kVadMaxFrames || a.max_segments < 1 || a.min_frames < 1 || a.max_frames <= a.min_frames || a.k_noise < 1 ||
+        a.k_peak < a.k_noise || a.k_peak > a.F)
+        return hipErrorInvalidValue;
+    unsigned char* mask = static_cast<unsigned char*>(ws);
+    const size_t mask_bytes = ((size_t)a.F + 15) & ~(size_t)15, bnd_bytes = (((size_t)a.F + 1) * 4 + 15) & ~(size_t)15;
+    int32_t* bnd = reinterpret_cast<int32_t*>(mask + mask_bytes);
+    int32_t* rid = reinterpret_cast<int32_t*>(mask + mask_bytes + bnd_bytes);
+    hipLaunchKernelGGL(vad_segments_kernel, dim3(1), dim3(kVadThreads), 0, s, db, a, seg_start, seg_end, count, threshold_db, mask, bnd, rid);
+    return hipGetLastError();
+}
+
+}  // namespace loco

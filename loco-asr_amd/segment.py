@@ -1,0 +1,169 @@
+"""Long-form segmentation on the device (csrc/segment.hip): a 16 kHz recording is cut into utterance-sized segments at
+pauses, so that ``SpeechT5ForSpeechToTextMI355X.transcribe_long`` can hand each one to the decoder, whose rows end at 450 tokens.
+
+    db = frame_energy_db(wave)             # f32 [F], the encoder's frames: frame t covers samples [320 t, 320 t + 400)
+    seg = segment(wave, max_segment_s=15)  # Segments: frame and sample bounds on the device, count and threshold on the host
+
+Parity unpinned: the reference has no counterpart; the rules are pinned by the numpy restatement in tests/segment_ref.py.  CUDA
+tensors only: without a GPU both functions raise.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, fields
+from typing import Optional
+
+import torch
+
+from . import _lib
+
+HOP, WINDOW, FRAME_RATE, SAMPLE_RATE = 320, 400, 50, 16000
+
+
+@dataclass
+class VadParams:
+    """The fields of LocoVadParams (include/loco_asr.h); seconds become frames by round(s * 50)."""
+    max_segment_s: float = 20.0
+    min_segment_s: float = 1.0
+    min_silence_s: float = 0.3
+    min_speech_s: float = 0.1
+    pad_s: float = 0.2
+    noise_quantile: float = 0.10
+    peak_quantile: float = 0.99
+    margin_db: float = 10.0
+    abs_floor_db: float = -60.0
+    min_dynamic_db: float = 15.0
+    trim: bool = True
+
+    def to_c(self) -> _lib.LocoVadParams:
+        p = _lib.LocoVadParams()
+        p.struct_size = C.sizeof(_lib.LocoVadParams)
+        p.trim = 1 if self.trim else 0
+        for f in fields(self):
+            if f.name != "trim":
+                setattr(p, f.name, float(getattr(self, f.name)))
+        return p
+
+    def frames(self):
+        """(max_frames, min_frames, min_silence, min_speech, pad) as the library derives them; ValueError naming a refused field."""
+        out = (C.c_int32 * 5)()
+        _lib.check(_lib.load().loco_vad_frames(C.byref(self.to_c()), out), "VadParams")
+        return tuple(out)
+
+
+def resolve_params(vad=None, **params) -> VadParams:
+    """``vad``: None, a VadParams or a dict of its fields; keyword fields override it.  Checked on the host (ValueError by name)."""
+    if isinstance(vad, VadParams):
+        base = {f.name: getattr(vad, f.name) for f in fields(vad)}
+    elif vad is None:
+        base = {}
+    else:
+        base = dict(vad)
+    base.update(params)
+    known = {f.name for f in fields(VadParams)}
+    for k in base:
+        if k not in known:
+            raise TypeError(f"unknown segmentation parameter '{k}' (known: {', '.join(sorted(known))})")
+    p = VadParams(**base)
+    p.frames()
+    return p
+
+
+@dataclass
+class Segments:
+    """What ``segment`` returns.  ``start_frames`` / ``end_frames`` i32 [count] on the device (end exclusive), ``start_samples`` /
+    ``end_samples`` i64 [count] on the device with start = 320 start_frame and end = min(n, 320 end_frame + 80) -- the samples the
+    segment's frames cover; ``threshold_db`` (+inf: a silent recording, -inf: no usable silence, every frame speech) and ``count`` on
+    the host."""
+    start_frames: torch.Tensor
+    end_frames: torch.Tensor
+    start_samples: torch.Tensor
+    end_samples: torch.Tensor
+    threshold_db: float
+    count: int
+    samples: int = 0  # of the waveform
+
+
+def _wave(wave, what):
+    if not torch.is_tensor(wave) or not wave.is_cuda:
+        raise RuntimeError(f"{what} runs on an AMD GPU only: the waveform must be a CUDA tensor (there is no CPU path)")
+    if wave.dim() != 1:
+        raise ValueError(f"{what}: expected a 1-D waveform [samples], got {tuple(wave.shape)}")
+    if wave.shape[0] < WINDOW:
+        raise ValueError(f"{what}: {wave.shape[0]} samples are shorter than one encoder frame ({WINDOW})")
+    return wave.to(torch.float32).contiguous()
+
+
+def frame_energy_db(wave: torch.Tensor) -> torch.Tensor:
+    """f32 [F]: 10 log10(mean(x^2) + 1e-12) of every encoder frame of a 1-D 16 kHz CUDA waveform."""
+    wave = _wave(wave, "frame_energy_db")
+    lib = _lib.load()
+    n = int(wave.shape[0])
+    db = torch.empty(int(lib.loco_output_frames(n)), dtype=torch.float32, device=wave.device)
+    with torch.cuda.device(wave.device):
+        _lib.check(lib.loco_op_frame_energy_db(C.c_void_p(wave.data_ptr()), n, C.c_void_p(db.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)), "loco_op_frame_energy_db")
+    return db
+
+
+def segments_from_db(db: torch.Tensor, params: VadParams, max_segments: Optional[int] = None):
+    """The segmentation kernel on a given f32 [F] CUDA tensor: (start_frames i32 [max_segments], end_frames, count i32 [1], threshold
+    f32 [1]), all on the device and nothing read back.  ``max_segments`` None = the most the rules can produce for F frames."""
+    if not torch.is_tensor(db) or not db.is_cuda or db.dim() != 1 or db.dtype != torch.float32:
+        raise RuntimeError("segments_from_db: db must be a 1-D float32 CUDA tensor (there is no CPU path)")
+    db = db.contiguous()
+    lib = _lib.load()
+    F = int(db.shape[0])
+    maxf, minf = params.frames()[:2]
+    if max_segments is None:  # every step but the last advances by at least min(min_frames + 1, max_frames // 2) frames
+        max_segments = F // min(minf + 1, maxf // 2) + 1
+    dev = db.device
+    start = torch.empty(max(int(max_segments), 0), dtype=torch.int32, device=dev)
+    end = torch.empty_like(start)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    thr = torch.empty(1, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.loco_vad_workspace_bytes(F))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.loco_op_vad_segments(C.c_void_p(db.data_ptr()), F, C.byref(params.to_c()), C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr()),
+                                            int(max_segments), C.c_void_p(count.data_ptr()), C.c_void_p(thr.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                            ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "loco_op_vad_segments")
+    return start, end, count, thr
+
+
+def segment(wave: torch.Tensor, vad=None, **params) -> Segments:
+    """Cut a 1-D 16 kHz CUDA waveform at pauses: two launches (energy, segmentation), then the count and the threshold are
+    read back.  Parameters: the fields of VadParams, as keywords or as ``vad`` (a VadParams or a dict)."""
+    p = resolve_params(vad, **params)
+    wave = _wave(wave, "segment")
+    n = int(wave.shape[0])
+    db = frame_energy_db(wave)
+    start, end, count, thr = segments_from_db(db, p)
+    k, t = int(count.item()), float(thr.item())
+    if k < 0:
+        raise _lib.LocoError(f"segment: {-k} segments exceed the {start.shape[0]} the rules allow for {db.shape[0]} frames")
+    start, end = start[:k], end[:k]
+    return Segments(start_frames=start, end_frames=end, start_samples=start.to(torch.int64) * HOP,
+                    end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), threshold_db=t, count=k, samples=n)
+
+
+@dataclass
+class LongSegment:
+    """One segment of a LongTranscript: ``start_s`` / ``end_s`` in recording time, ``ids`` a 1-D LongTensor (host) as ``generate_many``
+    returns it; ``token_logprobs`` [len - 1] (device), ``logprob`` and ``avg_logprob`` with ``return_scores``; ``token_times`` f32
+    [len - 1, 2] (host), start and end of every generated token in recording time, with ``timestamps``."""
+    start_s: float
+    end_s: float
+    ids: torch.Tensor
+    token_logprobs: Optional[torch.Tensor] = None
+    logprob: Optional[float] = None
+    avg_logprob: Optional[float] = None
+    token_times: Optional[torch.Tensor] = None
+
+
+@dataclass
+class LongTranscript:
+    """What ``transcribe_long`` returns: the segments in time order, the recording's length and the speech threshold used."""
+    segments: list
+    duration_s: float
+    threshold_db: float

@@ -1,7 +1,8 @@
 """``SpeechT5ForSpeechToTextMI355X``: HuggingFace's speech-to-text model over the speech encoder (encoder.py) and, when decoder
 weights are loaded, the text decoder (decoder.py) -- ``forward(decoder_input_ids= / labels=)``, ``generate``, ``score``, ``align`` and
 their corpus forms ``generate_many`` / ``score_many`` / ``align_many``, which share one walk over the corpus (``corpus_packs``);
-``sample`` / ``sample_many`` draw n-best lists in ``generate_many``'s slot pool."""
+``sample`` / ``sample_many`` draw n-best lists in ``generate_many``'s slot pool; ``transcribe_long`` cuts a recording at pauses
+(segment.py) and hands the segments to ``generate_many`` / ``align_many``."""
 from __future__ import annotations
 
 import itertools
@@ -13,6 +14,7 @@ from torch import nn
 
 from . import checkpoint_map
 from . import decoder as dec
+from . import segment as seg
 from .encoder import SpeechT5EncoderWithSpeechPrenetMI355X
 from .holders import _Ref
 from .synth import LAYERS
@@ -443,6 +445,44 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                 lp, seq, _, _, _ = dec.score_logits(self.speecht5.encoder._lib, block, targets.to(block.device).contiguous(), len(rows), S - 1)
             out.token_logprobs, out.sequence_logprobs = lp, seq
         return out
+
+    @torch.no_grad()
+    def transcribe_long(self, waveform: torch.Tensor, vad=None, max_length: Optional[int] = None, slots: int = 64, pack: int = 8,
+                        return_scores: bool = False, timestamps: bool = False, do_normalize: bool = False):
+        """A transcript of a whole recording: ``waveform`` is a 1-D 16 kHz CUDA tensor of any length from one encoder frame on.  It is
+        cut at pauses on the device (segment.segment; ``vad``: None, a segment.VadParams or a dict of its fields), and every segment is
+        a batch of ONE clip -- ``input_values = waveform[s:e][None]``, mask all ones -- so its padded length is its own and GroupNorm
+        sees nothing of its neighbours: a segment's transcript depends on the segment's samples alone.  The batches go through
+        ``generate_many`` in time order (``max_length`` None = 450, the decoder's positions; ``slots``, ``pack`` as there) and, with
+        ``timestamps``, through ``align_many``; nothing else is computed here.
+
+        Returns a segment.LongTranscript whose ``segments[k]`` carries ``start_s`` / ``end_s``, ``ids``, with ``return_scores``
+        ``token_logprobs`` (device), ``logprob`` and ``avg_logprob``, and with ``timestamps`` ``token_times`` [len - 1, 2] in
+        recording time (``align_many``'s times plus ``start_s``).  ``do_normalize``: each segment is normalised on its own."""
+        self._require_decoder("transcribe_long()")
+        params = seg.resolve_params(vad)
+        cap = dec.resolve_max_length(dec.MAX_TEXT_POSITIONS if max_length is None else max_length)
+        segs = seg.segment(waveform, params)
+        duration = segs.samples / seg.SAMPLE_RATE
+        if segs.count == 0:
+            return seg.LongTranscript(segments=[], duration_s=duration, threshold_db=segs.threshold_db)
+        from .feature_extractor import SpeechT5FeatureExtractorMI355X
+        fe = SpeechT5FeatureExtractorMI355X(do_normalize=do_normalize)
+        bounds = list(zip(segs.start_samples.cpu().tolist(), segs.end_samples.cpu().tolist()))  # one read-back
+        wave = waveform.to(torch.float32)
+        batches = [fe(audio=[wave[s:e]], sampling_rate=seg.SAMPLE_RATE) for s, e in bounds]
+        rows = self.generate_many(batches, max_length=cap, slots=slots, pack=pack, return_scores=return_scores)
+        ids, scores = rows if return_scores else (rows, None)
+        out = [seg.LongSegment(start_s=s / seg.SAMPLE_RATE, end_s=e / seg.SAMPLE_RATE, ids=r)
+               for (s, e), r in zip(bounds, ids)]
+        if return_scores:
+            sums = [float(v) for v in torch.stack([t.double().sum() for t in scores]).cpu().tolist()]  # one read-back
+            for o, t, v in zip(out, scores, sums):
+                o.token_logprobs, o.logprob, o.avg_logprob = t, v, v / max(int(t.shape[0]), 1)
+        if timestamps:
+            for o, al in zip(out, self.align_many(batches, [r[1:] for r in ids], pack=pack)):
+                o.token_times = torch.stack([al.start_times, al.end_times], dim=1).cpu() + o.start_s
+        return seg.LongTranscript(segments=out, duration_s=duration, threshold_db=segs.threshold_db)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):

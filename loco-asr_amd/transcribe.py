@@ -13,6 +13,11 @@ with ``--greedy-first``, a sampled one otherwise.  No data parallelism.  Inputs,
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
 ``--synthetic N`` seeded clips; weights: ``--pretrained DIR`` (a HuggingFace speech-to-text checkpoint directory with the decoder)
 or ``--random-init`` (the deterministic synthetic weights).
+
+``--long FILE...`` transcribes whole recordings (a 10-minute call, a podcast): each file is cut at pauses on the device (segment.py:
+``--max-segment-s``, ``--min-silence-s``, ``--vad-margin-db``, ``--no-trim``) and its segments are decoded in the slot pool
+(``transcribe_long``; ``--slots`` defaults to 64).  One JSON line per recording: {"id", "duration_s", "threshold_db", "segments":
+[{"start_s", "end_s", "token_ids", "text"?, "logprob"?, "avg_logprob"?, "token_times"?}], "text"?}, the times in recording time.
 """
 from __future__ import annotations
 
@@ -118,6 +123,56 @@ def build_model(args):
     return model.to("cuda")
 
 
+def main_long(args, ap):
+    """``--long``: every FILE is one recording.  Flag combinations and segmentation parameters are refused before a model is built."""
+    from .segment import resolve_params
+    for flag, given in (("--split", bool(args.split)), ("--synthetic", args.synthetic > 0), ("--nbest", args.nbest != 0),
+                        ("--batch-size", args.batch_size != ap.get_default("batch_size"))):
+        if given:
+            raise SystemExit(f"--long does not go with {flag}: every segment of a recording is a batch of one, decoded greedily")
+    if not args.files:
+        raise SystemExit("--long needs audio FILES")
+    slots = args.slots or 64
+    if not 1 <= slots <= 64 or args.pack < 1:
+        raise SystemExit("--slots must be 1 .. 64 and --pack >= 1")
+    given = {k: v for k, v in (("max_segment_s", args.max_segment_s), ("min_silence_s", args.min_silence_s), ("margin_db", args.vad_margin_db))
+             if v is not None}
+    try:
+        vad = resolve_params(None, trim=not args.no_trim, **given)
+    except ValueError as e:
+        raise SystemExit(f"--max-segment-s / --min-silence-s / --vad-margin-db: {e}")
+    model = build_model(args)
+    tok = load_tokenizer(args.tokenizer)
+    device = torch.device("cuda", torch.cuda.current_device())
+    from .extract import load_audio_16k
+    fh = sys.stdout if args.out == "-" else open(args.out, "w")
+    try:
+        for path in args.files:
+            x = load_audio_16k(path, device=device)
+            x = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))
+            res = model.transcribe_long(x.to(device), vad=vad, max_length=args.max_length, slots=slots, pack=args.pack, return_scores=args.scores,
+                                        timestamps=args.timestamps, do_normalize=args.do_normalize)
+            rec = {"id": os.path.splitext(os.path.basename(path))[0], "duration_s": round(res.duration_s, 4),
+                   "threshold_db": res.threshold_db if math.isfinite(res.threshold_db) else None, "segments": []}  # JSON has no infinities
+            for sg in res.segments:
+                row = sg.ids.tolist()
+                one = {"start_s": round(sg.start_s, 4), "end_s": round(sg.end_s, 4), "token_ids": row}
+                if tok is not None:
+                    one["text"] = tok.decode(strip_special(row))
+                if args.scores:
+                    one["logprob"], one["avg_logprob"] = sg.logprob, sg.avg_logprob
+                if args.timestamps:
+                    one["token_times"] = [[round(a, 4), round(b, 4)] for a, b in sg.token_times.tolist()]
+                rec["segments"].append(one)
+            if tok is not None:
+                rec["text"] = " ".join(one["text"] for one in rec["segments"])
+            fh.write(json.dumps(rec) + "\n")
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m loco-asr_amd.transcribe", description=__doc__.split("\n\n")[0])
     ap.add_argument("--pretrained", default=None, metavar="DIR", help="HuggingFace SpeechT5ForSpeechToText checkpoint on disk (never downloaded)")
@@ -145,7 +200,18 @@ def main(argv=None):
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
     ap.add_argument("--precision", choices=["f16x3", "f32", "f16x2"], default="f16x3", help="arithmetic of the ENCODER (the decoder is fp32)")
     ap.add_argument("--out", default="-", help="JSON-lines file, - = stdout")
+    ap.add_argument("--long", action="store_true", help="FILES are whole recordings: cut each at pauses on the device, one JSON line per recording")
+    ap.add_argument("--max-segment-s", type=float, default=None, help="with --long: longest segment in seconds (default 20)")
+    ap.add_argument("--min-silence-s", type=float, default=None, help="with --long: shortest pause that counts as one (default 0.3)")
+    ap.add_argument("--vad-margin-db", type=float, default=None, help="with --long: speech is this far above the noise level (default 10)")
+    ap.add_argument("--no-trim", action="store_true", help="with --long: keep each segment's leading and trailing silence (segments then tile the recording)")
     args = ap.parse_args(argv)
+    if args.long:
+        return main_long(args, ap)
+    for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
+                    ("--no-trim", args.no_trim or None)):
+        if v is not None:
+            raise SystemExit(f"{flag} needs --long")
     if args.batch_size < 1:
         raise SystemExit("--batch-size must be >= 1")
     if args.slots < 0 or args.pack < 1:
