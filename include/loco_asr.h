@@ -351,7 +351,7 @@ int loco_op_layernorm(const float* x, const float* gamma, const float* beta, flo
                       float eps, void* stream);
 
 /* C[z][m,n] = epi(sum_k A[z][m*lda+k] * W[n*ldw+k] + bias[n]) (+ R[z][m*ldr+n]); fp32 MFMA.
- * epilogue: 0 = none, 1 = exact-erf GELU, 2 = add residual R.  K % 32 == 0; lda/ldw/ldc/ldr % 4 == 0.
+ * epilogue: 0 = none, 1 = exact-erf GELU, 2 = add residual R, 5 = tanh GELU (GPT-2's gelu_new).  K % 32 == 0; lda/ldw/ldc/ldr % 4 == 0.
  * z = z1*nb2 + z2 walks nb1*nb2 problems with element strides (sA1,sA2), (sC1,sC2) (R uses C's). */
 int loco_op_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* R, int64_t ldr,
                  float* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t nb1, int32_t nb2,
@@ -751,6 +751,60 @@ size_t loco_vad_workspace_bytes(int64_t F);
 int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream);
 int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
                          int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- language model: GPT-2 token negative log-likelihoods (lm.hip, lm_api.hip) --------------------------------------------------
+ * The scorer of the reference's lms/ half: nll[b, s] = -log P(token s + 1 | tokens 0 .. s) under GPT-2 base (12 x 768 x 12 heads of 64
+ * x 3072, checkpoint "gpt2"; any other width is refused by loco_lm_create with LOCO_E_INVALID naming the field -- gpt2-medium, -large
+ * and -xl are out of scope).  Pre-LN blocks on the exact-fp32 GEMM (epilogue 5 = gelu_new for mlp.c_fc), the LayerNorm and the causal
+ * wave-per-row attention the decoder uses (scale 1/8, key counts lens[b], no bias table), then ln_f and the tied LM head.
+ *
+ * Weights: loco_lm_set_weight takes HF's GPT2LMHeadModel names with or without the "transformer." prefix, fp32 on the device, and
+ *   copies them (the handle owns its copies).  Conv1D weights come as HF stores them, [in, out]; loco_lm_finalize transposes them once.
+ *   "*.attn.bias", "*.attn.masked_bias" and "lm_head.weight" are accepted and ignored: the head is tied to wte, of which there is one copy
+ *   (a caller whose lm_head.weight differs from wte must refuse the checkpoint itself).  loco_lm_missing_weights returns the number of
+ *   tensors still missing and writes their comma-separated names.
+ * Sequences: `tokens` is ONE 1-D int32 device buffer -- a recording, or a corpus's utterances end to end; sequence b of a call is
+ *   tokens[starts[b] .. starts[b] + lens[b]), starts / lens int32 [B] on the device, 0 <= lens[b] <= S <= n_positions <= 1024, position
+ *   s of the model = offset s of the sequence.  Windows and ragged batches are thus formed on the device; rows beyond lens[b] embed as
+ *   zeros and are never attended to.  The caller guarantees that starts[b] + lens[b] stays inside tokens.
+ * Workspace: loco_lm_workspace_bytes(lm, B, S, R) bytes (R = 0 for loco_lm_forward), caller-owned; 0 for arguments outside the limits.
+ *   Its first int32 is a status word: LOCO_LM_STATUS_CLEAN after a forward whose ids were all inside [0, vocab), else the smallest index
+ *   into `tokens` of an id that was not (that token embedded as zeros); read it after the stream has completed the call.
+ * loco_lm_nll: rows int32 [R] on the device are flat indices b * S + s of the positions to score; nll_out[r] scores position (b, s)
+ *   against token s + 1 of sequence b, 0 where s + 1 >= lens[b], NaN for a row index outside [0, B S).  Only these R rows go through ln_f
+ *   and the head, and the [R, vocab] logits are never formed: the head keeps a running (max, sum of exp, target logit) per row and
+ *   vocabulary chunk of 1024 and merges a row's chunks in ascending order.  nll_out[r] is a function of that row's hidden state, its target
+ *   and the weights alone, bit for bit: it does not depend on R or on r.
+ * loco_lm_forward: for tests and small calls -- hidden_states (or NULL) are n_layer + 1 device pointers [B, S, 768] (each may be NULL):
+ *   the embedding output, the residual stream after blocks 0 .. n_layer - 2, and ln_f of the last block's output, HF's
+ *   output_hidden_states; logits (or NULL) [B, S, ldv] with ldv = loco_lm_vocab_stride (vocab rounded up to 4; columns >= vocab are 0),
+ *   by the plain GEMM on wte.  B * S * ldv must stay below 2^31.
+ * Operators (parity tests): loco_op_lm_head_nll is the head alone on h [R, 768] (already through ln_f) and targets int32 [R] (0 for
+ *   ignore_index, NaN for another target outside [0, V)); V need not be a multiple of anything, columns >= V and rows >= R are never read;
+ *   scratch >= loco_lm_head_scratch_bytes(R, V).  loco_op_lm_embed is the embedding (status: int32 [1] the caller set to
+ *   LOCO_LM_STATUS_CLEAN, or NULL).  loco_op_lm_group_mean: mean[g] (double) of nll[offsets[g] .. offsets[g + 1]) summed in double in a
+ *   fixed order, ppl[g] = exp(mean[g]); offsets int32 [G + 1] on the device.  loco_op_gemm's epilogue 5 is gelu_new. */
+#define LOCO_LM_MAX_POSITIONS 1024
+#define LOCO_LM_IGNORE_INDEX (-100)
+#define LOCO_LM_STATUS_CLEAN 0x7f7f7f7f
+typedef struct loco_lm loco_lm;
+loco_lm* loco_lm_create(int32_t n_layer, int32_t n_positions, int32_t vocab, int32_t n_embd, int32_t n_head);
+void loco_lm_destroy(loco_lm* lm);
+int loco_lm_set_weight(loco_lm* lm, const char* hf_key, const void* dev_ptr, const int64_t* shape, int ndim);
+int loco_lm_missing_weights(loco_lm* lm, char* names, size_t capacity);
+int loco_lm_finalize(loco_lm* lm, void* stream);
+int32_t loco_lm_vocab_stride(loco_lm* lm);
+size_t loco_lm_workspace_bytes(loco_lm* lm, int32_t B, int32_t S, int32_t R);
+int loco_lm_nll(loco_lm* lm, const int32_t* tokens, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, const int32_t* rows, int32_t R,
+                float* nll_out, void* workspace, size_t workspace_bytes, void* stream);
+int loco_lm_forward(loco_lm* lm, const int32_t* tokens, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, float* const* hidden_states,
+                    float* logits, void* workspace, size_t workspace_bytes, void* stream);
+size_t loco_lm_head_scratch_bytes(int64_t R, int32_t V);
+int loco_op_lm_head_nll(const float* h, int64_t ldh, const float* wte, int64_t ldw, const int32_t* targets, int64_t R, int32_t V, int32_t ignore_index,
+                        float* nll, void* scratch, size_t scratch_bytes, void* stream);
+int loco_op_lm_embed(const int32_t* tokens, const int32_t* starts, const int32_t* lens, const float* wte, int32_t V, const float* wpe, float* x,
+                     int32_t B, int32_t S, int32_t* status, void* stream);
+int loco_op_lm_group_mean(const float* nll, const int32_t* offsets, int32_t G, double* mean, double* ppl, void* stream);
 
 #ifdef __cplusplus
 }

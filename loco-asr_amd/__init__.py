@@ -10,6 +10,8 @@ from ._lib import LIB_PATH, LocoError  # noqa: F401
 from .encoder import BaseModelOutput, Pack, SpeechT5EncoderWithSpeechPrenetMI355X, sinusoid_table  # noqa: F401
 from .feature_extractor import BatchFeature, SpeechT5FeatureExtractorMI355X  # noqa: F401
 from .intent_head import IntentClassifierMI355X  # noqa: F401
+from . import lm  # noqa: F401
+from .lm import GPT2LMHeadModelMI355X  # noqa: F401
 from . import segment  # noqa: F401
 from .segment import LongSegment, LongTranscript, Segments, VadParams  # noqa: F401
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X  # noqa: F401
@@ -19,4 +21,4 @@ from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextT
 __all__ = ["synth", "LIB_PATH", "LocoError", "BaseModelOutput", "Pack", "SpeechT5EncoderWithSpeechPrenetMI355X",
            "SpeechT5ForSpeechToTextMI355X", "sinusoid_table", "BatchFeature", "SpeechT5FeatureExtractorMI355X", "IntentClassifierMI355X",
            "SpeechT5EncoderWithTextPrenetMI355X", "SpeechT5ForTextToSpeechMI355X", "scaled_positional_table", "segment", "VadParams", "Segments",
-           "LongSegment", "LongTranscript"]
+           "LongSegment", "LongTranscript", "lm", "GPT2LMHeadModelMI355X"]

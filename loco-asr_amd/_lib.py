@@ -156,6 +156,19 @@ SIGNATURES = {
     "loco_vad_workspace_bytes": (_sz, [_i64]),
     "loco_op_frame_energy_db": (C.c_int, [_vp, _i64, _vp, _vp]),
     "loco_op_vad_segments": (C.c_int, [_vp, _i64, C.POINTER(LocoVadParams), _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "loco_lm_create": (_vp, [_i32, _i32, _i32, _i32, _i32]),
+    "loco_lm_destroy": (None, [_vp]),
+    "loco_lm_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), C.c_int]),
+    "loco_lm_missing_weights": (C.c_int, [_vp, C.c_char_p, _sz]),
+    "loco_lm_finalize": (C.c_int, [_vp, _vp]),
+    "loco_lm_vocab_stride": (_i32, [_vp]),
+    "loco_lm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "loco_lm_nll": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "loco_lm_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    "loco_lm_head_scratch_bytes": (_sz, [_i64, _i32]),
+    "loco_op_lm_head_nll": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "loco_op_lm_embed": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "loco_op_lm_group_mean": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

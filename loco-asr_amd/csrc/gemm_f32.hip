@@ -225,6 +225,10 @@ __global__ __launch_bounds__(kGemmThreads, 2) void gemm_f32_kernel(GemmArgs p, i
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
                     }
+                    if (EPI == kEpiGeluNew) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = gelu_new(v[e]);
+                    }
                     if (EPI == kEpiResidual) v += *reinterpret_cast<const f32x4*>(R + (long)m * p.ldr + n);
                     *reinterpret_cast<f32x4*>(C + (long)m * p.ldc + n) = v;
                 }
@@ -252,6 +256,9 @@ hipError_t launch_gemm(const GemmArgs& a, hipStream_t s) {
             break;
         case kEpiGelu:
             hipLaunchKernelGGL((gemm_f32_kernel<kEpiGelu>), grid, block, 0, s, a, tiles_m, tiles_n, (int)nblk);
+            break;
+        case kEpiGeluNew:
+            hipLaunchKernelGGL((gemm_f32_kernel<kEpiGeluNew>), grid, block, 0, s, a, tiles_m, tiles_n, (int)nblk);
             break;
         case kEpiResidual:
             if (!a.R) return hipErrorInvalidValue;

@@ -30,7 +30,10 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
+}  // namespace
+
+namespace loco {
+int api_fail(int code, const char* fmt, ...) {  // declared in loco_kernels.h: lm_api.hip reports through the same string
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -39,6 +42,11 @@ int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
+}  // namespace loco
+
+namespace {
+
+constexpr auto& fail = loco::api_fail;
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \

@@ -25,7 +25,7 @@ constexpr int kQkv = 3 * kHidden;
 constexpr size_t kSplitKBytes = (size_t)256 * 256 * 128 * sizeof(float);
 constexpr int kSplitKMaxM = 8192;
 
-enum Epilogue { kEpiNone = 0, kEpiGelu = 1, kEpiResidual = 2, kEpiQkvScatter = 3, kEpiPosConv = 4 };
+enum Epilogue { kEpiNone = 0, kEpiGelu = 1, kEpiResidual = 2, kEpiQkvScatter = 3, kEpiPosConv = 4, kEpiGeluNew = 5 };
 
 struct GemmArgs {
     const float* A;
@@ -227,6 +227,16 @@ __device__ __forceinline__ float gelu_erf(float x) {
     // the clamp of the negative branch is a compare + select, not fmaxf: fmaxf(NaN, c) = c would launder a NaN input into a finite
     // number (HF's GELU propagates it, and the forward's finite check must see it)
     return x >= 0.f ? x * (1.0f - h) : (x < -kSMax ? -kSMax : x) * h;
+}
+
+// GPT-2's tanh GELU ("gelu_new", HF transformers/activations.py NewGELUActivation): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3).
+// tanh goes through exp2: tanh(u) = 1 - 2 / (1 + e^(2u)), so 0.5 (1 + tanh(u)) = 1 / (1 + e^(-2u)) and the result is x / (1 + 2^(-2 log2(e) u)).
+// The exponential saturates to 0 or +inf, never inf / inf: tanh is exactly +-1 from |u| ~ 44 on, large positive x returns x, large negative
+// finite x returns -0, and there is no 1 - tanh cancellation in the negative tail.  No fmaxf / fminf anywhere (see gelu_erf): NaN comes out
+// as NaN, and so does -inf (HF's own -inf * 0), +inf as +inf.
+__device__ __forceinline__ float gelu_new(float x) {
+    const float u = 0.7978845608028654f * fmaf(0.044715f * x, x * x, x);
+    return x / (1.0f + __builtin_amdgcn_exp2f(-2.885390081777927f * u));
 }
 
 // fp16 hi/lo split of two value pairs (a0,a1) and (b0,b1): hi = fp16(x) (hipcc emits one v_cvt_pk_f16_f32 per pair),
@@ -438,6 +448,29 @@ size_t vad_workspace_bytes(long F);
 // f32 [1] (+inf: silent recording, -inf: no usable silence), all on the device; ws >= vad_workspace_bytes(F)
 hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
                                void* ws, hipStream_t s);
+
+// ---- GPT-2 language-model scorer (lm.hip) ----
+constexpr int kLmChunk = 1024;  // vocabulary columns of one lm_head_nll workgroup: fixed, part of the result's bits
+int lm_head_chunks(int V);
+size_t lm_head_scratch_bytes(long R, int V);
+// nll[r] = logsumexp_{v < V}(h[r] . wte[v]) - h[r] . wte[targets[r]]; 0 where targets[r] == ignore_index, NaN for another target outside
+// [0, V).  h [R, 768] (row stride ldh), wte [V, 768] (row stride ldw); scratch >= lm_head_scratch_bytes(R, V).  A row's result does not
+// depend on R or on the row's index.
+hipError_t launch_lm_head_nll(const float* h, long ldh, const float* wte, long ldw, const int32_t* targets, long R, int V, int ignore_index,
+                              float* nll, void* scratch, hipStream_t s);
+// x[b,s,:] = wte[tokens[start[b] + s]] + wpe[s] for s < len[b], zeros beyond; an id outside [0, V) embeds as zeros and lowers status[0]
+// (optional; the caller sets it to INT_MAX) to its position in tokens
+hipError_t launch_lm_embed(const int32_t* tokens, const int32_t* start, const int32_t* len, const float* wte, int V, const float* wpe, float* x,
+                           int B, int S, int32_t* status, hipStream_t s);
+// out[r,:] = x[rows[r],:] (rows = b S + s) and targets[r] = tokens[start[b] + s + 1], ignore_index where s + 1 >= len[b]
+hipError_t launch_lm_gather(const float* x, const int32_t* rows, const int32_t* tokens, const int32_t* start, const int32_t* len, int B, int S,
+                            int R, int ignore_index, float* out, int32_t* targets, hipStream_t s);
+hipError_t launch_lm_transpose(const float* in, float* out, int rows, int cols, hipStream_t s);  // out[c][r] = in[r][c]
+// mean[g] (double) = mean of nll[offsets[g] .. offsets[g + 1]) summed in double in an order that depends on the two offsets only; ppl = exp
+hipError_t launch_lm_group_mean(const float* nll, const int32_t* offsets, int G, double* mean, double* ppl, hipStream_t s);
+
+// the C ABI's error string (loco_last_error) for translation units other than loco_api.hip
+int api_fail(int code, const char* fmt, ...);
 
 inline long conv_out_len(long n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 

@@ -328,3 +328,48 @@ def split_decoder_state_dict(sd: dict):
     dec = {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
     post = {k[len("text_decoder_postnet."):]: v for k, v in sd.items() if k.startswith("text_decoder_postnet.")}
     return dec, post
+
+
+# ---- GPT-2 language model (GPT2LMHeadModel) ---------------------------------------------------------------------------------------
+GPT2_VOCAB = 50257
+GPT2_POSITIONS = 1024
+
+
+def gpt2_state_dict(seed: int = 0, n_layer: int = LAYERS, n_positions: int = GPT2_POSITIONS, vocab: int = GPT2_VOCAB,
+                    logit_scale: float = 3.0) -> dict[str, np.ndarray]:
+    """numpy fp32 weights under HF's ``GPT2LMHeadModel.state_dict()`` names (``transformer.*`` and the tied ``lm_head.weight``, the
+    SAME array as ``transformer.wte.weight``).  Conv1D weights are ``[in, out]`` as HF stores them.  ``logit_scale`` is the standard
+    deviation the logits of a row come out with, roughly: ln_f's output has unit variance per channel, so wte is drawn with standard
+    deviation ``logit_scale / sqrt(768)``.  HF's own initialisation (0.02) gives logits of deviation 0.5, a flat softmax and an NLL of
+    ln(vocab) for every token, which tests nothing.  The other scales follow the encoder's generator: attention logits of deviation ~2,
+    LayerNorm affines that are not the identity, sub-layer outputs of the size of the residual they are added to."""
+    sd: dict[str, np.ndarray] = {}
+    t = "transformer."
+    wte = _w(t + "wte.weight", (vocab, HIDDEN), logit_scale / math.sqrt(HIDDEN), seed)
+    sd[t + "wte.weight"] = wte
+    sd[t + "wpe.weight"] = _w(t + "wpe.weight", (n_positions, HIDDEN), 0.05, seed)
+    for l in range(n_layer):
+        b = f"{t}h.{l}."
+        for ln in ("ln_1", "ln_2"):
+            sd[f"{b}{ln}.weight"] = _w(f"{b}{ln}.weight", (HIDDEN,), 0.1, seed, 1.0)
+            sd[f"{b}{ln}.bias"] = _w(f"{b}{ln}.bias", (HIDDEN,), 0.1, seed)
+        qkv = _w(b + "attn.c_attn.weight", (HIDDEN, 3 * HIDDEN), 1.5 / math.sqrt(HIDDEN), seed)
+        qkv[:, 2 * HIDDEN:] *= np.float32(1.0 / 1.5)
+        sd[b + "attn.c_attn.weight"] = qkv
+        sd[b + "attn.c_attn.bias"] = _w(b + "attn.c_attn.bias", (3 * HIDDEN,), 0.02, seed)
+        sd[b + "attn.c_proj.weight"] = _w(b + "attn.c_proj.weight", (HIDDEN, HIDDEN), 0.15 / math.sqrt(HIDDEN), seed)
+        sd[b + "attn.c_proj.bias"] = _w(b + "attn.c_proj.bias", (HIDDEN,), 0.02, seed)
+        sd[b + "mlp.c_fc.weight"] = _w(b + "mlp.c_fc.weight", (HIDDEN, FFN), 1.2 / math.sqrt(HIDDEN), seed)
+        sd[b + "mlp.c_fc.bias"] = _w(b + "mlp.c_fc.bias", (FFN,), 0.02, seed)
+        sd[b + "mlp.c_proj.weight"] = _w(b + "mlp.c_proj.weight", (FFN, HIDDEN), 0.2 / math.sqrt(FFN), seed)
+        sd[b + "mlp.c_proj.bias"] = _w(b + "mlp.c_proj.bias", (HIDDEN,), 0.02, seed)
+    sd[t + "ln_f.weight"] = _w(t + "ln_f.weight", (HIDDEN,), 0.1, seed, 1.0)
+    sd[t + "ln_f.bias"] = _w(t + "ln_f.bias", (HIDDEN,), 0.1, seed)
+    sd["lm_head.weight"] = wte
+    return sd
+
+
+def gpt2_token_ids(n: int, vocab: int = GPT2_VOCAB, tag: str = "ids", seed: int = 7) -> np.ndarray:
+    """n deterministic token ids in [0, vocab), int64."""
+    u = hashed_uniform(f"gpt2_ids/{tag}/{vocab}", (n,), seed)
+    return np.floor((u.astype(np.float64) + 1.0) * 0.5 * vocab).astype(np.int64).clip(0, vocab - 1)
