@@ -9,16 +9,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/loco_asr.h"
-#include "loco_kernels.h"
+#include "loco_host.h"
 
 using namespace loco;
-
-#define LM_HIP_TRY(expr)                                                                                  \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return api_fail(LOCO_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+using namespace loco::host;
 
 namespace {
 
@@ -45,8 +39,6 @@ struct loco_lm {
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct LmWorkspace {
     int32_t* status;
     float *x, *ln, *qkv, *ffn, *attn, *hsel;
@@ -60,7 +52,7 @@ LmWorkspace carve(const loco_lm* lm, void* base, int B, int S, int R) {
     size_t off = 0;
     auto take = [&](size_t n) {
         char* q = p + off;
-        off += align256(n);
+        off += align_up(n);
         return q;
     };
     const size_t rows = (size_t)B * S;
@@ -92,25 +84,25 @@ int lm_body(const loco_lm* lm, const int32_t* tokens, const int32_t* starts, con
             float* const* hidden, hipStream_t st) {
     const int M = B * S;
     const size_t row_bytes = (size_t)M * kHidden * sizeof(float);
-    LM_HIP_TRY(hipMemsetAsync(w.status, 0x7f, 256, st));
-    LM_HIP_TRY(launch_lm_embed(tokens, starts, lens, lm->wte, lm->vocab, lm->wpe, w.x, B, S, w.status, st));
-    if (hidden && hidden[0]) LM_HIP_TRY(hipMemcpyAsync(hidden[0], w.x, row_bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(w.status, 0x7f, 256, st));
+    HIP_TRY(launch_lm_embed(tokens, starts, lens, lm->wte, lm->vocab, lm->wpe, w.x, B, S, w.status, st));
+    if (hidden && hidden[0]) HIP_TRY(hipMemcpyAsync(hidden[0], w.x, row_bytes, hipMemcpyDeviceToDevice, st));
     auto gemm = [&](const float* A, const float* W, const float* bias, const float* R, float* C, int N, int K, int epi) {
         GemmArgs a{A, W, bias, R, C, M, N, K, K, K, N, N, 1, 1, 0, 0, 0, 0, epi};
         return launch_gemm(a, st);
     };
     for (int l = 0; l < lm->n_layer; ++l) {
         const LmLayerW& W = lm->L[l];
-        LM_HIP_TRY(launch_layernorm(w.x, W.ln1_w, W.ln1_b, w.ln, M, kHidden, 1e-5f, st));
-        LM_HIP_TRY(gemm(w.ln, W.wqkv, W.bqkv, nullptr, w.qkv, kQkv, kHidden, kEpiNone));
+        HIP_TRY(launch_layernorm(w.x, W.ln1_w, W.ln1_b, w.ln, M, kHidden, 1e-5f, st));
+        HIP_TRY(gemm(w.ln, W.wqkv, W.bqkv, nullptr, w.qkv, kQkv, kHidden, kEpiNone));
         // causal, key counts lens[b], scale 1/8, no bias table; right padding needs no other mask
-        LM_HIP_TRY(launch_dec_attention(w.qkv, kQkv, (long)S * kQkv, w.qkv + kHidden, kQkv, (long)S * kQkv, w.qkv + 2 * kHidden, kQkv, (long)S * kQkv, lens,
+        HIP_TRY(launch_dec_attention(w.qkv, kQkv, (long)S * kQkv, w.qkv + kHidden, kQkv, (long)S * kQkv, w.qkv + 2 * kHidden, kQkv, (long)S * kQkv, lens,
                                         w.ln, kHidden, (long)S * kHidden, B, S, S, 1, 0, 0.125f, w.attn, st));
-        LM_HIP_TRY(gemm(w.ln, W.wo, W.bo, w.x, w.x, kHidden, kHidden, kEpiResidual));
-        LM_HIP_TRY(launch_layernorm(w.x, W.ln2_w, W.ln2_b, w.ln, M, kHidden, 1e-5f, st));
-        LM_HIP_TRY(gemm(w.ln, W.wfc, W.bfc, nullptr, w.ffn, kFfn, kHidden, kEpiGeluNew));
-        LM_HIP_TRY(gemm(w.ffn, W.wproj, W.bproj, w.x, w.x, kHidden, kFfn, kEpiResidual));
-        if (hidden && l + 1 < lm->n_layer && hidden[l + 1]) LM_HIP_TRY(hipMemcpyAsync(hidden[l + 1], w.x, row_bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(gemm(w.ln, W.wo, W.bo, w.x, w.x, kHidden, kHidden, kEpiResidual));
+        HIP_TRY(launch_layernorm(w.x, W.ln2_w, W.ln2_b, w.ln, M, kHidden, 1e-5f, st));
+        HIP_TRY(gemm(w.ln, W.wfc, W.bfc, nullptr, w.ffn, kFfn, kHidden, kEpiGeluNew));
+        HIP_TRY(gemm(w.ffn, W.wproj, W.bproj, w.x, w.x, kHidden, kFfn, kEpiResidual));
+        if (hidden && l + 1 < lm->n_layer && hidden[l + 1]) HIP_TRY(hipMemcpyAsync(hidden[l + 1], w.x, row_bytes, hipMemcpyDeviceToDevice, st));
     }
     return LOCO_OK;
 }
@@ -203,10 +195,10 @@ int loco_lm_set_weight(loco_lm* lm, const char* hf_key, const void* dev_ptr, con
     const size_t alloc = key == "wte.weight" ? (size_t)lm->ldv * kHidden : count;
     float*& buf = lm->raw[key];
     if (!buf) {
-        LM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), alloc * sizeof(float)));
-        if (alloc > count) LM_HIP_TRY(hipMemset(buf + count, 0, (alloc - count) * sizeof(float)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), alloc * sizeof(float)));
+        if (alloc > count) HIP_TRY(hipMemset(buf + count, 0, (alloc - count) * sizeof(float)));
     }
-    LM_HIP_TRY(hipMemcpy(buf, dev_ptr, count * sizeof(float), hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(buf, dev_ptr, count * sizeof(float), hipMemcpyDeviceToDevice));
     lm->ready = false;
     return LOCO_OK;
 }
@@ -248,12 +240,12 @@ int loco_lm_finalize(loco_lm* lm, void* stream) {
                                                                                  {"mlp.c_fc.weight", &W.wfc, kHidden, kFfn},
                                                                                  {"mlp.c_proj.weight", &W.wproj, kFfn, kHidden}};
         for (const auto& m : mats) {  // HF Conv1D [in, out] -> the GEMM's [N = out, K = in]
-            if (!*m.dst) LM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(m.dst), (size_t)m.in * m.out * sizeof(float)));
-            LM_HIP_TRY(launch_lm_transpose(get(p + m.name), *m.dst, m.in, m.out, st));
+            if (!*m.dst) HIP_TRY(hipMalloc(reinterpret_cast<void**>(m.dst), (size_t)m.in * m.out * sizeof(float)));
+            HIP_TRY(launch_lm_transpose(get(p + m.name), *m.dst, m.in, m.out, st));
             done.push_back(p + m.name);
         }
     }
-    LM_HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (const auto& k : done) {  // the [in, out] originals are not read again
         (void)hipFree(lm->raw[k]);
         lm->raw.erase(k);
@@ -280,9 +272,9 @@ int loco_lm_nll(loco_lm* lm, const int32_t* tokens, const int32_t* starts, const
     hipStream_t st = (hipStream_t)stream;
     if (const int rc = lm_body(lm, tokens, starts, lens, B, S, w, nullptr, st)) return rc;
     // only the rows that are scored go through ln_f and the head
-    LM_HIP_TRY(launch_lm_gather(w.x, rows, tokens, starts, lens, B, S, R, LOCO_LM_IGNORE_INDEX, w.hsel, w.targets, st));
-    LM_HIP_TRY(launch_layernorm(w.hsel, lm->lnf_w, lm->lnf_b, w.hsel, R, kHidden, 1e-5f, st));
-    LM_HIP_TRY(launch_lm_head_nll(w.hsel, kHidden, lm->wte, kHidden, w.targets, R, lm->vocab, LOCO_LM_IGNORE_INDEX, nll_out, w.part, st));
+    HIP_TRY(launch_lm_gather(w.x, rows, tokens, starts, lens, B, S, R, LOCO_LM_IGNORE_INDEX, w.hsel, w.targets, st));
+    HIP_TRY(launch_layernorm(w.hsel, lm->lnf_w, lm->lnf_b, w.hsel, R, kHidden, 1e-5f, st));
+    HIP_TRY(launch_lm_head_nll(w.hsel, kHidden, lm->wte, kHidden, w.targets, R, lm->vocab, LOCO_LM_IGNORE_INDEX, nll_out, w.part, st));
     return LOCO_OK;
 }
 
@@ -299,11 +291,11 @@ int loco_lm_forward(loco_lm* lm, const int32_t* tokens, const int32_t* starts, c
     const int M = B * S;
     float* last = hidden_states ? hidden_states[lm->n_layer] : nullptr;
     if (!last && !logits) return LOCO_OK;
-    LM_HIP_TRY(launch_layernorm(w.x, lm->lnf_w, lm->lnf_b, w.ln, M, kHidden, 1e-5f, st));
-    if (last) LM_HIP_TRY(hipMemcpyAsync(last, w.ln, (size_t)M * kHidden * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(launch_layernorm(w.x, lm->lnf_w, lm->lnf_b, w.ln, M, kHidden, 1e-5f, st));
+    if (last) HIP_TRY(hipMemcpyAsync(last, w.ln, (size_t)M * kHidden * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (logits) {
         GemmArgs a{w.ln, lm->wte, nullptr, nullptr, logits, M, lm->ldv, kHidden, kHidden, kHidden, lm->ldv, 0, 1, 1, 0, 0, 0, 0, kEpiNone};
-        LM_HIP_TRY(launch_gemm(a, st));
+        HIP_TRY(launch_gemm(a, st));
     }
     return LOCO_OK;
 }
@@ -318,7 +310,7 @@ int loco_op_lm_head_nll(const float* h, int64_t ldh, const float* wte, int64_t l
     if (ldh < kHidden || ldw < kHidden || ((ldh | ldw) & 3)) return api_fail(LOCO_E_INVALID, "%s: row strides must be >= 768 floats and multiples of 4", fn);
     if (scratch_bytes < lm_head_scratch_bytes((long)R, V))
         return api_fail(LOCO_E_WORKSPACE, "%s: scratch %zu < %zu bytes", fn, scratch_bytes, lm_head_scratch_bytes((long)R, V));
-    LM_HIP_TRY(launch_lm_head_nll(h, (long)ldh, wte, (long)ldw, targets, (long)R, V, ignore_index, nll, scratch, (hipStream_t)stream));
+    HIP_TRY(launch_lm_head_nll(h, (long)ldh, wte, (long)ldw, targets, (long)R, V, ignore_index, nll, scratch, (hipStream_t)stream));
     return LOCO_OK;
 }
 
@@ -327,13 +319,13 @@ int loco_op_lm_embed(const int32_t* tokens, const int32_t* starts, const int32_t
     const char* fn = "loco_op_lm_embed";
     if (!tokens || !starts || !lens || !wte || !wpe || !x) return api_fail(LOCO_E_INVALID, "%s: null argument", fn);
     if (B < 1 || B > 65535 || S < 1 || V < 1) return api_fail(LOCO_E_INVALID, "%s: B = %d (1 .. 65535), S = %d, V = %d must be >= 1", fn, B, S, V);
-    LM_HIP_TRY(launch_lm_embed(tokens, starts, lens, wte, V, wpe, x, B, S, status, (hipStream_t)stream));
+    HIP_TRY(launch_lm_embed(tokens, starts, lens, wte, V, wpe, x, B, S, status, (hipStream_t)stream));
     return LOCO_OK;
 }
 
 int loco_op_lm_group_mean(const float* nll, const int32_t* offsets, int32_t G, double* mean, double* ppl, void* stream) {
     if (!nll || !offsets || !mean || !ppl || G < 1) return api_fail(LOCO_E_INVALID, "loco_op_lm_group_mean: null argument or G < 1");
-    LM_HIP_TRY(launch_lm_group_mean(nll, offsets, G, mean, ppl, (hipStream_t)stream));
+    HIP_TRY(launch_lm_group_mean(nll, offsets, G, mean, ppl, (hipStream_t)stream));
     return LOCO_OK;
 }
 

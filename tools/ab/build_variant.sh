@@ -8,8 +8,8 @@ src=$here/../../loco-asr_amd/csrc
 out=$here/_build_$name
 mkdir -p $out
 flags="$(sed -n 's/^CXXFLAGS ?= //p' $src/Makefile | sed 's/$(ARCH)/gfx950/') $(sed -n 's/^override CXXFLAGS += //p' $src/Makefile)"
-for f in gemm_f32 gemm_f16x3 attention_f32 attention_f16x3 conv0_gn_gelu pos_conv norm_misc intent_head resample flac_decode loco_api; do
-  hipcc $flags "$@" -c $src/$f.hip -o $out/$f.o &
+for f in $(sed -n 's/^SRCS := //p' $src/Makefile); do  # the Makefile's own list: every translation unit of the library
+  hipcc $flags "$@" -c $src/$f -o $out/${f%.hip}.o &
 done
 wait
 hipcc --offload-arch=gfx950 -shared -fPIC -o $here/lib$name.so $out/*.o

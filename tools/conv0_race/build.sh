@@ -22,7 +22,18 @@ ls -la old_conv0.so
 CS=../../loco-asr_amd/csrc
 cp _old/conv0_gn_gelu.hip _old/conv0_old_for_current.hip
 sed -i 's#"loco_kernels.h"#"../../../loco-asr_amd/csrc/loco_kernels.h"#' _old/conv0_old_for_current.hip
+# the old launcher predates range tracking and the packed forward: today's signature in front of it, the two new arguments dropped
+cat >> _old/conv0_old_for_current.hip <<'EOC'
+namespace loco {
+hipError_t launch_conv0_gn_gelu(const float* wav, int B, long L, const float* w, const float* gn_w, const float* gn_b, float* out, void* scratch,
+                                float eps, hipStream_t s, void* out_hi, void* out_lo, float*, const int32_t*) {
+    using Old = hipError_t (*)(const float*, int, long, const float*, const float*, const float*, float*, void*, float, hipStream_t, void*, void*);
+    return static_cast<Old>(launch_conv0_gn_gelu)(wav, B, L, w, gn_w, gn_b, out, scratch, eps, s, out_hi, out_lo);
+}
+}  // namespace loco
+EOC
 hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -c _old/conv0_old_for_current.hip -o _old/conv0_old.o
 make -C $CS >/dev/null
-hipcc --offload-arch=gfx950 -shared -fPIC -o libloco_oldconv0.so $(for f in gemm_f32 gemm_f16x3 attention_f32 attention_f16x3 pos_conv norm_misc intent_head resample loco_api; do echo $CS/build/$f.o; done) _old/conv0_old.o
+# every object of the Makefile's SRCS but the current conv0
+hipcc --offload-arch=gfx950 -shared -fPIC -o libloco_oldconv0.so $(for f in $(sed -n 's/^SRCS := //p' $CS/Makefile); do [ $f = conv0_gn_gelu.hip ] || echo $CS/build/${f%.hip}.o; done) _old/conv0_old.o
 ls -la libloco_oldconv0.so

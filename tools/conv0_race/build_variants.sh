@@ -9,7 +9,8 @@
 set -e
 cd "$(dirname "$0")"
 CS=../../loco-asr_amd/csrc
-OBJS=$(for f in gemm_f32 gemm_f16x3 attention_f32 attention_f16x3 pos_conv norm_misc intent_head resample loco_api; do echo $CS/build/$f.o; done)
+# every object of the Makefile's SRCS but the current conv0 (built by build.sh's make)
+OBJS=$(for f in $(sed -n 's/^SRCS := //p' $CS/Makefile); do [ $f = conv0_gn_gelu.hip ] || echo $CS/build/${f%.hip}.o; done)
 python3 - <<'PY'
 src = open("_old/conv0_old_for_current.hip").read()
 def put(name, s):
