@@ -806,6 +806,45 @@ int loco_op_lm_embed(const int32_t* tokens, const int32_t* starts, const int32_t
                      int32_t B, int32_t S, int32_t* status, void* stream);
 int loco_op_lm_group_mean(const float* nll, const int32_t* offsets, int32_t G, double* mean, double* ppl, void* stream);
 
+/* ---- language model with a cached context (lm_attention.hip, lm_api.hip) --------------------------------------------------------
+ * A loco_lm_cache holds `slots` (1 .. 64) independent contexts: per slot and layer n_positions rows of k and of v in fp32, and the
+ * residual row of the slot's last token, which predicts the token that follows the context.  A slot's length is host-side state
+ * (loco_lm_cache_length: no synchronisation, -1 for a bad argument); it changes when a step is enqueued, so calls that share a cache must be
+ * enqueued on one stream, by one thread at a time.  loco_lm_cache_reset sets a length to 0 and touches no device memory.
+ *
+ * loco_lm_ctx_step runs the model on N (1 .. 64) sequences of GPT-2 ids, each behind the tokens its slot already holds.  `tokens` is one
+ * 1-D int32 device buffer, as for loco_lm_nll; `seqs` is a HOST array int32 [N][4] of (start, len, slot, flags): sequence n is
+ * tokens[start .. start + len), stands at positions P .. P + len - 1 with P = the slot's length, and attends to the slot's P tokens and
+ * causally to itself (csrc/lm_attention.hip).  flags:
+ *   LOCO_LM_CTX_SCORE   nll_out receives len values, nll[t] = -log P(ids[t] | slot tokens, ids[:t]); token 0 is predicted from the slot's
+ *                       stored last row and scores 0 on an empty slot.  The values of the scoring sequences are flat in sequence order.
+ *   LOCO_LM_CTX_COMMIT  the sequence's k / v rows of every layer are appended to the slot, its last row replaces the slot's, and the length
+ *                       grows by len.  At most one committing sequence per slot and call.
+ * Any number of sequences may read one slot (an n-best list); a slot changes only through a commit, and every sequence of a call sees
+ * the slots as they were before the call.  Refused by name before any launch: P + len > n_positions, len < 1, a slot out of range, two
+ * commits on one slot, a null argument, a workspace below loco_lm_ctx_workspace_bytes(lm, rows, N) (rows = the sum of len; 0 outside the
+ * limits).  The call allocates nothing, never synchronises and runs on the caller's stream; the workspace's first int32 is the status
+ * word of loco_lm_nll.
+ * Bits: a sequence's values are a function of its ids, its slot's contents and P alone -- not of N, of the sequences beside it or of the
+ * slot's index.  A context built in several commits and the same tokens committed at once partition the keys differently and agree to
+ * fp32 rounding, not to the bit; for a given chunking the result is bit-reproducible.
+ * loco_op_lm_ctx_attention is the attention kernel alone: qkv packed rows of q | k | v (row stride 2304), kcache / vcache
+ * [slots][rows][768] with slot_stride floats between slots, seqs a HOST array int32 [N][3] of (len, slot, P), out packed rows of 768. */
+#define LOCO_LM_CTX_SCORE 1
+#define LOCO_LM_CTX_COMMIT 2
+#define LOCO_LM_CTX_MAX_SEQS 64
+#define LOCO_LM_CACHE_MAX_SLOTS 64
+typedef struct loco_lm_cache loco_lm_cache;
+loco_lm_cache* loco_lm_cache_create(loco_lm* lm, int32_t slots);
+void loco_lm_cache_destroy(loco_lm_cache* cache);
+int loco_lm_cache_reset(loco_lm_cache* cache, int32_t slot);
+int32_t loco_lm_cache_length(loco_lm_cache* cache, int32_t slot);
+size_t loco_lm_ctx_workspace_bytes(loco_lm* lm, int32_t rows, int32_t N);
+int loco_lm_ctx_step(loco_lm* lm, loco_lm_cache* cache, const int32_t* tokens, const int32_t* seqs, int32_t N, float* nll_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int loco_op_lm_ctx_attention(const float* qkv, const float* kcache, const float* vcache, int64_t slot_stride, const int32_t* seqs, int32_t N,
+                             int32_t slots, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

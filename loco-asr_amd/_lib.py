@@ -169,6 +169,13 @@ SIGNATURES = {
     "loco_op_lm_head_nll": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "loco_op_lm_embed": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "loco_op_lm_group_mean": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "loco_lm_cache_create": (_vp, [_vp, _i32]),
+    "loco_lm_cache_destroy": (None, [_vp]),
+    "loco_lm_cache_reset": (C.c_int, [_vp, _i32]),
+    "loco_lm_cache_length": (_i32, [_vp, _i32]),
+    "loco_lm_ctx_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "loco_lm_ctx_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _i32, _vp, _vp, _sz, _vp]),
+    "loco_op_lm_ctx_attention": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_i32), _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

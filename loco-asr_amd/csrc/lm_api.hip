@@ -1,6 +1,7 @@
 // C ABI of the GPT-2 language-model scorer (include/loco_asr.h, "language model"): the handle, the two forward functions and the
 // operators of the parity tests.  The layer body is launch_layernorm / launch_gemm / launch_dec_attention as they stand; lm.hip has the
 // embedding, the row gather and the fused LM head.  Forwards allocate nothing, never synchronise and run on the caller's stream.
+// The cached-context half (loco_lm_cache_*, loco_lm_ctx_step) runs the same body with lm_attention.hip's prefix + causal attention.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -109,7 +110,183 @@ int lm_body(const loco_lm* lm, const int32_t* tokens, const int32_t* starts, con
 
 }  // namespace
 
+// K/V cache of the cached-context forward: per slot and layer n_positions rows of k and of v, and per slot the residual row of its last
+// token (what predicts the next one).  `length` is host-side state: it changes when a step is ENQUEUED, so calls on one stream see each
+// other's commits in order.
+struct loco_lm_cache {
+    loco_lm* lm = nullptr;
+    int slots = 0;
+    float *k = nullptr, *v = nullptr;  // [n_layer][slots][n_positions][768] each
+    float* last = nullptr;             // [slots][768]
+    std::vector<int32_t> length;
+};
+
+namespace {
+
+struct LmCtxWorkspace {
+    int32_t* status;
+    float *x, *ln, *qkv, *ffn, *hsel;
+    int32_t* targets;
+    void* part;
+    size_t bytes;
+};
+
+LmCtxWorkspace carve_ctx(const loco_lm* lm, void* base, int rows) {
+    char* p = static_cast<char*>(base);
+    size_t off = 0;
+    auto take = [&](size_t n) {
+        char* q = p + off;
+        off += align_up(n);
+        return q;
+    };
+    LmCtxWorkspace w;
+    w.status = reinterpret_cast<int32_t*>(take(256));
+    w.x = reinterpret_cast<float*>(take((size_t)rows * kHidden * sizeof(float)));
+    w.ln = reinterpret_cast<float*>(take((size_t)rows * kHidden * sizeof(float)));  // LayerNorm output, then the attention context
+    w.qkv = reinterpret_cast<float*>(take((size_t)rows * kQkv * sizeof(float)));
+    w.ffn = reinterpret_cast<float*>(take((size_t)rows * kFfn * sizeof(float)));
+    w.hsel = reinterpret_cast<float*>(take((size_t)rows * kHidden * sizeof(float)));  // at most every row is scored
+    w.targets = reinterpret_cast<int32_t*>(take((size_t)rows * sizeof(int32_t)));
+    w.part = take(lm_head_scratch_bytes(rows, lm->vocab));
+    w.bytes = off;
+    return w;
+}
+
+constexpr int kLmCtxMaxRows = kLmCtxMaxSeqs * LOCO_LM_MAX_POSITIONS;
+
+}  // namespace
+
 extern "C" {
+
+loco_lm_cache* loco_lm_cache_create(loco_lm* lm, int32_t slots) {
+    const char* fn = "loco_lm_cache_create";
+    if (!lm) {
+        api_fail(LOCO_E_INVALID, "%s: null handle", fn);
+        return nullptr;
+    }
+    if (slots < 1 || slots > LOCO_LM_CACHE_MAX_SLOTS) {
+        api_fail(LOCO_E_INVALID, "%s: slots = %d is outside 1 .. %d", fn, slots, LOCO_LM_CACHE_MAX_SLOTS);
+        return nullptr;
+    }
+    loco_lm_cache* c = new loco_lm_cache;
+    c->lm = lm, c->slots = slots;
+    c->length.assign(slots, 0);
+    const size_t plane = (size_t)lm->n_layer * slots * lm->n_positions * kHidden * sizeof(float);
+    if (hipMalloc(reinterpret_cast<void**>(&c->k), plane) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&c->v), plane) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->last), (size_t)slots * kHidden * sizeof(float)) != hipSuccess) {
+        api_fail(LOCO_E_HIP, "%s: hipMalloc of 2 x %zu bytes failed", fn, plane);
+        loco_lm_cache_destroy(c);
+        return nullptr;
+    }
+    return c;
+}
+
+void loco_lm_cache_destroy(loco_lm_cache* c) {
+    if (!c) return;
+    for (float* p : {c->k, c->v, c->last})
+        if (p) (void)hipFree(p);
+    delete c;
+}
+
+int loco_lm_cache_reset(loco_lm_cache* c, int32_t slot) {
+    if (!c) return api_fail(LOCO_E_INVALID, "loco_lm_cache_reset: null handle");
+    if (slot < 0 || slot >= c->slots) return api_fail(LOCO_E_INVALID, "loco_lm_cache_reset: slot = %d is outside 0 .. %d", slot, c->slots - 1);
+    c->length[slot] = 0;
+    return LOCO_OK;
+}
+
+int32_t loco_lm_cache_length(loco_lm_cache* c, int32_t slot) { return c && slot >= 0 && slot < c->slots ? c->length[slot] : -1; }
+
+size_t loco_lm_ctx_workspace_bytes(loco_lm* lm, int32_t rows, int32_t N) {
+    if (!lm || N < 1 || N > kLmCtxMaxSeqs || rows < N || rows > kLmCtxMaxRows || (long)rows > (long)N * lm->n_positions) return 0;
+    return carve_ctx(lm, nullptr, rows).bytes;
+}
+
+int loco_lm_ctx_step(loco_lm* lm, loco_lm_cache* cache, const int32_t* tokens, const int32_t* seqs, int32_t N, float* nll_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_lm_ctx_step";
+    if (!lm || !cache || !tokens || !seqs || !workspace) return api_fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (cache->lm != lm) return api_fail(LOCO_E_INVALID, "%s: the cache belongs to another model handle", fn);
+    if (!lm->ready) return api_fail(LOCO_E_STATE, "%s: weights not finalized (loco_lm_finalize)", fn);
+    if (N < 1 || N > kLmCtxMaxSeqs) return api_fail(LOCO_E_INVALID, "%s: N = %d is outside 1 .. %d", fn, N, kLmCtxMaxSeqs);
+    LmCtxSeqs s{};
+    s.n = N;
+    int rows = 0, R = 0;
+    unsigned long long committing = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t start = seqs[4 * n], len = seqs[4 * n + 1], slot = seqs[4 * n + 2], flags = seqs[4 * n + 3];
+        if (slot < 0 || slot >= cache->slots) return api_fail(LOCO_E_INVALID, "%s: sequence %d: slot = %d is outside 0 .. %d", fn, n, slot, cache->slots - 1);
+        if (len < 1) return api_fail(LOCO_E_INVALID, "%s: sequence %d: len = %d must be >= 1", fn, n, len);
+        if (start < 0) return api_fail(LOCO_E_INVALID, "%s: sequence %d: start = %d is negative", fn, n, start);
+        if (flags & ~(LOCO_LM_CTX_SCORE | LOCO_LM_CTX_COMMIT) || !flags)
+            return api_fail(LOCO_E_INVALID, "%s: sequence %d: flags = %d must be SCORE (1), COMMIT (2) or both", fn, n, flags);
+        const int P = cache->length[slot];
+        if (P + len > lm->n_positions)
+            return api_fail(LOCO_E_INVALID, "%s: sequence %d: P + len = %d + %d exceeds n_positions = %d (slot %d)", fn, n, P, len, lm->n_positions, slot);
+        if (flags & LOCO_LM_CTX_COMMIT) {
+            if (committing >> slot & 1) return api_fail(LOCO_E_INVALID, "%s: sequence %d: two committing sequences on slot %d in one call", fn, n, slot);
+            committing |= 1ull << slot;
+        }
+        s.row0[n] = rows, s.len[n] = len, s.slot[n] = slot, s.P[n] = P, s.tok0[n] = start, s.flags[n] = flags;
+        rows += len;
+        if (flags & LOCO_LM_CTX_SCORE) R += len;
+    }
+    if (R && !nll_out) return api_fail(LOCO_E_INVALID, "%s: null nll_out with a scoring sequence", fn);
+    const LmCtxWorkspace w = carve_ctx(lm, workspace, rows);
+    if (workspace_bytes < w.bytes) return api_fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, w.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const long slot_stride = (long)lm->n_positions * kHidden, layer_stride = slot_stride * cache->slots;
+    HIP_TRY(hipMemsetAsync(w.status, 0x7f, 256, st));
+    HIP_TRY(launch_lm_ctx_embed(tokens, s, lm->wte, lm->vocab, lm->wpe, w.x, w.status, st));
+    auto gemm = [&](const float* A, const float* W, const float* bias, const float* R_, float* C, int Nn, int K, int epi) {
+        GemmArgs a{A, W, bias, R_, C, rows, Nn, K, K, K, Nn, Nn, 1, 1, 0, 0, 0, 0, epi};
+        return launch_gemm(a, st);
+    };
+    for (int l = 0; l < lm->n_layer; ++l) {
+        const LmLayerW& W = lm->L[l];
+        float *kc = cache->k + l * layer_stride, *vc = cache->v + l * layer_stride;
+        HIP_TRY(launch_layernorm(w.x, W.ln1_w, W.ln1_b, w.ln, rows, kHidden, 1e-5f, st));
+        HIP_TRY(gemm(w.ln, W.wqkv, W.bqkv, nullptr, w.qkv, kQkv, kHidden, kEpiNone));
+        HIP_TRY(launch_lm_ctx_attention(w.qkv, kc, vc, slot_stride, s, w.ln, st));
+        if (committing) HIP_TRY(launch_lm_ctx_append(w.qkv, s, kc, vc, slot_stride, st));  // rows >= P: nothing this layer's attention read
+        HIP_TRY(gemm(w.ln, W.wo, W.bo, w.x, w.x, kHidden, kHidden, kEpiResidual));
+        HIP_TRY(launch_layernorm(w.x, W.ln2_w, W.ln2_b, w.ln, rows, kHidden, 1e-5f, st));
+        HIP_TRY(gemm(w.ln, W.wfc, W.bfc, nullptr, w.ffn, kFfn, kHidden, kEpiGeluNew));
+        HIP_TRY(gemm(w.ffn, W.wproj, W.bproj, w.x, w.x, kHidden, kFfn, kEpiResidual));
+    }
+    if (R) {  // only the scored rows go through ln_f and the head; the slots' last rows are read before a commit replaces them
+        HIP_TRY(launch_lm_ctx_gather(w.x, tokens, s, cache->last, R, LOCO_LM_IGNORE_INDEX, w.hsel, w.targets, st));
+        HIP_TRY(launch_layernorm(w.hsel, lm->lnf_w, lm->lnf_b, w.hsel, R, kHidden, 1e-5f, st));
+        HIP_TRY(launch_lm_head_nll(w.hsel, kHidden, lm->wte, kHidden, w.targets, R, lm->vocab, LOCO_LM_IGNORE_INDEX, nll_out, w.part, st));
+    }
+    if (committing) {
+        HIP_TRY(launch_lm_ctx_last(w.x, s, cache->last, st));
+        for (int n = 0; n < N; ++n)
+            if (s.flags[n] & LOCO_LM_CTX_COMMIT) cache->length[s.slot[n]] += s.len[n];
+    }
+    return LOCO_OK;
+}
+
+int loco_op_lm_ctx_attention(const float* qkv, const float* kcache, const float* vcache, int64_t slot_stride, const int32_t* seqs, int32_t N,
+                             int32_t slots, float* out, void* stream) {
+    const char* fn = "loco_op_lm_ctx_attention";
+    if (!qkv || !kcache || !vcache || !seqs || !out) return api_fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (N < 1 || N > kLmCtxMaxSeqs) return api_fail(LOCO_E_INVALID, "%s: N = %d is outside 1 .. %d", fn, N, kLmCtxMaxSeqs);
+    if (slots < 1 || slot_stride < kHidden || slot_stride % kHidden) return api_fail(LOCO_E_INVALID, "%s: slots = %d, slot_stride = %lld: need slots >= 1 and a stride of whole rows of 768", fn, slots, (long long)slot_stride);
+    LmCtxSeqs s{};
+    s.n = N;
+    int rows = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t len = seqs[3 * n], slot = seqs[3 * n + 1], P = seqs[3 * n + 2];
+        if (len < 1 || len > LOCO_LM_MAX_POSITIONS) return api_fail(LOCO_E_INVALID, "%s: sequence %d: len = %d is outside 1 .. %d", fn, n, len, LOCO_LM_MAX_POSITIONS);
+        if (slot < 0 || slot >= slots) return api_fail(LOCO_E_INVALID, "%s: sequence %d: slot = %d is outside 0 .. %d", fn, n, slot, slots - 1);
+        if (P < 0 || (long)P * kHidden > slot_stride) return api_fail(LOCO_E_INVALID, "%s: sequence %d: P = %d does not fit the slot's %lld rows", fn, n, P, (long long)(slot_stride / kHidden));
+        s.row0[n] = rows, s.len[n] = len, s.slot[n] = slot, s.P[n] = P;
+        rows += len;
+    }
+    HIP_TRY(launch_lm_ctx_attention(qkv, kcache, vcache, (long)slot_stride, s, out, (hipStream_t)stream));
+    return LOCO_OK;
+}
 
 loco_lm* loco_lm_create(int32_t n_layer, int32_t n_positions, int32_t vocab, int32_t n_embd, int32_t n_head) {
     if (n_embd != kHidden) {

@@ -469,6 +469,32 @@ hipError_t launch_lm_transpose(const float* in, float* out, int rows, int cols, 
 // mean[g] (double) = mean of nll[offsets[g] .. offsets[g + 1]) summed in double in an order that depends on the two offsets only; ppl = exp
 hipError_t launch_lm_group_mean(const float* nll, const int32_t* offsets, int G, double* mean, double* ppl, hipStream_t s);
 
+// ---- GPT-2 with a cached context (lm_attention.hip) ----
+constexpr int kLmCtxMaxSeqs = 64;  // sequences of one call
+constexpr int kLmCtxScore = 1, kLmCtxCommit = 2;
+// By value.  Sequence n owns packed rows [row0[n], row0[n] + len[n]) of the call's buffers (sequence order, no gaps), its ids are
+// tokens[tok0[n] ..], and it reads (and, with kLmCtxCommit, extends) cache slot slot[n], which holds P[n] tokens.
+struct LmCtxSeqs {
+    int n;
+    int32_t row0[kLmCtxMaxSeqs], len[kLmCtxMaxSeqs], slot[kLmCtxMaxSeqs], P[kLmCtxMaxSeqs], tok0[kLmCtxMaxSeqs], flags[kLmCtxMaxSeqs];
+};
+// out[row0[n] + t, 64 h ..] = softmax_j(q . k_j / 8) v_j over the slot's cached keys j < P[n] and the sequence's own keys t' <= t.  qkv:
+// packed rows of q | k | v (row stride 2304); kcache / vcache: [slot][position][768] with slot_stride floats between slots; out: row
+// stride 768.  A sequence's output does not depend on n, on the other sequences or on the slot's index.
+hipError_t launch_lm_ctx_attention(const float* qkv, const float* kcache, const float* vcache, long slot_stride, const LmCtxSeqs& seqs, float* out,
+                                   hipStream_t s);
+// x[row0[n] + t, :] = wte[tokens[tok0[n] + t]] + wpe[P[n] + t]; a bad id embeds as zeros and lowers status[0] to its index in tokens
+hipError_t launch_lm_ctx_embed(const int32_t* tokens, const LmCtxSeqs& seqs, const float* wte, int V, const float* wpe, float* x, int32_t* status,
+                               hipStream_t s);
+// the k | v rows of the sequences with kLmCtxCommit -> cache positions P[n] + t of their slots
+hipError_t launch_lm_ctx_append(const float* qkv, const LmCtxSeqs& seqs, float* kcache, float* vcache, long slot_stride, hipStream_t s);
+// The R = sum of len over the sequences with kLmCtxScore scored rows, flat in sequence order: token t > 0 is predicted from x's row t - 1,
+// token 0 from last[slot] (ignore_index and a zero row when the slot is empty)
+hipError_t launch_lm_ctx_gather(const float* x, const int32_t* tokens, const LmCtxSeqs& seqs, const float* last, int R, int ignore_index, float* hsel,
+                                int32_t* targets, hipStream_t s);
+// last[slot[n], :] = x's last row of every sequence with kLmCtxCommit
+hipError_t launch_lm_ctx_last(const float* x, const LmCtxSeqs& seqs, float* last, hipStream_t s);
+
 // the C ABI's error string (loco_last_error) for translation units other than loco_api.hip
 int api_fail(int code, const char* fmt, ...);
 

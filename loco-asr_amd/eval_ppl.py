@@ -5,6 +5,11 @@ The flags of the reference's ``lms/src/eval_ppl_with_pretrained_lm.py`` (``--in_
 minimum and maximum perplexity.  Nothing is downloaded: ``--pretrained DIR`` names a checkpoint directory on disk, ``--random-init``
 builds the synthetic weight family of ``synth.gpt2_state_dict``.  ``--tokenized`` reads ``utt_id id id ...`` lines; without it the
 checkpoint directory must hold GPT-2's tokenizer files.
+
+``--context_type carry`` is this project's third mode and not the reference's: a K/V cache is carried from utterance to utterance of a
+recording and rebuilt from the last ``--keep`` tokens when it is full -- HuggingFace's strided perplexity with utterance-aligned strides.
+Every token but a recording's first is scored once, behind ``--keep`` .. ``n_positions - 1`` tokens of context, where ``max_len`` gives
+every token the full window at the price of one forward per token.
 """
 from __future__ import annotations
 
@@ -29,8 +34,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--out_dir", "-o", required=True, help="where rec_id2nlls.pkl, rec_id2ppl.json and the log are written")
     p.add_argument("--bsize", "--batch_size", "-bsize", "-batch_size", "--sb", "-sb", type=int, default=128, help="max batch size")
     p.add_argument("--model", "-model", "-m", default="gpt2", choices=["gpt2"], help="only GPT-2 base (768 wide) is implemented")
-    p.add_argument("--context_type", "-context_type", "--ct", "-ct", choices=["indep", "max_len"], default="indep",
-                   help="indep: every utterance alone; max_len: the recording's left context up to n_positions tokens")
+    p.add_argument("--context_type", "-context_type", "--ct", "-ct", choices=["indep", "max_len", "carry"], default="indep",
+                   help="indep: every utterance alone; max_len: the recording's left context up to n_positions tokens (the reference's stride-1 "
+                        "windows); carry: a K/V cache carried from utterance to utterance, HuggingFace's strided perplexity with utterance-aligned "
+                        "strides -- NOT the reference's max_len: a token sees between --keep and n_positions - 1 tokens of context")
+    p.add_argument("--keep", type=int, default=None, help="carry: tokens of context kept when the cache is rebuilt (default n_positions // 2)")
+    p.add_argument("--inflight", type=int, default=8, help="carry: recordings walked in lock-step, one cache slot each (1 .. 64)")
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("--pretrained", metavar="DIR", help="HuggingFace GPT-2 checkpoint directory on disk (config.json + model.safetensors / pytorch_model.bin)")
     src.add_argument("--random-init", action="store_true", help="synthetic weights (synth.gpt2_state_dict) with --layers / --positions / --vocab")
@@ -89,6 +98,8 @@ def main(argv=None) -> int:
     t0 = time.time()
     if args.context_type == "indep":
         rec_id2nlls, rec_id2ppl = lm.score_indep(model, utts, tokenizer, args.bsize)
+    elif args.context_type == "carry":
+        rec_id2nlls, rec_id2ppl = lm.score_carry(model, utts, tokenizer, keep=args.keep, inflight=args.inflight)
     else:
         rec_id2nlls, rec_id2ppl = lm.score_max_len(model, utts, tokenizer, args.bsize, strict_reference=args.strict_reference)
     with open(os.path.join(args.out_dir, "rec_id2nlls.pkl"), "wb") as fh:

@@ -16,6 +16,10 @@ The reference's edge behaviour in ``max_len`` mode is kept as it stands (``stric
 * a recording of exactly ``n_positions`` tokens therefore yields no window at all, and no perplexity.
 
 ``strict_reference=False`` adds the one missing window (offset ``n - n_positions``), which scores both.
+
+A K/V cache (``model.new_cache``, ``append``, ``token_nll_given``, ``rescore``) scores continuations behind a context that is encoded
+once, and ``score_carry`` walks a recording with such a cache: a third context mode that is NOT the reference's ``max_len`` but
+HuggingFace's strided perplexity with utterance-aligned strides (``carry_plan``).
 """
 from __future__ import annotations
 
@@ -295,6 +299,130 @@ class GPT2LMHeadModelMI355X:
                 out[j] = piece
         return out
 
+    # ---- cached context (csrc/lm_attention.hip) ----
+    def new_cache(self, slots: int = 1, device=None) -> "LmCache":
+        """``slots`` independent contexts (1 .. 64), each up to ``n_positions`` tokens of K/V in fp32 on the device."""
+        import torch
+        device = torch.device(device) if device is not None else (self.device or torch.device("cuda"))
+        if device.type != "cuda":
+            raise RuntimeError("GPT2LMHeadModelMI355X has no CPU path: a cache lives on a ROCm device only")
+        if self.device is None:
+            self.device = device
+        self._upload()
+        return LmCache(self, slots)
+
+    def _ctx_step(self, cache: "LmCache", tokens, seqs: Sequence[Tuple[int, int, int, int]]):
+        """One ``loco_lm_ctx_step``: ``seqs`` = (start, len, slot, flags) per sequence.  Returns the flat f32 NLLs of the scoring sequences
+        (or None).  Host-side refusals (a full slot, two commits on one slot, ...) raise ValueError with the library's message."""
+        import torch
+        if cache.model is not self:
+            raise ValueError("the cache belongs to another model")
+        arr = np.ascontiguousarray(np.asarray(seqs, np.int32).reshape(-1, 4))
+        if tokens.dtype != torch.int32 or tokens.dim() != 1 or not tokens.is_contiguous():
+            raise ValueError("tokens must be a contiguous 1-D int32 tensor")
+        if len(arr) and (arr[:, 0].min() < 0 or (arr[:, 0].astype(np.int64) + arr[:, 1].clip(min=0)).max() > tokens.numel()):
+            raise ValueError(f"every sequence must lie inside the {tokens.numel()}-token buffer")
+        N, rows = len(arr), int(arr[:, 1].clip(min=0).sum())
+        R = int(arr[arr[:, 3] & 1 == 1, 1].clip(min=0).sum())
+        with torch.cuda.device(self.device):
+            need = self._lib.loco_lm_ctx_workspace_bytes(self._h, max(rows, N), N)
+            if need and (self._ws is None or self._ws.numel() < need or self._ws.device != self.device):
+                self._ws = None
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._ws if self._ws is not None else torch.empty(256, dtype=torch.uint8, device=self.device)
+            out = torch.empty(max(R, 1), dtype=torch.float32, device=self.device)
+            p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+            rc = self._lib.loco_lm_ctx_step(self._h, cache._h, p(tokens), arr.ctypes.data_as(C.POINTER(C.c_int32)), N, p(out), p(ws), ws.numel(),
+                                            self._stream())
+            if rc < 0:
+                raise ValueError(self._lib.loco_last_error().decode(errors="replace"))
+            self._check_status(ws, tokens)
+        return out[:R] if R else None
+
+    def _ids(self, ids, what):
+        import torch
+        self._need_cuda(ids, what)
+        if ids.dim() != 1 or ids.numel() < 1:
+            raise ValueError(f"{what} must be a 1-D tensor of at least one GPT-2 id")
+        return ids.to(torch.int32).contiguous()
+
+    def append(self, cache: "LmCache", slot: int, ids, score: bool = False):
+        """Append ``ids`` (1-D, on the device) to ``slot``.  ``score=True`` also returns f32 ``[len]``: entry t = -log P(ids[t] | the slot's
+        tokens, ids[:t]) -- what ``token_nll_given`` returns for the same ids, bit for bit; entry 0 is 0 on an empty slot."""
+        return self._ctx_step(cache, self._ids(ids, "ids"), [(0, ids.numel(), slot, CTX_COMMIT | (CTX_SCORE if score else 0))])
+
+    def token_nll_given(self, cache: "LmCache", hyps: Sequence, slots=0) -> list:
+        """One f32 ``[len_n]`` tensor per hypothesis: entry t = -log P(hyp[t] | the slot's tokens, hyp[:t]).  ``slots``: one slot for all
+        hypotheses (an n-best list of one context) or one per hypothesis.  The cache is unchanged, and a hypothesis's values do not depend
+        on the hypotheses scored beside it, bit for bit."""
+        import torch
+        if not len(hyps):
+            return []
+        slots = [int(slots)] * len(hyps) if np.ndim(slots) == 0 else [int(v) for v in slots]
+        if len(slots) != len(hyps):
+            raise ValueError(f"{len(slots)} slots for {len(hyps)} hypotheses")
+        ids = [self._ids(t, "every hypothesis") for t in hyps]
+        lens = [t.numel() for t in ids]
+        offs = np.concatenate([[0], np.cumsum(lens)])
+        tokens = torch.cat(ids)
+        out = []
+        for a in range(0, len(ids), CTX_MAX_SEQS):
+            b = min(a + CTX_MAX_SEQS, len(ids))
+            nll = self._ctx_step(cache, tokens, [(int(offs[n]), lens[n], slots[n], CTX_SCORE) for n in range(a, b)])
+            out += list(torch.split(nll, lens[a:b]))
+        return out
+
+
+CTX_SCORE, CTX_COMMIT, CTX_MAX_SEQS = 1, 2, 64
+
+
+class LmCache:
+    """K/V cache of ``GPT2LMHeadModelMI355X``: ``slots`` contexts that ``append`` extends and ``token_nll_given`` reads.  A slot's length is
+    host-side state that changes when a call is enqueued; use a cache from one thread and one stream at a time."""
+
+    def __init__(self, model: GPT2LMHeadModelMI355X, slots: int):
+        import torch
+        self.model, self.slots, self._h = model, slots, None
+        with torch.cuda.device(model.device):
+            self._h = model._lib.loco_lm_cache_create(model._h, slots)
+        if not self._h:
+            raise ValueError(model._lib.loco_last_error().decode(errors="replace"))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self.model._lib.loco_lm_cache_destroy(h)
+
+    def reset(self, slot: int):
+        if self.model._lib.loco_lm_cache_reset(self._h, slot) < 0:
+            raise ValueError(self.model._lib.loco_last_error().decode(errors="replace"))
+
+    def length(self, slot: int) -> int:
+        n = self.model._lib.loco_lm_cache_length(self._h, slot)
+        if n < 0:
+            raise ValueError(f"slot = {slot} is outside 0 .. {self.slots - 1}")
+        return n
+
+
+def rescore(model: GPT2LMHeadModelMI355X, context_ids, hyps: Sequence):
+    """N hypotheses of one utterance against a shared context: the context is encoded ONCE into a private slot, then every hypothesis is
+    scored behind it.  Returns (list of f32 ``[len_n]`` NLLs, f64 ``[N]`` totals, each summed on the device in an order that depends on
+    its length only).  ``context_ids`` may be empty (1-D, numel 0): every hypothesis's first token then scores 0."""
+    import torch
+    model._need_cuda(context_ids, "context_ids")
+    longest = max((t.numel() for t in hyps), default=0)
+    if context_ids.numel() + longest > model.n_positions:
+        raise ValueError(f"context ({context_ids.numel()} tokens) + the longest hypothesis ({longest}) exceed n_positions = {model.n_positions}")
+    cache = getattr(model, "_rescore_cache", None)
+    if cache is None:
+        cache = model._rescore_cache = model.new_cache(1)
+    cache.reset(0)
+    if context_ids.numel():
+        model.append(cache, 0, context_ids)
+    nlls = model.token_nll_given(cache, hyps, slots=0)
+    totals = torch.stack([t.double().sum() for t in nlls]) if nlls else torch.zeros(0, dtype=torch.float64, device=model.device)
+    return nlls, totals
+
 
 # ---- corpus walkers: the reference's two context modes ------------------------------------------------------------------------------
 class TokenizedLines:
@@ -345,9 +473,10 @@ def indep_plan(utts: "Dict[str, str]", tokenizer, bsize: int = 128) -> Tuple[Lis
     return keys, ids, batches
 
 
-def recordings(utts: "Dict[str, str]", tokenizer) -> "OrderedDict[str, List[int]]":
+def recordings(utts: "Dict[str, str]", tokenizer, utt_lens: Optional[dict] = None) -> "OrderedDict[str, List[int]]":
     """``max_len`` mode's sequences: per recording its utterances in (rec, start, end) order -- utt_id is ``rec-x-start-end`` and the key
-    is the STRING ``rec-start-end``, as the reference sorts -- each followed by ``<eos>``, no ``<bos>``."""
+    is the STRING ``rec-start-end``, as the reference sorts -- each followed by ``<eos>``, no ``<bos>``.  ``utt_lens`` (a dict, optional)
+    receives per recording the token count of every utterance, its ``<eos>`` included: ``carry`` mode's chunks."""
 
     def key(utt_id):
         parts = utt_id.split("-")
@@ -358,8 +487,11 @@ def recordings(utts: "Dict[str, str]", tokenizer) -> "OrderedDict[str, List[int]
     recs: "OrderedDict[str, List[int]]" = OrderedDict()
     for utt_id in sorted(utts, key=key):
         seq = recs.setdefault(rec_id_of(utt_id), [])
+        n0 = len(seq)
         seq.extend(tokenizer(utts[utt_id])["input_ids"])
         seq.append(tokenizer.eos_token_id)
+        if utt_lens is not None:
+            utt_lens.setdefault(rec_id_of(utt_id), []).append(len(seq) - n0)
     return recs
 
 
@@ -451,4 +583,74 @@ def score_max_len(model: GPT2LMHeadModelMI355X, utts, tokenizer, bsize: int = 12
             counts.append(len(rows))
     if not out:
         return {}, {}
+    return fold_ppl(torch.cat(out), rec_ids, counts)
+
+
+# ---- a third context mode: carry -----------------------------------------------------------------------------------------------------
+def carry_plan(chunk_lens: Sequence[int], n_positions: int, keep: Optional[int] = None) -> Iterator[Tuple[int, int, int, int, bool]]:
+    """``carry`` mode's walk of one recording whose utterances have ``chunk_lens`` tokens: (base, P, chunk_start, chunk_end, rebased) per
+    chunk, all offsets into the recording's token stream.  A chunk is one utterance; an utterance longer than ``n_positions - keep`` is
+    cut into pieces of that size.  The slot holds stream tokens [base, base + P) when the chunk [chunk_start, chunk_end) is scored behind
+    them and appended.  A chunk that does not fit (P + L > n_positions) first rebases the slot: it is reset and re-prefilled with the
+    last ``keep`` stream tokens before the chunk (base = chunk_start - keep, P = keep).  Pure host arithmetic."""
+    keep = n_positions // 2 if keep is None else keep
+    if not 1 <= keep < n_positions:
+        raise ValueError(f"keep = {keep} must satisfy 1 <= keep < n_positions = {n_positions}")
+    piece = n_positions - keep
+    base = P = pos = 0
+    for n in chunk_lens:
+        if n < 1:
+            raise ValueError(f"a chunk of {n} tokens")
+        for a in range(0, n, piece):
+            L = min(piece, n - a)
+            rebased = P + L > n_positions
+            if rebased:
+                base, P = pos - keep, keep
+            yield base, P, pos, pos + L, rebased
+            P += L
+            pos += L
+
+
+def score_carry(model: GPT2LMHeadModelMI355X, utts, tokenizer, keep: Optional[int] = None, inflight: int = 8):
+    """``carry`` mode over a corpus: (rec_id2nlls, rec_id2ppl).  Every token of a recording but its very first is scored exactly once,
+    behind everything since the recording's start until the slot fills, then behind the last ``keep`` .. ``n_positions - 1`` tokens
+    (``carry_plan``).  This is HuggingFace's strided perplexity with utterance-aligned strides, NOT the reference's ``max_len``, which
+    gives every token the full ``n_positions - 1`` of context at the price of one forward per token.
+
+    Up to ``inflight`` recordings are walked in lock-step, one cache slot each: per round one call re-prefills the slots that rebase
+    (through the same attention kernel, P = 0) and one call scores and appends every recording's chunk.  A recording's NLLs do not depend
+    on ``inflight`` or on the recordings walked beside it, bit for bit."""
+    import torch
+    if not 1 <= inflight <= CTX_MAX_SEQS:
+        raise ValueError(f"inflight = {inflight} is outside 1 .. {CTX_MAX_SEQS}")
+    utt_lens: dict = {}
+    recs = [(r, seq) for r, seq in recordings(utts, tokenizer, utt_lens).items() if len(seq) >= 2]
+    if not recs:
+        return {}, {}
+    plans = [list(carry_plan(utt_lens[r], model.n_positions, keep)) for r, _ in recs]
+    offs = np.concatenate([[0], np.cumsum([len(seq) for _, seq in recs])])
+    dev = model.device or "cuda"
+    tokens = torch.as_tensor(np.concatenate([np.asarray(seq, np.int32) for _, seq in recs]), device=dev)
+    cache = model.new_cache(min(inflight, len(recs)), dev)
+    out, rec_ids, counts = [], [], []
+    for g0 in range(0, len(recs), inflight):
+        group = range(g0, min(g0 + inflight, len(recs)))
+        for i in group:
+            cache.reset(i - g0)
+        for rnd in range(max(len(plans[i]) for i in group)):
+            live = [i for i in group if rnd < len(plans[i])]
+            rebase = [i for i in live if plans[i][rnd][4]]
+            for i in rebase:
+                cache.reset(i - g0)
+            if rebase:  # phase A: the last `keep` tokens before the chunk, committed and not scored
+                model._ctx_step(cache, tokens, [(int(offs[i]) + plans[i][rnd][0], plans[i][rnd][1], i - g0, CTX_COMMIT) for i in rebase])
+            # phase B: every live recording's chunk, scored behind its slot and appended to it
+            nll = model._ctx_step(cache, tokens, [(int(offs[i]) + plans[i][rnd][2], plans[i][rnd][3] - plans[i][rnd][2], i - g0, CTX_SCORE | CTX_COMMIT)
+                                                  for i in live])
+            for i, piece in zip(live, torch.split(nll, [plans[i][rnd][3] - plans[i][rnd][2] for i in live])):
+                piece = piece[1:] if rnd == 0 else piece  # the recording's very first token: nothing predicts it
+                if piece.numel():
+                    out.append(piece)
+                    rec_ids.append(recs[i][0])
+                    counts.append(piece.numel())
     return fold_ppl(torch.cat(out), rec_ids, counts)
