@@ -30,15 +30,17 @@ def n_layers(sd):
     return 1 + max(int(m.group(1)) for m in (re.search(r"(?:^|\.)h\.(\d+)\.ln_1\.weight$", k) for k in sd) if m)
 
 
-def hidden_states(sd, ids):
+def hidden_states(sd, ids, mask=None):
     """ids: 1-D int sequence (one sequence; causal attention makes right padding irrelevant to the valid positions).  Returns the
-    n_layer + 1 hidden states HF reports ([S, 768] each: embedding output, blocks 0 .. n - 2, ln_f of the last block)."""
+    n_layer + 1 hidden states HF reports ([S, 768] each: embedding output, blocks 0 .. n - 2, ln_f of the last block).
+    mask (optional, bool [S, S], every layer and head): entry (t, j) says whether query t sees key j, in place of the causal rule j <= t
+    -- for tests that plant an attention fault in this reference to see how far the NLLs move."""
     ids = np.asarray(ids, np.int64)
     S = len(ids)
     x = _get(sd, "wte.weight")[ids] + _get(sd, "wpe.weight")[:S]
     out = [x]
     L = n_layers(sd)
-    mask = np.tril(np.ones((S, S), bool))
+    mask = np.tril(np.ones((S, S), bool)) if mask is None else np.asarray(mask, bool).reshape(S, S)
     for l in range(L):
         p = f"h.{l}."
         h = layernorm(x, _get(sd, p + "ln_1.weight"), _get(sd, p + "ln_1.bias"))
@@ -73,9 +75,9 @@ def head_nll(h, wte, targets, ignore_index=-100):
     return out
 
 
-def token_nll(sd, ids):
-    """[S - 1] float64: entry s = -log P(ids[s + 1] | ids[:s + 1])."""
-    h = hidden_states(sd, ids)[-1]
+def token_nll(sd, ids, mask=None):
+    """[S - 1] float64: entry s = -log P(ids[s + 1] | ids[:s + 1]).  mask: see hidden_states."""
+    h = hidden_states(sd, ids, mask)[-1]
     return head_nll(h[:-1], _get(sd, "wte.weight"), np.asarray(ids)[1:])
 
 

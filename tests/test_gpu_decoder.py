@@ -258,6 +258,11 @@ def _attn_ref(q, k, v, counts, causal, offset, scale):
     dict(B=3, Sq=37, Tk=70, counts=[70, 65, 63], causal=1, offset=33),
     dict(B=3, Sq=24, Tk=149, counts=[149, 97, 1], causal=0, offset=0),
     dict(B=1, Sq=3, Tk=1499, counts=[1499], causal=0, offset=0),
+    # the language model's shapes (csrc/lm_api.hip: causal self-attention, Sq = Tk = S, counts = the rows' lengths)
+    dict(B=1, Sq=300, Tk=300, counts=[300], causal=1, offset=0),       # two key splits
+    dict(B=1, Sq=341, Tk=341, counts=[200], causal=1, offset=0),       # the longest S with two splits; queries past the count see its keys
+    dict(B=1, Sq=1024, Tk=1024, counts=[1024], causal=1, offset=0),    # n_positions: 16 key tiles, one split
+    dict(B=3, Sq=1024, Tk=1024, counts=[1024, 700, 1], causal=1, offset=0),
 ])
 def test_op_decoder_attention(gu, case):
     B, Sq, Tk = case["B"], case["Sq"], case["Tk"]
@@ -278,7 +283,7 @@ def test_op_decoder_attention(gu, case):
     torch.cuda.synchronize()
     first = out.clone()
     r = gu.rel_l2(out, ref)
-    record_figure("op_decoder_attention", **{k_: v_ for k_, v_ in case.items() if k_ != "counts"}, split_bytes=nb, rel_l2=r)
+    record_figure("op_decoder_attention", **{k_: v_ for k_, v_ in case.items() if k_ != "counts"}, split_bytes=nb, rel_l2=r, bar=BAR_ATTN)
     assert r <= BAR_ATTN, r
     gu.check(lib.loco_op_decoder_attention(*args), "decoder_attention")
     torch.cuda.synchronize()

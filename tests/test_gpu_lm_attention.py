@@ -7,6 +7,9 @@ tile, past a whole tile (65); sequences of 1, 2, 32, 33 and 70 queries (one lane
 scores are planted (``value_domain_cases._planted``) so that the running maximum moves where the kernel is most likely to mishandle it:
 at the last prefix key, at the first own key, at own key 31 / 32, and at every key (ascending).
 
+The second half of the file repeats this with 1024 rows per slot: sequences of 129 .. 257 queries (a second and a third query tile of the
+128 a workgroup owns) and prefixes of up to 1023 keys, the lead at own key 127 / 128 / 192, at prefix key 63 / 64 and at the last prefix key.
+
 Bars are the project's own: per row 4 x torch's fp32 error against float64 (``row_bar``), and 1e-5 relative L2 (``BAR_ATTN``)."""
 import ctypes as C
 
@@ -109,6 +112,19 @@ def test_prefix_plus_causal_against_float64(P_index, kind):
     assert fig["rel_l2"] <= BAR_ATTN, fig
 
 
+def alone_among_others_and_moved(qkv, kc, vc, seqs):
+    together = launch(qkv, kc, vc, seqs)
+    r0 = 0
+    for L, slot, P in seqs:
+        alone = launch(qkv[r0:r0 + L], kc, vc, [(L, slot, P)])
+        assert torch.equal(alone.view(torch.int32), together[r0:r0 + L].view(torch.int32)), (L, slot, P)
+        # the slot's contents moved to slot index 2 of a wider cache, the sequence last of a call instead of first
+        kc3, vc3 = torch.cat([kc, kc[slot:slot + 1]]), torch.cat([vc, vc[slot:slot + 1]])
+        moved = launch(torch.cat([qkv[:5], qkv[r0:r0 + L]]), kc3, vc3, [(5, 1, 0), (L, 2, P)], slots=3)
+        assert torch.equal(moved[5:].view(torch.int32), together[r0:r0 + L].view(torch.int32)), (L, slot, P)
+        r0 += L
+
+
 @pytest.mark.parametrize("P_index", [0, 3, 5])
 def test_a_sequence_alone_is_itself_among_others_and_on_another_slot(P_index):
     qkv, kc, vc, seqs = build(P_index, "ascending")
@@ -122,3 +138,71 @@ def test_a_sequence_alone_is_itself_among_others_and_on_another_slot(P_index):
         moved = launch(torch.cat([qkv[:5], qkv[r0:r0 + L]]), kc3, vc3, [(5, 1, 0), (L, 2, P)], slots=3)
         assert torch.equal(moved[5:].view(torch.int32), together[r0:r0 + L].view(torch.int32)), (L, slot, P)
         r0 += L
+
+
+# ---- GPT-2's own lengths: 1024 rows per slot, more than one query tile ----------------------------------------------------------------------
+# A workgroup owns 128 queries of one sequence.  Case A puts a second and a third query tile (q0 = 128, 256; own key tiles past the
+# second; the skip of own tiles past a wave's last query; own_end = min(len, q0 + 128)) behind a prefix of exactly one key tile and of a
+# single key; case B puts a second query tile of two queries, a half tile and a lone query behind 14 .. 16 prefix tiles, up to P = 1023
+# and P + L = 1024, with two sequences of different P on one slot.
+LONG_CAP = 1024
+LONG_CASES = {"A": [(129, 0, 64), (257, 1, 1), (200, 0, 64)], "B": [(130, 0, 893), (64, 1, 960), (1, 0, 1023)]}
+LONG_KINDS = ["own127", "own128", "own192", "prefix63", "prefix64", "last_prefix", "ascending"]
+
+
+def build_long(case, kind):
+    """The layout of ``build`` with LONG_CAP rows per slot.  The lead -- the key that outscores all others by about LEAD nats, where the
+    running maximum arrives -- stands at own key 127 (the last of the first query tile), 128 (the first of the second), 192 (the first of
+    the fourth own key tile), each clipped to the sequence's last key; at prefix key 63 or 64 of both slots (the last of the first key
+    tile, the first of the second), clipped to the slot's last visible key; or at every sequence's last prefix key.  ascending: every key
+    of the prefix, then every own key, raises the maximum."""
+    seqs = LONG_CASES[case]
+    g = torch.Generator().manual_seed(5000 + 100 * sorted(LONG_CASES).index(case) + LONG_KINDS.index(kind))
+    rows = sum(s[0] for s in seqs)
+    q, k, u = vd._planted(g, rows, 2 * LONG_CAP + rows)   # keys: slot 0's rows, slot 1's rows, then every sequence's own
+    q, k = q[0], k[0]
+    v = torch.randn((2 * LONG_CAP + rows, 768), generator=g, dtype=torch.float64)
+    base = float((vd.SCALE * torch.einsum("ihd,jhd->hij", q, k)).abs().max())
+    lead = (vd.LEAD + 2 * base) * u
+    if kind == "ascending":
+        step = vd.ASCENT / 64.0
+        k = (0.2 * step / base) * k
+        k[:2 * LONG_CAP] += step * torch.arange(LONG_CAP, dtype=torch.float64).repeat(2)[:, None, None] * u
+    elif kind.startswith("prefix"):
+        for slot in (0, 1):
+            k[slot * LONG_CAP + min(int(kind[6:]), min(P for _, s, P in seqs if s == slot) - 1)] += lead
+    elif kind == "last_prefix":
+        for slot, P in sorted({(s, P) for _, s, P in seqs}):
+            k[slot * LONG_CAP + P - 1] += lead
+    own0 = 2 * LONG_CAP
+    for L, slot, P in seqs:
+        if kind.startswith("own"):
+            k[own0 + min(int(kind[3:]), L - 1)] += lead
+        elif kind == "ascending":
+            k[own0:own0 + L] += step * (P + torch.arange(L, dtype=torch.float64))[:, None, None] * u
+        own0 += L
+    qkv = torch.cat([q.reshape(rows, 768), k[2 * LONG_CAP:].reshape(rows, 768), v[2 * LONG_CAP:]], 1).float()
+    kc, vc = k[:2 * LONG_CAP].reshape(2, LONG_CAP, 768).float(), v[:2 * LONG_CAP].reshape(2, LONG_CAP, 768).float()
+    return qkv, kc, vc, seqs
+
+
+@pytest.mark.parametrize("kind", LONG_KINDS)
+@pytest.mark.parametrize("case", sorted(LONG_CASES))
+def test_later_query_tiles_and_long_prefixes_against_float64(case, kind):
+    qkv, kc, vc, seqs = build_long(case, kind)
+    assert all(P + L <= LONG_CAP for L, _, P in seqs)
+    ref = reference(qkv, kc, vc, seqs, torch.float64)
+    own = reference(qkv, kc, vc, seqs, torch.float32)
+    out = launch(qkv, kc, vc, seqs)                       # two launches, the same bits
+    assert bool(torch.isfinite(out).all())
+    bar = vd.row_bar(ref, own)
+    fig = dict(rel_l2=rel_l2(out, ref), over_row_bar=vd.worst_ratio(out, ref, bar), max_abs=float((out.double() - ref).abs().max()),
+               torch_fp32_max_abs=float((own.double() - ref).abs().max()))
+    record_figure("lm_ctx_attention_long", case=case, kind=kind, seqs=seqs, bar_rel_l2=BAR_ATTN, **fig)
+    print("lm ctx attention long", case, kind, seqs, fig)
+    assert fig["over_row_bar"] <= 1.0, fig
+    assert fig["rel_l2"] <= BAR_ATTN, fig
+
+
+def test_a_long_sequence_alone_is_itself_among_others_and_on_another_slot():
+    alone_among_others_and_moved(*build_long("A", "ascending"))
