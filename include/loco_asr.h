@@ -388,7 +388,8 @@ int loco_op_attention_probs(const float* qkv, const float* qp, const int32_t* fr
  * x = hi + lo with hi = fp16(x), lo = fp16(x - hi); A W^T ~= Ahi Whi^T + Alo Whi^T + Ahi Wlo^T (gemm_f16x3.hip). */
 int loco_op_split_f16(const float* x, void* hi, void* lo, int64_t n, void* stream); /* n % 4 == 0 */
 /* as loco_op_gemm with fp16 hi/lo planes for A and W (lda/ldw % 8 == 0); output fp32 C, or split planes Chi/Clo
- * when Chi != NULL (the form the next GEMM consumes). */
+ * when Chi != NULL (the form the next GEMM consumes).  Plane outputs are written as 16-byte pieces: with Chi set, ldc, sC1 and
+ * sC2 must be multiples of 8 halves (fp32 output: of 4 floats); anything else is LOCO_E_INVALID. */
 int loco_op_gemm_f16x3(const void* Ahi, const void* Alo, int64_t lda, const void* Whi, const void* Wlo, int64_t ldw,
                        const float* bias, const float* R, int64_t ldr, float* C, void* Chi, void* Clo, int64_t ldc,
                        int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t nb1, int32_t nb2, int64_t sA1, int64_t sA2,
@@ -416,6 +417,46 @@ int loco_op_gemm_f16x3_splitk(const void* Ahi, const void* Alo, int64_t lda, con
                               const float* bias, const float* R, int64_t ldr, float* C, void* Chi, void* Clo, int64_t ldc,
                               int32_t M, int32_t N, int32_t K, int32_t epilogue, void* splitk_ws, size_t splitk_bytes,
                               void* stream);
+
+/* Every argument of the split-precision GEMM as loco_forward launches it (parity tests): those of loco_op_gemm_f16x3 plus
+ *   Rhi / Rlo    epilogue 2: the residual as fp16 hi/lo planes (element offsets and ldr of R, ldr % 8 == 0) instead of R;
+ *   out_scale    the accumulator is multiplied by it before bias / epilogue (weight planes holding W * 2^k: out_scale = 2^-k);
+ *   terms        3, or 2 = the A_hi W_lo term dropped (precision mode "f16x2");
+ *   range_slot   device, 8 floats, or NULL: max|x| of what is written into planes is folded into max(range_slot[0..7]);
+ *   qkv_stride   epilogue 3 (q|k|v scatter; N = 2304, one batch entry, plane output): columns [768 j, 768 j + 768) go to rows of 768
+ *                halves at Chi / Clo + j * qkv_stride; qkv_stride >= M * 768 and % 8 == 0;
+ *   splitk_ws    NULL, or the workspace of loco_op_gemm_f16x3_splitk (splitk_bytes >= loco_gemm_splitk_bytes());
+ *   co_scheduled nonzero: the tile choice stops rounding up to whole rounds of workgroups (the two half-batch schedule).
+ * struct_size must be sizeof(LocoGemmF16Desc). */
+typedef struct LocoGemmF16Desc {
+    uint32_t struct_size;
+    int32_t M, N, K, epilogue, nb1, nb2, terms, co_scheduled;
+    const void *Ahi, *Alo, *Whi, *Wlo;
+    const float *bias, *R;
+    const void *Rhi, *Rlo;
+    float* C;
+    void *Chi, *Clo;
+    float* range_slot;
+    void* splitk_ws;
+    size_t splitk_bytes;
+    int64_t lda, ldw, ldc, ldr, sA1, sA2, sC1, sC2, qkv_stride;
+    float out_scale;
+} LocoGemmF16Desc;
+int loco_op_gemm_f16x3_desc(const LocoGemmF16Desc* desc, void* stream);
+
+/* The grouped positional conv of the f16x3 forward (gemm_f16x3.hip), as loco_forward runs it: h [B,T,768] is re-laid into group-major
+ * fp16 planes with a 64-frame zero halo (ghi / glo: B * 16 * (T + 128) * 48 halves each; rows t >= rows_clip[b] read as zeros when
+ * rows_clip is given), then out = h + GELU(out_scale * conv + bias) + sin_table[pos] as loco_op_pos_conv.  whi / wlo: planes of the
+ * folded weight in GEMM order [16][48][128 * 48] ([g][o][tap * 48 + i]) times 1 / out_scale (a power of two); terms 3 or 2;
+ * splitk_ws NULL or >= loco_gemm_splitk_bytes() (taken for B * 16 * ceil(T / 512) <= 64). */
+int loco_op_pos_conv_f16x3(const float* h, const void* whi, const void* wlo, const float* bias, const float* sin_table,
+                           const int32_t* frames, const int32_t* rows_clip, float out_scale, int32_t terms, void* ghi, void* glo,
+                           void* splitk_ws, size_t splitk_bytes, float* out, int32_t B, int32_t T, void* stream);
+
+/* loco_op_layernorm as the f16x3 forward runs it: y (optional fp32 copy), yhi = fp16(y) and ylo = fp16(y - yhi) as planes
+ * [rows, dim], and nonfinite_slot (device, 8 floats, or NULL) set to +inf when a row's statistics are not finite. */
+int loco_op_layernorm_f16x3(const float* x, const float* gamma, const float* beta, float* y, void* yhi, void* ylo,
+                            float* nonfinite_slot, int64_t rows, int32_t dim, float eps, void* stream);
 
 /* split-precision attention core: q, k and v as fp16 hi/lo planes [B*T,768] (q pre-scaled by 1/8) -- the layout the fused q|k|v
  * projection writes; the kernel transposes its V tiles with the LDS read; qp/frames/ctx as loco_op_attention. */

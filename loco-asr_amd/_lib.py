@@ -41,6 +41,16 @@ class LocoVadParams(C.Structure):
                 ("peak_quantile", C.c_double), ("margin_db", C.c_double), ("abs_floor_db", C.c_double), ("min_dynamic_db", C.c_double)]
 
 
+class LocoGemmF16Desc(C.Structure):
+    """LocoGemmF16Desc of include/loco_asr.h (loco_op_gemm_f16x3_desc): ``struct_size`` must be ``ctypes.sizeof(LocoGemmF16Desc)``."""
+    _fields_ = ([("struct_size", C.c_uint32)] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "epilogue", "nb1", "nb2", "terms", "co_scheduled")] +
+                [(n, C.c_void_p) for n in ("Ahi", "Alo", "Whi", "Wlo", "bias", "R", "Rhi", "Rlo", "C", "Chi", "Clo", "range_slot", "splitk_ws")] +
+                [("splitk_bytes", C.c_size_t)] +
+                [(n, C.c_int64) for n in ("lda", "ldw", "ldc", "ldr", "sA1", "sA2", "sC1", "sC2", "qkv_stride")] +
+                [("out_scale", C.c_float)])
+
+
 _vp, _i32, _i64, _sz, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 _u32p = C.POINTER(C.c_uint32)
 
@@ -107,6 +117,9 @@ SIGNATURES = {
                                             _vp, _sz, _vp]),
     "loco_op_gemm_f16x3": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i64, _i64, _i64, _i64, _vp]),
+    "loco_op_gemm_f16x3_desc": (C.c_int, [C.POINTER(LocoGemmF16Desc), _vp]),
+    "loco_op_pos_conv_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i32, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
+    "loco_op_layernorm_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _vp]),
     "loco_op_permute_conv_k": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "loco_op_conv_gemm_f16x3": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp]),
     "loco_op_attention_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),

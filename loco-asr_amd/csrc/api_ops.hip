@@ -105,6 +105,8 @@ int loco_op_gemm_f16x3(const void* Ahi, const void* Alo, int64_t lda, const void
                        int64_t sC2, void* stream) {
     if (!Ahi || !Alo || !Whi || !Wlo || (!C && !Chi)) return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3: null argument");
     if (K % 32 || (lda | ldw) & 7) return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3: K %% 32 and lda/ldw %% 8 must be 0");
+    if (Chi && ((ldc | sC1 | sC2) & 7))
+        return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3: plane output needs ldc, sC1 and sC2 %% 8 == 0 (16-byte stores)");
     GemmSplitArgs a{(const _Float16*)Ahi, (const _Float16*)Alo, (const _Float16*)Whi, (const _Float16*)Wlo, bias, R, C,
                     (_Float16*)Chi, (_Float16*)Clo, M, N, K, lda, ldw, ldc, ldr, nb1, nb2, sA1, sA2, sC1, sC2, epilogue};
     HIP_TRY(launch_gemm_split(a, (hipStream_t)stream));
@@ -142,10 +144,75 @@ int loco_op_gemm_f16x3_splitk(const void* Ahi, const void* Alo, int64_t lda, con
     if (!Ahi || !Alo || !Whi || !Wlo || (!C && !Chi) || !splitk_ws) return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3_splitk: null argument");
     if (K % 32 || (lda | ldw) & 7) return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3_splitk: K %% 32 and lda/ldw %% 8 must be 0");
     if (splitk_bytes < kSplitKBytes) return fail(LOCO_E_WORKSPACE, "loco_op_gemm_f16x3_splitk: workspace %zu < %zu bytes", splitk_bytes, kSplitKBytes);
+    if (Chi && (ldc & 7)) return fail(LOCO_E_INVALID, "loco_op_gemm_f16x3_splitk: plane output needs ldc %% 8 == 0 (16-byte stores)");
     GemmSplitArgs a{(const _Float16*)Ahi, (const _Float16*)Alo, (const _Float16*)Whi, (const _Float16*)Wlo, bias, R, C,
                     (_Float16*)Chi, (_Float16*)Clo, M, N, K, lda, ldw, ldc, ldr, 1, 1, 0, 0, 0, 0, epilogue};
     a.splitk_ws = reinterpret_cast<float*>(splitk_ws);
     HIP_TRY(launch_gemm_split(a, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_gemm_f16x3_desc(const LocoGemmF16Desc* d, void* stream) {
+    const char* fn = "loco_op_gemm_f16x3_desc";
+    if (!d) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (d->struct_size != sizeof(LocoGemmF16Desc))
+        return fail(LOCO_E_INVALID, "%s: struct_size = %u is not sizeof(LocoGemmF16Desc) = %zu", fn, d->struct_size, sizeof(LocoGemmF16Desc));
+    if (!d->Ahi || !d->Alo || !d->Whi || !d->Wlo || (!d->C && !d->Chi)) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (d->K % 32 || (d->lda | d->ldw) & 7) return fail(LOCO_E_INVALID, "%s: K %% 32 and lda/ldw %% 8 must be 0", fn);
+    if (d->epilogue < 0 || d->epilogue > 3) return fail(LOCO_E_INVALID, "%s: epilogue %d not in 0..3", fn, d->epilogue);
+    if (d->terms != 2 && d->terms != 3) return fail(LOCO_E_INVALID, "%s: terms must be 2 or 3", fn);
+    if ((d->Rhi == nullptr) != (d->Rlo == nullptr)) return fail(LOCO_E_INVALID, "%s: Rhi and Rlo go together", fn);
+    if (d->Chi && ((d->ldc | d->sC1 | d->sC2 | d->qkv_stride) & 7))
+        return fail(LOCO_E_INVALID, "%s: plane output needs ldc, sC1, sC2 and qkv_stride %% 8 == 0 (16-byte stores)", fn);
+    if (d->splitk_ws && d->splitk_bytes < kSplitKBytes)
+        return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, d->splitk_bytes, kSplitKBytes);
+    GemmSplitArgs a{(const _Float16*)d->Ahi, (const _Float16*)d->Alo, (const _Float16*)d->Whi, (const _Float16*)d->Wlo, d->bias, d->R, d->C,
+                    (_Float16*)d->Chi, (_Float16*)d->Clo, d->M, d->N, d->K, d->lda, d->ldw, d->ldc, d->ldr, d->nb1, d->nb2, d->sA1, d->sA2,
+                    d->sC1, d->sC2, d->epilogue};
+    a.Rhi = (const _Float16*)d->Rhi;
+    a.Rlo = (const _Float16*)d->Rlo;
+    a.out_scale = d->out_scale;
+    a.terms = d->terms;
+    a.range_slot = d->range_slot;
+    a.qkv_stride = d->qkv_stride;
+    a.splitk_ws = reinterpret_cast<float*>(d->splitk_ws);
+    a.co_scheduled = d->co_scheduled != 0;
+    HIP_TRY(launch_gemm_split(a, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_pos_conv_f16x3(const float* h, const void* whi, const void* wlo, const float* bias, const float* sin_table, const int32_t* frames,
+                           const int32_t* rows_clip, float out_scale, int32_t terms, void* ghi, void* glo, void* splitk_ws, size_t splitk_bytes,
+                           float* out, int32_t B, int32_t T, void* stream) {
+    const char* fn = "loco_op_pos_conv_f16x3";
+    if (!h || !whi || !wlo || !bias || !sin_table || !ghi || !glo || !out) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (B <= 0 || T <= 0) return fail(LOCO_E_INVALID, "%s: B and T must be >= 1", fn);
+    if (terms != 2 && terms != 3) return fail(LOCO_E_INVALID, "%s: terms must be 2 or 3", fn);
+    if (splitk_ws && splitk_bytes < kSplitKBytes) return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, splitk_bytes, kSplitKBytes);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_group_major_split(h, ghi, glo, B, T, s, nullptr, rows_clip));
+    // the launch of prenet_f16x3 (api_forward.hip)
+    GemmSplitArgs a{};
+    a.M = T; a.N = kPosCg; a.K = kPosK * kPosCg; a.epilogue = kEpiPosConv;
+    a.Ahi = (const _Float16*)ghi; a.Alo = (const _Float16*)glo; a.Whi = (const _Float16*)whi; a.Wlo = (const _Float16*)wlo;
+    a.bias = bias; a.R = h; a.C = out;
+    a.lda = kPosCg; a.ldw = kPosK * kPosCg; a.ldc = kHidden; a.ldr = kHidden;
+    a.nb1 = B; a.nb2 = kPosGroups;
+    a.sA1 = (long)kPosGroups * (T + kPosK) * kPosCg; a.sA2 = (long)(T + kPosK) * kPosCg;
+    a.sC1 = (long)T * kHidden; a.sC2 = kPosCg;
+    a.sW2 = (long)kPosCg * kPosK * kPosCg; a.sBias2 = kPosCg;
+    a.sin_table = sin_table; a.frames = frames; a.T = T;
+    a.out_scale = out_scale; a.terms = terms;
+    a.splitk_ws = reinterpret_cast<float*>(splitk_ws);
+    HIP_TRY(launch_gemm_split(a, s));
+    return LOCO_OK;
+}
+
+int loco_op_layernorm_f16x3(const float* x, const float* gamma, const float* beta, float* y, void* yhi, void* ylo, float* nonfinite_slot,
+                            int64_t rows, int32_t dim, float eps, void* stream) {
+    if (!x || !gamma || !beta || !yhi || !ylo) return fail(LOCO_E_INVALID, "loco_op_layernorm_f16x3: null argument");
+    if (dim != 512 && dim != 768) return fail(LOCO_E_INVALID, "loco_op_layernorm_f16x3: dim %d not in {512,768}", dim);
+    HIP_TRY(launch_layernorm(x, gamma, beta, y, rows, dim, eps, (hipStream_t)stream, yhi, ylo, nonfinite_slot));
     return LOCO_OK;
 }
 

@@ -904,6 +904,8 @@ hipError_t launch_gemm_split(const GemmSplitArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % SBK != 0) return hipErrorInvalidValue;
     if ((a.lda | a.ldw | a.sA1 | a.sA2) & 7) return hipErrorInvalidValue;  // 16-byte staging of 8 halves
     if ((a.N | a.ldc | a.sC1 | a.sC2) & 3) return hipErrorInvalidValue;
+    // plane outputs leave as 16-byte pieces of 8 halves (split_gemm_store16): a row or batch entry that starts 8 bytes off would split them
+    if (a.Chi && ((a.ldc | a.sC1 | a.sC2 | a.qkv_stride) & 7)) return hipErrorInvalidValue;
     if (a.epilogue == kEpiResidual && ((!a.R && !(a.Rhi && a.Rlo)) || (a.ldr & (a.Rhi ? 7 : 3)))) return hipErrorInvalidValue;
     const bool split = a.Chi != nullptr;
     if (split ? (a.Clo == nullptr) : (a.C == nullptr)) return hipErrorInvalidValue;

@@ -1,0 +1,197 @@
+"""Per-element checks of single operators: guarded outputs, poisoned inputs, fp64 references and derived error bars.
+
+Used by tests/test_gpu_gemm_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
+roundings times the forward-error scale of the element it applies to.
+
+Guards.  An output lives inside a larger allocation filled with a sentinel bit pattern (a NaN with a payload): before the first
+owned element, after the last (at least one 256 x 256 tile of rows), in the ld - N pad of every row and in the gaps between
+batch entries.  After a launch every element the operator does not own must still hold the sentinel's bits, and no owned element
+may (a NaN with that payload is not something the arithmetic produces).  Inputs are laid out the same way with NaN everywhere the
+kernel has no business reading a VALUE from: pads, gaps, rows past the end.  (The kernels clamp row indices to the last row and
+read only k in [0, K); a NaN that reaches an accumulator shows in the output.)
+
+Error bars, u = 2^-24, S[m,n] = sum_k |a_k| |w_k| + |bias[n]| + |R[m,n]| (with out_scale folded into the sum).
+  f16x3 (gemm_f16x3.hip): an element is accumulated k-tile by k-tile (32 deep), `terms` MFMAs per k-tile, each charged two
+    roundings of at most u * |partial sum| <= u S; plus 8 for out_scale, bias, residual and the dropped lo * lo term (<= u S by
+    construction of the planes: |lo| <= 2^-11 |hi|).  Count = 2 * terms * K / 32 + 8.
+  fp32 (gemm_f32.hip): v_mfma_f32_32x32x2_f32 adds two products to its accumulator (charged one rounding each, the "fmaf chain" of the
+    kernel's header).  The running sum is folded into a total every four k-tiles, so a chain holds at most 4 * 32 = 128 products and
+    its roundings are bounded by u times the partial sums of ITS block; summed over the blocks that is min(K, 128) u S.  The folds add
+    ceil(K / 128) roundings of at most u S, the last add, bias and residual three more.  Count = min(K, 128) + ceil(K / 128) + 3.
+  GELU epilogues: the pre-activation bar times max |gelu'| <= 1.13, plus the activation's own error: 4 u |ref| for the erf form
+    (loco_kernels.h: 2.2e-7 = 3.7 u relative); the tanh form (epilogue 5, x / (1 + 2^y)) adds 2 u |x|: y carries ~5 u relative
+    error, which 2^y turns into 3.5 |y| u relative, and |x| e^-t * 5 t u <= 5 u |x| / e over t = y ln 2 > 0.
+  Plane outputs: hi + lo is compared, and hi + lo keeps 22 bits: + 2^-21 |ref|.
+"""
+import math
+
+import numpy as np
+import torch
+
+from conftest import record_figure
+from gpu_util import check, lib, ptr, stream
+
+U = 2.0 ** -24
+SENTINEL = {torch.float32: 0x7FC0BEEF, torch.float16: 0x7E5A}  # quiet NaNs with a payload
+_INT = {torch.float32: torch.int32, torch.float16: torch.int16}
+TILE_SLACK = 256  # rows (and elements) of sentinel behind every output: one full 256 x 256 tile
+
+
+class Layout:
+    """nb1 x nb2 matrices of rows x cols inside one flat allocation: element (z1, z2, r, c) at head + z1 s1 + z2 s2 + r ld + c,
+    `head` elements of guard before and `tail` after (default: 256 rows and 256 elements)."""
+
+    def __init__(self, rows, cols, ld=None, nb1=1, nb2=1, s1=0, s2=0, head=64, tail=None):
+        self.rows, self.cols, self.ld = rows, cols, ld or cols
+        self.nb1, self.nb2, self.s1, self.s2, self.head = nb1, nb2, s1, s2, head
+        self.tail = TILE_SLACK * self.ld + TILE_SLACK if tail is None else tail
+        self.span = (nb1 - 1) * s1 + (nb2 - 1) * s2 + (rows - 1) * self.ld + cols
+        self.total = self.head + self.span + self.tail
+        self._index = None
+
+    def index(self):
+        """flat positions of the owned elements, int64 [nb1, nb2, rows, cols] on the device"""
+        if self._index is None:
+            ar = lambda n: torch.arange(n, device="cuda", dtype=torch.int64)
+            self._index = (self.head + ar(self.nb1)[:, None, None, None] * self.s1 + ar(self.nb2)[None, :, None, None] * self.s2 +
+                           ar(self.rows)[None, None, :, None] * self.ld + ar(self.cols)[None, None, None, :])
+            assert self._index.unique().numel() == self._index.numel(), "layout overlaps itself"
+        return self._index
+
+
+def sentinel_buffer(layout, dtype):
+    return torch.full((layout.total,), SENTINEL[dtype], dtype=_INT[dtype], device="cuda").view(dtype)
+
+
+def base(buf, layout):
+    """pointer to element (0, 0, 0, 0)"""
+    import ctypes
+    return ctypes.c_void_p(buf.data_ptr() + layout.head * buf.element_size())
+
+
+def poisoned(values, layout):
+    """values [nb1, nb2, rows, cols] (device) placed in a NaN-filled allocation of the layout"""
+    buf = torch.full((layout.total,), float("nan"), dtype=values.dtype, device="cuda")
+    buf[layout.index().reshape(-1)] = values.reshape(-1)
+    return buf
+
+
+def owned(buf, layout):
+    return buf[layout.index().reshape(-1)].view(layout.nb1, layout.nb2, layout.rows, layout.cols)
+
+
+def assert_guards(buf, layout, what=""):
+    """every element outside the layout still holds the sentinel, every element inside was written"""
+    bits = buf.view(_INT[buf.dtype])
+    sent = SENTINEL[buf.dtype]
+    mask = torch.ones(layout.total, dtype=torch.bool, device="cuda")
+    mask[layout.index().reshape(-1)] = False
+    touched = torch.nonzero(mask & (bits != sent)).reshape(-1)
+    assert touched.numel() == 0, f"{what}: {touched.numel()} guard elements overwritten, first at flat offset {int(touched[0]) - layout.head}"
+    unwritten = int((owned(bits, layout) == sent).sum())
+    assert unwritten == 0, f"{what}: {unwritten} owned elements never written"
+
+
+def split_planes(x):
+    """fp32 device tensor -> (hi, lo) fp16 planes by the library's own split kernel"""
+    x = x.contiguous()
+    hi = torch.empty(x.shape, dtype=torch.float16, device="cuda")
+    lo = torch.empty_like(hi)
+    check(lib().loco_op_split_f16(ptr(x), ptr(hi), ptr(lo), x.numel(), stream()))
+    return hi, lo
+
+
+def gelu64(x):
+    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
+
+
+def gelu_new64(x):
+    return 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
+
+
+def f16x3_count(K, terms=3):
+    return 2 * terms * K / 32 + 8
+
+
+def f32_count(K):
+    return min(K, 128) + math.ceil(K / 128) + 3
+
+
+def products(a, w, out_scale=1.0):
+    """a [..., M, K], w [N, K] or [..., N, K], fp64 on the CPU: (a w^T, |a| |w|^T) times out_scale -- computed once per operand pair and
+    shared by every epilogue's reference, never modified"""
+    wt = w.transpose(-1, -2)
+    return out_scale * (a @ wt), out_scale * (a.abs() @ wt.abs())
+
+
+def reference(a, w, bias=None, R=None, epilogue=0, out_scale=1.0, prod=None):
+    """The operands the kernel really multiplies (a, w as in products, or prod = products(a, w, out_scale)), bias [N] / R [..., M, N] or
+    None, all fp64 on the CPU.  Returns (ref, pre, S): the epilogue's result, its pre-activation argument and the forward-error scale."""
+    pre, S = prod if prod is not None else products(a, w, out_scale)
+    if bias is not None:
+        pre = pre + bias
+        S = S + bias.abs()
+    if epilogue == 2:
+        pre = pre + R
+        S = S + R.abs()
+    ref = gelu64(pre) if epilogue == 1 else gelu_new64(pre) if epilogue == 5 else pre
+    return ref, pre, S
+
+
+def element_bar(ref, pre, S, count, epilogue=0, planes=False):
+    bar = count * U * S
+    if epilogue in (1, 5):
+        bar = 1.13 * bar + 4 * U * ref.abs()
+    if epilogue == 5:
+        bar = bar + 2 * U * pre.abs()
+    if planes:
+        bar = bar + 2.0 ** -21 * ref.abs()
+    return bar
+
+
+def assert_elements(name, out, ref, S, bar, rel_l2_bar=None, **tags):
+    """out within bar of ref element by element (and rel_l2 below rel_l2_bar); the measured maximum of err / (u S) is recorded"""
+    out = out.detach().double().cpu().reshape(ref.shape)
+    assert bool(torch.isfinite(out).all()), f"{name} {tags}: {int((~torch.isfinite(out)).sum())} non-finite outputs"
+    err = (out - ref).abs()
+    ratio = float((err / (U * S)).max())
+    worst = float((err / bar).max())
+    rl2 = float((out - ref).norm() / ref.norm())
+    record_figure(name, max_err_over_uS=round(ratio, 3), max_err_over_bar=round(worst, 4), rel_l2=float(f"{rl2:.3e}"), **tags)
+    print(f"{name} {tags}: max err / (u S) = {ratio:.3f}, max err / bar = {worst:.4f}, rel_l2 = {rl2:.3e}")
+    if worst > 1.0:
+        at = np.unravel_index(int(torch.argmax(err / bar)), tuple(ref.shape))
+        raise AssertionError(f"{name} {tags}: element {at} is {worst:.3g} x its bar (err {float(err[at]):.3e}, u S {U * float(S[at]):.3e}); "
+                             f"{int((err > bar).sum())} elements over")
+    if rel_l2_bar is not None:
+        assert rl2 < rel_l2_bar, f"{name} {tags}: rel_l2 {rl2:.3e} >= {rel_l2_bar}"
+    return ratio
+
+
+def same_bits(a, b):
+    return int((a.view(_INT[a.dtype]) != b.view(_INT[b.dtype])).sum()) == 0
+
+
+class knobs:
+    """with knobs(LOCO_GEMM_TILE="3"): ...  -- sets the A/B knobs of gemm_f16x3.hip, reloads them, and restores the environment and
+    reloads again on the way out, also after a failure."""
+
+    def __init__(self, **env):
+        self.env = {k: v for k, v in env.items() if v is not None}
+
+    def __enter__(self):
+        import os
+        self.saved = {k: os.environ.get(k) for k in self.env}
+        os.environ.update({k: str(v) for k, v in self.env.items()})
+        lib().loco_debug_reload_gemm_knobs()
+        return self
+
+    def __exit__(self, *exc):
+        import os
+        for k, v in self.saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        lib().loco_debug_reload_gemm_knobs()
+        return False

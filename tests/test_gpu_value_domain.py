@@ -112,18 +112,20 @@ def run_f16x3(bias, M, N, K, out_split, epi=1, R=None, A=None, W=None, splitk=Fa
     ahi, alo = A if A is not None else (zeros((M, K), torch.float16),) * 2
     whi, wlo = W if W is not None else (zeros((N, K), torch.float16),) * 2
     C_ = torch.full((M, N), -7.0, device="cuda")
-    chi = torch.full((M, N), -7.0, dtype=torch.float16, device="cuda")
-    clo = torch.full((M, N), -7.0, dtype=torch.float16, device="cuda")
+    ldp = (N + 7) // 8 * 8  # planes leave as 16-byte pieces: their row stride is a multiple of 8 halves (N = 1036: 1040)
+    chi = torch.full((M, ldp), -7.0, dtype=torch.float16, device="cuda")
+    clo = torch.full((M, ldp), -7.0, dtype=torch.float16, device="cuda")
     out = (None, ptr(chi), ptr(clo)) if out_split else (ptr(C_), None, None)
+    ldc = ldp if out_split else N
     if splitk:
         ws = torch.empty(int(lib().loco_gemm_splitk_bytes()), dtype=torch.uint8, device="cuda")
-        check(lib().loco_op_gemm_f16x3_splitk(ptr(ahi), ptr(alo), K, ptr(whi), ptr(wlo), K, ptr(bias), ptr(R), N, *out, N, M, N, K, epi, ptr(ws), ws.numel(),
+        check(lib().loco_op_gemm_f16x3_splitk(ptr(ahi), ptr(alo), K, ptr(whi), ptr(wlo), K, ptr(bias), ptr(R), N, *out, ldc, M, N, K, epi, ptr(ws), ws.numel(),
                                               stream()), "gemm_f16x3_splitk")
     else:
-        check(lib().loco_op_gemm_f16x3(ptr(ahi), ptr(alo), K, ptr(whi), ptr(wlo), K, ptr(bias), ptr(R), N, *out, N, M, N, K, epi, 1, 1, 0, 0, 0, 0, stream()),
+        check(lib().loco_op_gemm_f16x3(ptr(ahi), ptr(alo), K, ptr(whi), ptr(wlo), K, ptr(bias), ptr(R), N, *out, ldc, M, N, K, epi, 1, 1, 0, 0, 0, 0, stream()),
               "gemm_f16x3")
     torch.cuda.synchronize()
-    return (chi, clo) if out_split else C_
+    return (chi[:, :N].contiguous(), clo[:, :N].contiguous()) if out_split else C_
 
 
 def gelu_through_f16x3(name, cols, out_split, splitk=False, also=None, **where):
