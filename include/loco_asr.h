@@ -376,7 +376,11 @@ int loco_op_pos_conv(const float* h, const float* w_folded, const float* bias, c
 
 /* self-attention core (modeling:911-982): qkv [B,T,2304] = [q*1/8 | k | v] per frame, qp [B,12,T,320] =
  * q_scaled . pe_k^T, frames [B] or NULL; ctx [B,T,768] = softmax(q k^T + qp[i, clip(i-j)+160] + mask) v,
- * heads merged.  Flash-style: no [T,T] tensor is ever formed. */
+ * heads merged.  Flash-style: no [T,T] tensor is ever formed.
+ * What the launch reads of clip b, with n = frames[b] (T where frames is NULL or frames[b] is <= 0 or > T): rows [0, R) of k and v,
+ * R = min(T, 64 * ceil(n / 64)), and nothing of rows [R, T).  Keys [n, R) are masked by a select, so their k rows and table entries
+ * may hold anything, NaN included; their probabilities are exactly zero but still multiply v, so rows [n, R) of v MUST BE FINITE
+ * (0 * NaN and 0 * inf are NaN).  Every row of ctx below T is written, padded query rows included; nothing else is. */
 int loco_op_attention(const float* qkv, const float* qp, const int32_t* frames, float* ctx, int32_t B, int32_t T,
                       void* stream);
 /* The probabilities of that attention (attention_probs.hip): probs [B,12,T,T] fp32 as loco_set_attention_outputs describes,
@@ -459,7 +463,9 @@ int loco_op_layernorm_f16x3(const float* x, const float* gamma, const float* bet
                             float* nonfinite_slot, int64_t rows, int32_t dim, float eps, void* stream);
 
 /* split-precision attention core: q, k and v as fp16 hi/lo planes [B*T,768] (q pre-scaled by 1/8) -- the layout the fused q|k|v
- * projection writes; the kernel transposes its V tiles with the LDS read; qp/frames/ctx as loco_op_attention. */
+ * projection writes; the kernel transposes its V tiles with the LDS read; qp/frames/ctx as loco_op_attention, and the same contract
+ * for what is read: rows [0, min(T, 64 * ceil(frames[b] / 64))) of the k and v planes of clip b, of which the v rows from frames[b]
+ * on must be finite in both planes (they are multiplied by a zero probability); the k rows there may hold anything. */
 int loco_op_attention_f16x3(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi,
                             const void* vlo, const float* qp, const int32_t* frames, float* ctx, int32_t B, int32_t T,
                             void* stream);
@@ -467,10 +473,19 @@ int loco_op_attention_f16x3(const void* qhi, const void* qlo, const void* khi, c
  * attention kernel itself (each wave for its own 32 queries) from pe_k as fp16 hi/lo planes [320][64] -- no table GEMM in front
  * of it -- into qp_scratch ([B,12,T,320] fp32: written and read back by the launch).  Only the 32-column blocks some key can read
  * are formed: afterwards row i of qp_scratch holds columns 32 * floor((lo + 160) / 32) ... 32 * floor((hi + 160) / 32) + 31 with
- * lo = max(i0 - (64 * ceil(frames / 64) - 1), -160), hi = min(i0 + 31, 159), i0 = 32 * floor(i / 32); its other entries are untouched. */
+ * lo = max(i0 - (64 * ceil(frames / 64) - 1), -160), hi = min(i0 + 31, 159), i0 = 32 * floor(i / 32); its other entries are untouched.
+ * k and v rows as loco_op_attention_f16x3: v rows from frames[b] up to min(T, 64 * ceil(frames[b] / 64)) must be finite. */
 int loco_op_attention_f16x3_pe(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
                                const void* pe_hi, const void* pe_lo, float pe_scale, float* qp_scratch, const int32_t* frames,
                                float* ctx, int32_t B, int32_t T, void* stream);
+/* The instantiations loco_forward launches: the context leaves as fp16 hi/lo planes ctx_hi / ctx_lo [B*T,768] (hi = fp16(x), lo =
+ * fp16(x - hi), bit for bit what loco_op_split_f16 makes of the fp32 context of the two entries above), the A operand of the
+ * out-projection GEMM.  pe_hi and pe_lo both NULL: qp is the input table of loco_op_attention_f16x3; both given: qp is the scratch
+ * of loco_op_attention_f16x3_pe, filled by the launch.  Exactly one of them, or any other pointer NULL: LOCO_E_INVALID.  The same
+ * contract for k and v rows: v rows from frames[b] up to min(T, 64 * ceil(frames[b] / 64)) must be finite. */
+int loco_op_attention_f16x3_planes(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
+                                   const void* pe_hi, const void* pe_lo, float pe_scale, float* qp, const int32_t* frames,
+                                   void* ctx_hi, void* ctx_lo, int32_t B, int32_t T, void* stream);
 /* loco_op_attention_probs on fp16 hi/lo planes of q (pre-scaled) and k, [B*T,768] each, as the QKV projection writes them: terms 3
  * (Qlo Khi + Qhi Klo + Qhi Khi) or 2 (the Klo term dropped) v_mfma_f32_32x32x16_f16 per product.  qp may be the qp_scratch a
  * loco_op_attention_f16x3_pe launch with the same frames has just filled: a valid key reads only columns that launch formed, and a

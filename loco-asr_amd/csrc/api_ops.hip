@@ -236,6 +236,18 @@ int loco_op_attention_f16x3_pe(const void* qhi, const void* qlo, const void* khi
     return LOCO_OK;
 }
 
+int loco_op_attention_f16x3_planes(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
+                                   const void* pe_hi, const void* pe_lo, float pe_scale, float* qp, const int32_t* frames, void* ctx_hi,
+                                   void* ctx_lo, int32_t B, int32_t T, void* stream) {
+    if (!qhi || !qlo || !khi || !klo || !vhi || !vlo || !qp || !ctx_hi || !ctx_lo)
+        return fail(LOCO_E_INVALID, "loco_op_attention_f16x3_planes: null argument");
+    if ((pe_hi == nullptr) != (pe_lo == nullptr)) return fail(LOCO_E_INVALID, "loco_op_attention_f16x3_planes: pe_hi and pe_lo go together");
+    HIP_TRY(launch_attention_f16x3((const _Float16*)qhi, (const _Float16*)qlo, (const _Float16*)khi, (const _Float16*)klo,
+                                   (const _Float16*)vhi, (const _Float16*)vlo, qp, frames, (_Float16*)ctx_hi, (_Float16*)ctx_lo, nullptr, B, T,
+                                   (hipStream_t)stream, (const _Float16*)pe_hi, (const _Float16*)pe_lo, pe_scale));
+    return LOCO_OK;
+}
+
 int loco_op_attention_probs(const float* qkv, const float* qp, const int32_t* frames, float* probs, int32_t B, int32_t T, void* stream) {
     if (!qkv || !qp || !probs) return fail(LOCO_E_INVALID, "loco_op_attention_probs: null argument");
     HIP_TRY(launch_attention_probs(qkv, nullptr, nullptr, nullptr, nullptr, qp, frames, probs, B, T, 3, (hipStream_t)stream));

@@ -1,6 +1,6 @@
 """Per-element checks of single operators: guarded outputs, poisoned inputs, fp64 references and derived error bars.
 
-Used by tests/test_gpu_gemm_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
+Used by tests/test_gpu_gemm_contract.py and tests/test_gpu_attention_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
 roundings times the forward-error scale of the element it applies to.
 
 Guards.  An output lives inside a larger allocation filled with a sentinel bit pattern (a NaN with a payload): before the first
@@ -22,6 +22,32 @@ Error bars, u = 2^-24, S[m,n] = sum_k |a_k| |w_k| + |bias[n]| + |R[m,n]| (with o
     (loco_kernels.h: 2.2e-7 = 3.7 u relative); the tanh form (epilogue 5, x / (1 + 2^y)) adds 2 u |x|: y carries ~5 u relative
     error, which 2^y turns into 3.5 |y| u relative, and |x| e^-t * 5 t u <= 5 u |x| / e over t = y ln 2 > 0.
   Plane outputs: hi + lo is compared, and hi + lo keeps 22 bits: + 2^-21 |ref|.
+
+Encoder attention (attention_f32.hip, attention_f16x3.hip), attention_bar() below.  out[i,d] = sum_j w_ij v_jd, w = softmax_j(s_ij + bias_ij)
+over the valid keys; S[i,d] = sum_j w_ij |v_jd| with the fp64 softmax w.  Everything that perturbs a probability is first expressed as an
+absolute error delta_ij of its score (a relative error of p_ij IS an absolute error of its exponent), then propagated:
+  1. Score.  64-deep dot products: f16x3_count(64) = 20 roundings of at most u A_ij, A_ij = sum_c |q_c| |k_c| (the dropped lo * lo term is
+     among the 8 of that count); the fp32 kernel f32_count(64) = 68, plus 2 for q * log2e (one rounding per element of q and the
+     constant's own half ulp).  A table entry the kernel forms itself (the pe forms) carries f16x3_count(64) + 1 roundings (the + 1:
+     * pe_scale is exact, the entry is then rounded once more when it is added) of u sum_c |q_c| |pe_c|; a table that is an INPUT is an
+     operand and carries none.  Adding the bias to the score: one rounding, u (|s_ij| + |bias_ij|).
+  2. Exponent argument.  f16x3: fma(s, log2e, (cb - m) log2e) -- cb - m rounded once, times log2e once, log2e itself half an ulp, the
+     fma once: at most 4 u (|s_ij| + |m_i - cb|) in nats; the fp32 kernel (scores already in the log2 domain, mx + cb, cb - m, s + dsh)
+     the same count.  m is a running maximum and cb one of the row's own biases, so |s_ij| + |m_i - cb| <= 2 (max_j |s_ij| + max_j |bias_ij|).
+     v_exp_f32: one ulp = 2 u relative.
+  3. Propagation.  With p_ij (1 + delta_ij) in numerator and denominator the output moves by sum_j w_ij delta_ij (v_jd - out_id), at most
+     sum_j w_ij delta_ij (|v_jd| + |out_id|) <= 2 max_j delta_ij * S[i,d]   (|out| <= S).
+  4. P V accumulation.  f16x3: 2 * terms * 4 = 24 roundings per 64-key tile (four 16-key steps of three MFMAs, two roundings each, as in
+     the GEMM count) plus one for the rescale by alpha: 25 * ntiles, each at most u S (partial sums of |p v| / l never exceed S).  fp32:
+     32 MFMAs of two products per tile and accumulator, one rounding per product, plus the rescale: 65 * ntiles.
+  5. Dropped terms (f16x3 only).  P_lo V_lo is never formed and P = hi + lo keeps 22 bits: 2^-21 S each.
+  6. Normalisation.  l = sum_j p_ij is a sum of positive terms, so its error is relative: at most 32 additions and one rescale per tile
+     and lane half, one addition across the halves, 1 / l and the final product: (33 * ntiles + 4) u |ref|.
+  7. Plane outputs: + 2^-21 |ref|, as above.
+Charged nothing: alpha and the running maximum.  p, l and O all carry the factor exp(-m) for whatever m the kernel holds; an error in
+m or in alpha = exp(m_old - m_new) scales numerator and l_run by the SAME rounded number (both are multiplied by the one alpha register),
+and the quotient does not see it.  What an inexact m does cost is the |m_i - cb| of part 2, which is charged there.
+ntiles = ceil(frames[b] / 64) of the clip.  Bar = [2 max_j delta_ij + (pv * ntiles + dropped) u] S + parts 6 and 7.
 """
 import math
 
@@ -56,6 +82,21 @@ class Layout:
             self._index = (self.head + ar(self.nb1)[:, None, None, None] * self.s1 + ar(self.nb2)[None, :, None, None] * self.s2 +
                            ar(self.rows)[None, None, :, None] * self.ld + ar(self.cols)[None, None, None, :])
             assert self._index.unique().numel() == self._index.numel(), "layout overlaps itself"
+        return self._index
+
+
+class Subset:
+    """An owned set that is no matrix: `positions` (int64, flat, relative to element 0 of the region, all below `span`) inside an
+    allocation of head + span + tail elements.  Usable wherever a Layout is, as one row of len(positions) columns."""
+
+    def __init__(self, positions, span, head=64, tail=TILE_SLACK * 320 + TILE_SLACK):
+        self.nb1 = self.nb2 = self.rows = 1
+        self.cols = int(positions.numel())
+        self.head, self.span, self.tail = head, span, tail
+        self.total = head + span + tail
+        self._index = (positions.to(device="cuda", dtype=torch.int64) + head).view(1, 1, 1, -1)
+
+    def index(self):
         return self._index
 
 
@@ -149,6 +190,25 @@ def element_bar(ref, pre, S, count, epilogue=0, planes=False):
     return bar
 
 
+def attention_bar(kernel, ref, S, A_max, P_max, s_max, b_max, ntiles, table_formed, planes=False):
+    """The attention bar of the docstring.  kernel "f32" or "f16x3"; ref, S [B, 12, T, 64]; per query row [B, 12, T, 1]: A_max = max_j sum_c
+    |q_c| |k_c|, P_max = max_j sum_c |q_c| |pe_c| of the table entries its valid keys read, s_max = max_j |s_ij|, b_max = max_j |bias_ij|;
+    ntiles [B, 1, 1, 1]; table_formed: the kernel computes the table itself (pe planes given)."""
+    x3 = kernel == "f16x3"
+    delta = (f16x3_count(64) if x3 else f32_count(64) + 2) * U * A_max
+    if table_formed:
+        delta = delta + (f16x3_count(64) + 1) * U * P_max
+    delta = delta + U * (s_max + b_max)               # score + bias
+    delta = delta + 4 * U * 2 * (s_max + b_max) + 2 * U  # exponent argument, v_exp_f32
+    bar = 2 * delta * S + (25 if x3 else 65) * ntiles * U * S
+    if x3:
+        bar = bar + 2 * 2.0 ** -21 * S
+    bar = bar + (33 * ntiles + 4) * U * ref.abs()
+    if planes:
+        bar = bar + 2.0 ** -21 * ref.abs()
+    return bar
+
+
 def assert_elements(name, out, ref, S, bar, rel_l2_bar=None, **tags):
     """out within bar of ref element by element (and rel_l2 below rel_l2_bar); the measured maximum of err / (u S) is recorded"""
     out = out.detach().double().cpu().reshape(ref.shape)
@@ -173,7 +233,7 @@ def same_bits(a, b):
 
 
 class knobs:
-    """with knobs(LOCO_GEMM_TILE="3"): ...  -- sets the A/B knobs of gemm_f16x3.hip, reloads them, and restores the environment and
+    """with knobs(LOCO_GEMM_TILE="3"): ...  -- sets the A/B knobs of gemm_f16x3.hip (or LOCO_ATTN_LONG), reloads them, and restores the environment and
     reloads again on the way out, also after a failure."""
 
     def __init__(self, **env):

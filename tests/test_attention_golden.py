@@ -41,3 +41,20 @@ def test_host_only_argument_errors():
     assert lib.loco_op_attention_probs_f16x3(d, None, d, d, d, None, d, 1, 1, 3, None) == LOCO_E_INVALID
     assert lib.loco_op_attention_probs_f16x3(d, d, d, d, d, None, d, 1, 1, 1, None) == LOCO_E_INVALID
     assert b"terms" in lib.loco_last_error()
+
+
+def test_planes_entry_argument_errors():
+    """loco_op_attention_f16x3_planes: pe_hi and pe_lo go together, every other pointer is required -- refused on the host, before a launch"""
+    lib = _libmod.load()
+    d = C.c_void_p(16)  # never dereferenced
+    planes = lib.loco_op_attention_f16x3_planes
+    ok = [d, d, d, d, d, d, d, d, 1.0, d, None, d, d, 1, 1, None]
+    for pe in ((d, None), (None, d)):
+        assert planes(*ok[:6], *pe, *ok[8:]) == LOCO_E_INVALID
+        assert b"pe_hi and pe_lo" in lib.loco_last_error()
+    for missing in (0, 1, 2, 3, 4, 5, 9, 11, 12):  # q, k, v planes, qp, ctx_hi, ctx_lo; with and without pe planes
+        for pe in ((d, d), (None, None)):
+            args = ok[:6] + list(pe) + ok[8:]
+            args[missing] = None
+            assert planes(*args) == LOCO_E_INVALID, missing
+            assert b"null argument" in lib.loco_last_error()
