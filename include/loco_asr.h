@@ -384,7 +384,14 @@ int loco_op_pos_conv(const float* h, const float* w_folded, const float* bias, c
 int loco_op_attention(const float* qkv, const float* qp, const int32_t* frames, float* ctx, int32_t B, int32_t T,
                       void* stream);
 /* The probabilities of that attention (attention_probs.hip): probs [B,12,T,T] fp32 as loco_set_attention_outputs describes,
- * qkv / qp / frames as loco_op_attention (frames NULL: every key valid).  Exact-fp32 products. */
+ * qkv / qp / frames as loco_op_attention (frames NULL: every key valid).  Exact-fp32 products.
+ * What the launch reads of clip b, with n = frames[b] (T where frames is NULL or frames[b] is <= 0 or > T): every q row [0, T), padded
+ * queries included; k rows [0, R), R = min(T, 32 * ceil(n / 32)), of which rows [n, R) are discarded by a select and may hold anything,
+ * NaN included, and nothing of k rows [R, T); no v.  Of table row i: for i < n + 158 exactly the entries its valid keys j < n select,
+ * columns clip(i - n + 1) + 160 ... clip(i) + 160 with clip(x) = min(max(x, -160), 159); for i >= n + 158 (every valid key is 159 or more
+ * frames in the past and would read column 319) NO entry: a bias that is constant over a row cancels in the softmax, and the kernel adds
+ * 0 there.  A masked key reads no entry.  Every probs[b, h, i < T, j < T] is written -- masked keys j >= n as +0.0f -- and nothing else.
+ * Scores are expected finite: a +-inf or NaN among the entries or products a valid key reads is outside the contract (NaN rows). */
 int loco_op_attention_probs(const float* qkv, const float* qp, const int32_t* frames, float* probs, int32_t B, int32_t T,
                             void* stream);
 
@@ -474,6 +481,10 @@ int loco_op_attention_f16x3(const void* qhi, const void* qlo, const void* khi, c
  * of it -- into qp_scratch ([B,12,T,320] fp32: written and read back by the launch).  Only the 32-column blocks some key can read
  * are formed: afterwards row i of qp_scratch holds columns 32 * floor((lo + 160) / 32) ... 32 * floor((hi + 160) / 32) + 31 with
  * lo = max(i0 - (64 * ceil(frames / 64) - 1), -160), hi = min(i0 + 31, 159), i0 = 32 * floor(i / 32); its other entries are untouched.
+ * lo has no upper clamp: for i0 >= 64 * ceil(frames / 64) + 159 (padded queries at least 159 frames behind the end of the last key
+ * tile: T >= 225) lo >= 160, the range is empty and the row's 320 entries are ALL untouched.  Every key of such a wave is past-clipped;
+ * it uses 0 for their common bias (c_past) in place of entry 319, which changes no probability of the row: the context is that of
+ * the true table.  A consumer of qp_scratch must not read those rows (loco_op_attention_probs_f16x3 does not).
  * k and v rows as loco_op_attention_f16x3: v rows from frames[b] up to min(T, 64 * ceil(frames[b] / 64)) must be finite. */
 int loco_op_attention_f16x3_pe(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
                                const void* pe_hi, const void* pe_lo, float pe_scale, float* qp_scratch, const int32_t* frames,
@@ -487,9 +498,13 @@ int loco_op_attention_f16x3_planes(const void* qhi, const void* qlo, const void*
                                    const void* pe_hi, const void* pe_lo, float pe_scale, float* qp, const int32_t* frames,
                                    void* ctx_hi, void* ctx_lo, int32_t B, int32_t T, void* stream);
 /* loco_op_attention_probs on fp16 hi/lo planes of q (pre-scaled) and k, [B*T,768] each, as the QKV projection writes them: terms 3
- * (Qlo Khi + Qhi Klo + Qhi Khi) or 2 (the Klo term dropped) v_mfma_f32_32x32x16_f16 per product.  qp may be the qp_scratch a
- * loco_op_attention_f16x3_pe launch with the same frames has just filled: a valid key reads only columns that launch formed, and a
- * masked key reads no table entry at all. */
+ * (Qlo Khi + Qhi Klo + Qhi Khi) or 2 (the Klo term dropped) v_mfma_f32_32x32x16_f16 per product.  Reads and writes exactly what
+ * loco_op_attention_probs does, in both planes: q rows [0, T), k rows [0, min(T, 32 * ceil(n / 32))), and of table row i the entries
+ * clip(i - n + 1) + 160 ... clip(i) + 160 for i < n + 158, none for i >= n + 158, none for a masked key.  qp may therefore be the
+ * qp_scratch a loco_op_attention_f16x3_pe launch with the same frames has just filled, whatever the allocation held before: every
+ * entry read lies in a block that launch formed (for i < n + 158 its lo is at most i - n + 1 < 160, so the range of formed blocks is
+ * not empty and covers the entries above), and the rows it leaves wholly unformed (i0 >= 64 * ceil(n / 64) + 159, all of them
+ * i >= n + 158) are not read. */
 int loco_op_attention_probs_f16x3(const void* qhi, const void* qlo, const void* khi, const void* klo, const float* qp,
                                   const int32_t* frames, float* probs, int32_t B, int32_t T, int32_t terms, void* stream);
 

@@ -454,7 +454,8 @@ int encoder_f16x3(loco_encoder* e, Call& c, const Plan& p, float* out, float* co
             HIP_TRY(launch_attention_f16x3(qshi, qslo, kshi, kslo, vshi, vslo, bf.qp, bf.frames_or_null, chi, clo, nullptr, B, T,
                                            s, e->pe_s.hi, e->pe_s.lo, e->pe_s.inv_scale));
         }
-        // the table the launch just formed in bf.qp holds every column a valid key reads (include/loco_asr.h)
+        // bf.qp now holds the blocks that launch formed, and stale workspace everywhere else -- whole rows of it where every valid key is
+        // past-clipped.  The probabilities kernel reads only formed entries: rows i >= frames + 158 read none (include/loco_asr.h)
         LOCO_TRY(run_attention_probs(e, s, nullptr, qshi, qslo, kshi, kslo, bf.qp, bf.frames_or_null, l, B, T));
         dbg_planes(e, s, "attention context planes %s", l, chi, clo, MH, kHidden);
         // out_proj + residual, LayerNorm

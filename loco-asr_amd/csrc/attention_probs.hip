@@ -14,8 +14,12 @@
 //            v_mfma_f32_32x32x2_f32.
 //   true  -- f16x3 / f16x2: q and k as fp16 hi/lo planes [B*T,768], products on v_mfma_f32_32x32x16_f16 (terms 3: Qlo Khi +
 //            Qhi Klo + Qhi Khi; terms 2: the Klo term dropped).  qp is the scratch the f16x3 attention launch has just filled: only
-//            the columns some valid key reads are present (include/loco_asr.h, loco_op_attention_f16x3_pe), so a masked key is
-//            SET to 0 and never reads qp.
+//            some 32-column blocks of it are formed (include/loco_asr.h, loco_op_attention_f16x3_pe), and for a wave whose every
+//            valid key is past-clipped none at all.  So a masked key is SET to 0 and never reads qp, and a query row i >= frames[b] +
+//            158, whose valid keys would all read column 319, adds 0 to every score instead (both forms: one rule).
+//
+// What a launch reads of clip b with n = frames[b] valid keys (the contract of include/loco_asr.h): q rows [0, T); k rows [0, 32 ceil(n / 32)),
+// capped at T, those from n on discarded by a select; of table row i the entries clip(i - n + 1) + 160 ... clip(i) + 160 if i < n + 158, none otherwise.
 //
 // Schedule: one workgroup = 4 waves = 128 consecutive query rows of one (clip, head); each wave owns 32 rows as one 32x32
 // accumulator S = Q K^T per key tile, with the QUERY as the MFMA's m index and the KEY as its n index, so lane (n, half) holds
@@ -129,9 +133,16 @@ __global__ __launch_bounds__(256) void attention_probs_kernel(const float* __res
                 for (int e = 0; e < 16; ++e) {
                     int i = i0 + 32 * st + 8 * (e >> 2) + 4 * h + (e & 3);
                     i = i < T ? i : T - 1;
-                    int rel = i - j;
-                    rel = rel < -kRelMax ? -kRelMax : (rel > kRelMax - 1 ? kRelMax - 1 : rel);
-                    acc[st][e] = (acc[st][e] + qpb[(long)i * kRelN + rel + kRelMax]) * kLog2e;
+                    // a row whose every valid key is past-clipped (its nearest one, nvalid - 1, included) would add column 319 to all of
+                    // them: a bias that is constant over the row cancels in the softmax, so the row adds 0 and reads no entry.  The f16x3
+                    // attention launch forms NO block for a wave of such rows (its c_past is 0 as well): their scratch is unformed
+                    float bias = 0.f;
+                    if (i - (nvalid - 1) < kRelMax - 1) {
+                        int rel = i - j;
+                        rel = rel < -kRelMax ? -kRelMax : (rel > kRelMax - 1 ? kRelMax - 1 : rel);
+                        bias = qpb[(long)i * kRelN + rel + kRelMax];
+                    }
+                    acc[st][e] = (acc[st][e] + bias) * kLog2e;
                 }
         }
         // the score is rounded here, in both passes: without the barrier the compiler contracts it into the next operation

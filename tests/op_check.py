@@ -1,6 +1,6 @@
 """Per-element checks of single operators: guarded outputs, poisoned inputs, fp64 references and derived error bars.
 
-Used by tests/test_gpu_gemm_contract.py and tests/test_gpu_attention_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
+Used by tests/test_gpu_gemm_contract.py, tests/test_gpu_attention_contract.py and tests/test_gpu_attention_probs_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
 roundings times the forward-error scale of the element it applies to.
 
 Guards.  An output lives inside a larger allocation filled with a sentinel bit pattern (a NaN with a payload): before the first
@@ -48,6 +48,39 @@ Charged nothing: alpha and the running maximum.  p, l and O all carry the factor
 m or in alpha = exp(m_old - m_new) scales numerator and l_run by the SAME rounded number (both are multiplied by the one alpha register),
 and the quotient does not see it.  What an inexact m does cost is the |m_i - cb| of part 2, which is charged there.
 ntiles = ceil(frames[b] / 64) of the clip.  Bar = [2 max_j delta_ij + (pv * ntiles + dropped) u] S + parts 6 and 7.
+
+Attention probabilities (attention_probs.hip), probs_bar() below.  P_ij = exp(S_ij - m_i) / l_i over the valid keys j < n, S = s + bias in
+nats.  As above, every error of an exponent's argument is an absolute error delta_ij of the score in nats and a relative error of p_ij;
+first order in u throughout.  Each count is read off the kernel's instruction sequence (the `scores` lambda, pass 1, the reduction, pass 2):
+  1. delta_ij, the `scores` lambda and the exponential of pass 2:
+     a. the product s_ij: u A_ij, A_ij = sum_c |q_c| |k_c|, times the count of the form.  f32: 32 v_mfma_f32_32x32x2_f32 in ONE chain (no
+        fold), each adding two products, one rounding per product: 64.  x3: four 16-deep k-steps of three v_mfma_f32_32x32x16_f16, two
+        roundings each as in the GEMM count: 24; the dropped Q_lo K_lo is at most 2^-22 (1 + 2^-10) A (|lo| <= 2^-11 |hi|): 5 more, 29.
+        x2: four k-steps of two MFMAs, 16; its reference (Q_hi + Q_lo) K_hi drops exactly the terms the kernel drops, so nothing more.
+        The fp16 products themselves are exact in fp32.
+     b. a table entry the f16x3 attention launch formed (the chained form): (f16x3_count(64) + 1) u sum_c |q_c| |pe_c|, part 1 of the
+        attention bar.  A table that is an input is an operand: nothing.  A row that reads no entry (i >= n + 158) has bias 0 exactly.
+     c. `acc + bias`: one rounding, u (|s_ij| + |bias_ij|).
+     d. `* kLog2e`: the constant's own rounding and the product's, 2 u |S_ij| (a relative error of the log2 score is the same relative
+        error of the score in nats).
+     e. `acc - m` in pass 2: one rounding of the difference, u |S_ij - m_i|.  m_i itself is one of the rounded scores, bit for bit the
+        same number in pass 1 and pass 2 (the rounding barrier at the end of `scores`); as in the attention bar it is charged nothing.
+     f. v_exp_f32: one ulp, 2 u.
+  2. Pass 1 sees the SAME rounded scores, so parts a-d perturb numerator and l_i alike and l_i's share is their p-weighted mean: at most
+     max_j delta_ij.  Part e has a counterpart: key j enters l through exp2(s - mn) and is then rescaled by exp2(m_old - m_new) once per
+     later tile and by exp2(m_lane - m_row) in the reduction; the running maximum only rises, so the rounded differences along that
+     chain telescope to at most u (m_i - S_ij), the same bound.  Hence |dP_ij| <= P_ij (2 max_j delta_ij + c_norm u) + FLT_MIN, the
+     FLT_MIN for a result v_exp_f32 or the final product may flush.
+  3. c_norm, what is left of l_i's roundings and the final product: per 32-key tile of pass 1, `l * exp2(m - mn) + exp2(s - mn)`: the
+     rescale's v_exp_f32 (2 u), its product and the addition: 4 per tile, ceil(n / 32) tiles; the reduction's `l * exp2(m - mr)` (v_exp_f32
+     and product: 3) and the 5 additions of the butterfly (d = 16 ... 1); `1.0f / lr` (one ulp at worst: 2); `exp2(.) * l` in pass 2 (1).
+     c_norm = 4 ceil(n / 32) + 11.  (The first key's exponential in l is part 1 f's counterpart; it is counted in row sums below.)
+  4. Row sums.  sum_j P_ij = (sum_j p2_ij) / l_i with p2 the exponentials of pass 2 and l_i the sum pass 1 formed of ITS exponentials
+     of the same scores: the score errors a-d cancel exactly, what remains is part e on both sides, the two v_exp_f32 (2 u each), c_norm
+     and one FLT_MIN per key: |sum_j P_ij - 1| <= (2 max_j |S_ij - m_i| + 4 + c_norm) u + n FLT_MIN.
+  5. The context made of these probabilities, sum_j P_ij v_jd in fp64: within sum_j bar_ij |v_jd| of the fp64 context, which is at most
+     (2 max_j delta_ij + c_norm u) S[i,d] + n FLT_MIN max |v|, so within that plus the attention bar of what the attention kernel returns.
+Scores of +-inf or NaN are outside the contract (include/loco_asr.h): exp2(inf - inf) is NaN.
 """
 import math
 
@@ -207,6 +240,30 @@ def attention_bar(kernel, ref, S, A_max, P_max, s_max, b_max, ntiles, table_form
     if planes:
         bar = bar + 2.0 ** -21 * ref.abs()
     return bar
+
+
+FLT_MIN = 2.0 ** -126
+PROBS_PRODUCT_COUNT = {"f32": 64, "x3": 29, "x2": 16}
+
+
+def probs_bar(form, P, s, bias, A, valid, n, table_abs=None):
+    """The probabilities bar of the docstring.  form "f32", "x3" or "x2"; P the fp64 softmax, s, bias, A = sum_c |q_c| |k_c| [B, 12, T, T];
+    valid bool [B, 1, 1, T]; n [B, 1, 1, 1] valid keys per clip; table_abs: sum_c |q_c| |pe_c| of each key's entry where the attention
+    launch formed the table, else None.  -> (bar [B, 12, T, T], rel [B, 12, T, 1] = 2 max_j delta_ij + c_norm u, the row sums' bar
+    [B, 12, T, 1])."""
+    S = s + bias
+    m = S.masked_fill(~valid, float("-inf")).amax(-1, keepdim=True)
+    delta = PROBS_PRODUCT_COUNT[form] * U * A                       # a
+    if table_abs is not None:
+        delta = delta + (f16x3_count(64) + 1) * U * table_abs       # b
+    delta = delta + U * (s.abs() + bias.abs())                      # c
+    delta = delta + 2 * U * S.abs()                                 # d
+    spread = (S - m).abs().masked_fill(~valid, 0.0)
+    delta = delta + U * spread + 2 * U                              # e, f
+    c_norm = 4 * torch.ceil(n / 32) + 11
+    rel = 2 * delta.masked_fill(~valid, 0.0).amax(-1, keepdim=True) + c_norm * U
+    row_sum_bar = (2 * spread.amax(-1, keepdim=True) + 4 + c_norm) * U + n * FLT_MIN
+    return P * rel + FLT_MIN, rel, row_sum_bar
 
 
 def assert_elements(name, out, ref, S, bar, rel_l2_bar=None, **tags):

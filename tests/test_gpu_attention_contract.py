@@ -111,7 +111,7 @@ class Case:
     placements.  Built once per case and shared by every test of that case; nothing in it is modified afterwards."""
 
     def __init__(self, ci):
-        T, B, frames, coherent = CASES[ci]
+        T, B, frames, coherent = CASES[ci] if isinstance(ci, int) else ci  # an index into CASES, or a (T, B, frames, coherent) of the caller's
         self.T, self.B, self.frames = T, B, frames
         self.n = valid_keys(T, B, frames)
         qkv = hu("atc.qkv", (B, T, 2304), 1.5)

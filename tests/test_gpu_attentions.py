@@ -2,7 +2,8 @@
 encoders and as a standalone op, against HF's float64 probabilities (g12) and fp64 torch restatements.
 
 Bars: max |dP| <= 1e-5 in precision modes f32 and f16x3 (the issue's 2e-5, tightened to 4x the measured figure), 5e-3 in f16x2; masked keys exactly 0; row sums within 1e-5 of 1.
-Every measured figure goes to record_figure."""
+Every measured figure goes to record_figure.  The kernel's own contract -- per element, on poisoned inputs, chained behind a real attention
+launch -- is tests/test_gpu_attention_probs_contract.py; here one forward on a 0xFF-filled workspace guards the same hazard at model level."""
 import ctypes as C
 
 import numpy as np
@@ -141,6 +142,30 @@ def test_restatement_at_real_sizes(lengths, precision):
     assert worst <= TOL[precision], worst
 
 
+def test_poisoned_workspace_reaches_no_attention():
+    """The f16x3 forward hands the probabilities kernel the table scratch its attention launch has just filled, inside a torch.empty
+    workspace.  With T >= 225 and a clip of at most 64 frames that launch forms no table block for the padded queries from row 224 on;
+    the probabilities kernel must read nothing there.  The workspace is filled with 0xFF bytes (fp32 NaN) between two calls.  A
+    regression guard only -- other stages of the forward may overwrite the region first; the proof is the x3_chain form of
+    tests/test_gpu_attention_probs_contract.py."""
+    m, sd = model(layers=2, precision="f16x3")
+    enc = m.speecht5.encoder
+    lengths = [80000, 4800]
+    speech_call(enc, lengths, output_attentions=True)  # sizes the workspace
+    enc._workspace.fill_(0xFF)
+    out = speech_call(enc, lengths, output_attentions=True, output_hidden_states=True)
+    fr = frames_of(lengths)
+    T = out.last_hidden_state.shape[1]
+    assert T >= 225 and min(fr) <= 64 and len(out.attentions) == 2
+    worst = 0.0
+    for l in range(2):
+        P = out.attentions[l]
+        rs = check_structure(P, fr, f"poisoned workspace, layer {l}")
+        worst = max(worst, float((P.double() - restate(out.hidden_states[l], sd, l, fr)).abs().max()))
+    record_figure("attentions poisoned workspace f16x3", T=T, frames=fr, max_abs=worst, row_sum_dev=rs, bar=TOL["f16x3"])
+    assert worst <= TOL["f16x3"], worst
+
+
 # ---- 3. op level ----------------------------------------------------------------------------------------------------------
 def op_inputs(B, T, seed):
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -182,7 +207,9 @@ def run_op(form, qkv, qp, frames, terms=3):
 
 
 def stale_outside_read_columns(qp, frames):
-    """NaN in every qp entry no valid key reads: what a masked key would find in the f16x3 launch's scratch"""
+    """NaN in every qp entry no valid key reads: what a masked key would find in the f16x3 launch's scratch.  A host-side model, and a
+    generous one: the real scratch also lacks the whole rows of padded queries whose every key is past-clipped
+    (tests/test_gpu_attention_probs_contract.py chains a real launch and poisons those too)."""
     B, _, T, _ = qp.shape
     qp = qp.clone()
     i = torch.arange(T, device="cuda")[:, None]
