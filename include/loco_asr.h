@@ -823,6 +823,29 @@ int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream
 int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
                          int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same for a recording of C channels, one speaker per channel (a two-channel telephone call) ---------------------------------
+ * Each channel is cut on its own energies, so overlapping speech stays two segments and every segment keeps its speaker side.  Telephone
+ * channels leak into each other, hence a CROSS-TALK GATE at the raw-mask step.  The gate and its 15 dB default (segment.py) are this
+ * project's own rule, pinned by tests/segment_channels_ref.py like the rest; they are NOT validated on real Fisher audio.
+ *   loco_op_frame_energy_db_channels   wav f32 [C, stride] (n <= stride samples of each row are read) -> db f32 [C, F]; a row's bits are
+ *               those of loco_op_frame_energy_db on that row.
+ *   loco_op_vad_segments_channels      db f32 [C, F]; one workgroup per channel runs loco_op_vad_segments' steps on row c with one
+ *               addition: mask[t] = base(t) && !(other(t) - db[c][t] > crosstalk_db), where base is the rule above (db > thr, or "not
+ *               NaN" without usable silence), other(t) the maximum of db[o][t] over the channels o != c with NaN ignored (no other
+ *               channel, or all NaN: not gated), the test one fp32 subtraction and a strict > (a difference of exactly crosstalk_db is
+ *               kept; +inf switches the gate off).  The threshold comes from the channel's own ungated histogram.  seg_start / seg_end
+ *               i32 [C, max_segments], count i32 [C], threshold_db f32 [C] as above, per channel.  overlap (may be NULL) i32
+ *               [C, max_segments]: the frames of segment k of channel c in which the cleaned mask of any other channel is 1 (a silent
+ *               channel's mask is all zero); one wave per segment, a second launch.  workspace >= loco_vad_channels_workspace_bytes(C, F)
+ *               (0 for C outside 1 .. 8 or F outside 1 .. 2^24).
+ *               Errors, before any launch, by name: null pointers (overlap excepted), C outside 1 .. 8, crosstalk_db NaN or negative,
+ *               F outside 1 .. 2^24, max_segments < 1, refused parameters, a workspace that is too small: LOCO_E_INVALID. */
+size_t loco_vad_channels_workspace_bytes(int32_t C, int64_t F);
+int loco_op_frame_energy_db_channels(const float* wav, int32_t C, int64_t n, int64_t stride, float* db, void* stream);
+int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const LocoVadParams* params, float crosstalk_db, int32_t* seg_start,
+                                  int32_t* seg_end, int32_t* overlap, int32_t max_segments, int32_t* count, float* threshold_db, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- language model: GPT-2 token negative log-likelihoods (lm.hip, lm_api.hip) --------------------------------------------------
  * The scorer of the reference's lms/ half: nll[b, s] = -log P(token s + 1 | tokens 0 .. s) under GPT-2 base (12 x 768 x 12 heads of 64
  * x 3072, checkpoint "gpt2"; any other width is refused by loco_lm_create with LOCO_E_INVALID naming the field -- gpt2-medium, -large

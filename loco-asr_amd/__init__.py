@@ -13,7 +13,7 @@ from .intent_head import IntentClassifierMI355X  # noqa: F401
 from . import lm  # noqa: F401
 from .lm import GPT2LMHeadModelMI355X  # noqa: F401
 from . import segment  # noqa: F401
-from .segment import LongSegment, LongTranscript, Segments, VadParams  # noqa: F401
+from .segment import ChannelSegments, LongSegment, LongTranscript, Segments, VadParams  # noqa: F401
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X  # noqa: F401
 from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextToSpeechMI355X,  # noqa: F401
                            scaled_positional_table)
@@ -21,4 +21,4 @@ from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextT
 __all__ = ["synth", "LIB_PATH", "LocoError", "BaseModelOutput", "Pack", "SpeechT5EncoderWithSpeechPrenetMI355X",
            "SpeechT5ForSpeechToTextMI355X", "sinusoid_table", "BatchFeature", "SpeechT5FeatureExtractorMI355X", "IntentClassifierMI355X",
            "SpeechT5EncoderWithTextPrenetMI355X", "SpeechT5ForTextToSpeechMI355X", "scaled_positional_table", "segment", "VadParams", "Segments",
-           "LongSegment", "LongTranscript", "lm", "GPT2LMHeadModelMI355X"]
+           "ChannelSegments", "LongSegment", "LongTranscript", "lm", "GPT2LMHeadModelMI355X"]

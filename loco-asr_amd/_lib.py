@@ -170,6 +170,9 @@ SIGNATURES = {
     "loco_vad_workspace_bytes": (_sz, [_i64]),
     "loco_op_frame_energy_db": (C.c_int, [_vp, _i64, _vp, _vp]),
     "loco_op_vad_segments": (C.c_int, [_vp, _i64, C.POINTER(LocoVadParams), _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "loco_vad_channels_workspace_bytes": (_sz, [_i32, _i64]),
+    "loco_op_frame_energy_db_channels": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
+    "loco_op_vad_segments_channels": (C.c_int, [_vp, _i32, _i64, C.POINTER(LocoVadParams), _f, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "loco_lm_create": (_vp, [_i32, _i32, _i32, _i32, _i32]),
     "loco_lm_destroy": (None, [_vp]),
     "loco_lm_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), C.c_int]),

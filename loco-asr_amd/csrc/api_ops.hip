@@ -349,4 +349,41 @@ int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params
     return LOCO_OK;
 }
 
+size_t loco_vad_channels_workspace_bytes(int32_t C, int64_t F) { return vad_channels_workspace_bytes((int)C, (long)F); }
+
+int loco_op_frame_energy_db_channels(const float* wav, int32_t C, int64_t n, int64_t stride, float* db, void* stream) {
+    const char* fn = "loco_op_frame_energy_db_channels";
+    if (!wav || !db) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (C < 1 || C > kVadMaxChannels) return fail(LOCO_E_INVALID, "%s: C = %d is outside 1 .. %d channels", fn, C, kVadMaxChannels);
+    if (n < kVadWindow) return fail(LOCO_E_INVALID, "%s: n = %lld samples is shorter than one frame (400)", fn, (long long)n);
+    if (loco_output_frames(n) > kVadMaxFrames)
+        return fail(LOCO_E_INVALID, "%s: n = %lld samples exceed %ld frames", fn, (long long)n, kVadMaxFrames);
+    if (stride < n) return fail(LOCO_E_INVALID, "%s: stride = %lld is below n = %lld", fn, (long long)stride, (long long)n);
+    HIP_TRY(launch_frame_energy_db_channels(wav, (int)C, (long)n, (long)stride, db, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const LocoVadParams* params, float crosstalk_db, int32_t* seg_start,
+                                  int32_t* seg_end, int32_t* overlap, int32_t max_segments, int32_t* count, float* threshold_db, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_op_vad_segments_channels";
+    if (!db || !params || !seg_start || !seg_end || !count || !threshold_db || !workspace) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (C < 1 || C > kVadMaxChannels) return fail(LOCO_E_INVALID, "%s: C = %d is outside 1 .. %d channels", fn, C, kVadMaxChannels);
+    if (!(crosstalk_db >= 0.f)) return fail(LOCO_E_INVALID, "%s: crosstalk_db = %g is NaN or negative (+inf switches the gate off)", fn, (double)crosstalk_db);
+    if (F < 1 || F > kVadMaxFrames) return fail(LOCO_E_INVALID, "%s: F = %lld is outside 1 .. %ld frames", fn, (long long)F, kVadMaxFrames);
+    if (max_segments < 1) return fail(LOCO_E_INVALID, "%s: max_segments = %d must be >= 1", fn, max_segments);
+    int32_t fr[5];
+    if (const int rc = loco_vad_frames(params, fr)) return rc;
+    if (workspace_bytes < vad_channels_workspace_bytes((int)C, (long)F))
+        return fail(LOCO_E_INVALID, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, vad_channels_workspace_bytes((int)C, (long)F));
+    const auto rank = [F](double q) {
+        const int64_t k = (int64_t)std::ceil(q * (double)F);
+        return (int)(k < 1 ? 1 : (k > F ? F : k));
+    };
+    VadArgs a{(int)F, fr[0], fr[1], fr[2], fr[3], fr[4], params->trim ? 1 : 0, rank(params->noise_quantile), rank(params->peak_quantile),
+              (float)params->margin_db, (float)params->abs_floor_db, (float)params->min_dynamic_db, max_segments};
+    HIP_TRY(launch_vad_segments_channels(db, (int)C, a, crosstalk_db, seg_start, seg_end, overlap, count, threshold_db, workspace, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
 }  // extern "C"

@@ -448,6 +448,14 @@ size_t vad_workspace_bytes(long F);
 // f32 [1] (+inf: silent recording, -inf: no usable silence), all on the device; ws >= vad_workspace_bytes(F)
 hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
                                void* ws, hipStream_t s);
+// the same per channel of a C-channel recording, with the cross-talk gate (segment.hip): wav [C, stride] -> db [C, F]; db [C, F] ->
+// seg_start / seg_end / overlap (null: not computed) i32 [C, max_segments], count i32 [C], threshold_db f32 [C];
+// ws >= vad_channels_workspace_bytes(C, F)
+constexpr int kVadMaxChannels = 8;
+hipError_t launch_frame_energy_db_channels(const float* wav, int C, long n, long stride, float* db, hipStream_t s);
+size_t vad_channels_workspace_bytes(int C, long F);
+hipError_t launch_vad_segments_channels(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end,
+                                        int32_t* overlap, int32_t* count, float* threshold_db, void* ws, hipStream_t s);
 
 // ---- GPT-2 language-model scorer (lm.hip) ----
 constexpr int kLmChunk = 1024;  // vocabulary columns of one lm_head_nll workgroup: fixed, part of the result's bits

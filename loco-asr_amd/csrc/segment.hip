@@ -11,6 +11,18 @@
 //                            atomics), the speech mask, the run boundaries (chunked count + block scan, three times: raw mask, gaps
 //                            filled, short speech dropped) and each step's scan of its window.  Sequential: the walk over cuts, at
 //                            most F / min(min_frames + 1, max_frames / 2) steps of two or three barriers each.
+// A recording of C channels with one speaker per channel (a two-channel telephone call) is cut per channel, by the same rules -- each
+// rule above is ONE __device__ function that the mono and the channel kernels share -- with one addition, the cross-talk gate
+// (restated by tests/segment_channels_ref.py; this project's own rule like the rest, its 15 dB default not validated on real calls):
+//   frame_energy_db_channels_kernel   db[c][t] for wav [C, stride]: the grid's y is the channel, a row's bits are the mono kernel's.
+//   vad_segments_channels_kernel      one workgroup per channel, the grid is C.  Channel c runs the steps above on db[c]; at the raw-mask
+//                            step a frame is also required NOT to have another channel louder by more than crosstalk_db (the maximum
+//                            over the other channels, NaN ignored; one fp32 subtraction, a strict >).  The threshold stays the
+//                            channel's own, ungated.  The other rows of db are inputs only: no workgroup waits for another.  The
+//                            cleaned mask stays in the channel's workspace slice (all zero for a silent channel).
+//   vad_overlap_kernel       a second launch, one wave per (channel, segment): the frames of the segment in which any other channel's
+//                            cleaned mask is set.
+// Channels are addressed by strides from one base pointer; there is no array of pointers in an argument struct.
 // Memory: F bytes of mask, F + 1 run boundaries and F run indices in the workspace (global; read back by other waves of the same
 // workgroup only behind __syncthreads()).  Nothing here is larger than 180 000 frames x 9 bytes for an hour of audio.
 #include <cmath>
@@ -24,17 +36,31 @@ constexpr int kVadThreads = 1024;
 constexpr int kVadWaves = kVadThreads / 64;
 typedef unsigned long long u64;
 
-__global__ __launch_bounds__(256) void frame_energy_db_kernel(const float* __restrict__ wav, long F, float* __restrict__ db) {
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= F) return;  // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const float* x = wav + t * kVadHop;
+// One frame's energy in dB, computed by one wave from the frame's 400 samples at x; the same value in every lane.
+__device__ __forceinline__ float frame_energy_db_of(const float* __restrict__ x, int lane) {
     float acc = 0.f;
 #pragma unroll
     for (int i = lane; i < kVadWindow; i += 64) acc = fmaf(x[i], x[i], acc);
     const float mean = wave_sum(acc) / (float)kVadWindow;
     // 10 log10(1e-12) is -120 exactly; log10f's last bit is not relied on for it
-    if (lane == 0) db[t] = mean == 0.f ? -120.f : 10.f * log10f(mean + 1e-12f);
+    return mean == 0.f ? -120.f : 10.f * log10f(mean + 1e-12f);
+}
+
+__global__ __launch_bounds__(256) void frame_energy_db_kernel(const float* __restrict__ wav, long F, float* __restrict__ db) {
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= F) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const float v = frame_energy_db_of(wav + t * kVadHop, lane);
+    if (lane == 0) db[t] = v;
+}
+
+// the same for C channels: wav [C, stride], db [C, F]; blockIdx.y = the channel
+__global__ __launch_bounds__(256) void frame_energy_db_channels_kernel(const float* __restrict__ wav, long stride, long F, float* __restrict__ db) {
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= F) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const float v = frame_energy_db_of(wav + (long)blockIdx.y * stride + t * kVadHop, lane);
+    if (lane == 0) db[(long)blockIdx.y * F + t] = v;
 }
 
 // 0.25 dB bins from -120 dB: the scaling by 4 is exact, so no contraction can move a value across an edge.  NaN: bin 0.
@@ -109,17 +135,38 @@ __device__ int build_runs(const unsigned char* mask, int F, int32_t* bnd, int32_
     return R;
 }
 
-__global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* __restrict__ db, VadArgs a, int32_t* __restrict__ seg_start,
-                                                                    int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
-                                                                    float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
+// The cross-talk gate of the channel kernel: frame t of channel c is not speech when another channel is louder there by more than
+// crosstalk_db.  other = the maximum over the other channels with NaN ignored; no other value: not gated.  One fp32 subtraction and a
+// strict >, so +inf switches the gate off and a difference of exactly crosstalk_db is kept.
+__device__ __forceinline__ bool vad_crosstalk_gated(const float* __restrict__ dball, int C, int c, long F, int t, float v, float crosstalk_db) {
+    bool any = false;
+    float other = 0.f;
+    for (int o = 0; o < C; ++o) {
+        if (o == c) continue;
+        const float u = dball[(long)o * F + t];
+        if (u == u) {
+            other = any ? (u > other ? u : other) : u;
+            any = true;
+        }
+    }
+    return any && (other - v > crosstalk_db);
+}
+
+// The rules of one recording (or one channel of C), run by one workgroup of kVadThreads: db = dball + c F is the channel's own row,
+// the other rows are read by the gate alone.  C == 1 is the mono kernel: no gate.  zero_silent: a silent channel leaves an all-zero
+// mask behind, for vad_overlap_kernel.
+__device__ __forceinline__ void vad_segments_body(const float* __restrict__ dball, int C, int c, float crosstalk_db, bool zero_silent, const VadArgs& a,
+                                                  int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
+                                                  float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
     __shared__ int hist[kVadBins];
     __shared__ int sh_i[kVadWaves];
     __shared__ u64 sh_q[kVadWaves];
     __shared__ int sh_mode;
     __shared__ float sh_thr;
     const int tid = threadIdx.x, F = a.F;
+    const float* __restrict__ db = dball + (long)c * F;
 
-    // ---- threshold ----
+    // ---- threshold: the channel's own histogram, not gated ----
     for (int i = tid; i < kVadBins; i += kVadThreads) hist[i] = 0;
     __syncthreads();
     for (int t = tid; t < F; t += kVadThreads) atomicAdd(&hist[vad_bin(db[t])], 1);
@@ -149,12 +196,17 @@ __global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* 
     __syncthreads();
     const int mode = sh_mode;
     const float thr = sh_thr;
-    if (mode == kVadSilent) return;  // uniform
+    if (mode == kVadSilent) {  // uniform
+        if (zero_silent)
+            for (int t = tid; t < F; t += kVadThreads) mask[t] = 0;
+        return;
+    }
 
     // ---- mask and clean-up ----
     for (int t = tid; t < F; t += kVadThreads) {
         const float v = db[t];
-        mask[t] = (mode == kVadAllSpeech ? v == v : v > thr) ? 1 : 0;
+        const bool base = mode == kVadAllSpeech ? v == v : v > thr;
+        mask[t] = (base && !(C > 1 && vad_crosstalk_gated(dball, C, c, F, t, v, crosstalk_db))) ? 1 : 0;
     }
     __syncthreads();
     int R = build_runs(mask, F, bnd, rid, sh_i);
@@ -226,6 +278,47 @@ __global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* 
     }
     if (tid == 0) *count = n <= a.max_segments ? n : -n;
 }
+
+__global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* __restrict__ db, VadArgs a, int32_t* __restrict__ seg_start,
+                                                                    int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
+                                                                    float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
+    vad_segments_body(db, 1, 0, INFINITY, false, a, seg_start, seg_end, count, thr_out, mask, bnd, rid);
+}
+
+// One workgroup per channel: channel c = blockIdx.x owns row c of db [C, F], of seg_start / seg_end [C, max_segments], count [C] and
+// thr_out [C], and the c-th slice of the workspace (slice bytes each, laid out as the mono kernel's).  The channels are addressed
+// by strides from one base pointer each.
+__global__ __launch_bounds__(kVadThreads) void vad_segments_channels_kernel(const float* __restrict__ db, int C, float crosstalk_db, VadArgs a,
+                                                                             int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end,
+                                                                             int32_t* __restrict__ count, float* __restrict__ thr_out,
+                                                                             unsigned char* ws, long slice, long bnd_off, long rid_off) {
+    const int c = blockIdx.x;
+    unsigned char* mask = ws + (long)c * slice;
+    vad_segments_body(db, C, c, crosstalk_db, true, a, seg_start + (long)c * a.max_segments, seg_end + (long)c * a.max_segments, count + c,
+                      thr_out + c, mask, reinterpret_cast<int32_t*>(mask + bnd_off), reinterpret_cast<int32_t*>(mask + rid_off));
+}
+
+// One wave per (channel, segment): overlap[c][k] = the frames of [seg_start[c][k], seg_end[c][k]) in which the cleaned mask of any
+// other channel is 1.  Runs behind vad_segments_channels_kernel on the same stream; a count beyond max_segments covers the written ones.
+__global__ __launch_bounds__(256) void vad_overlap_kernel(const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_end,
+                                                          const int32_t* __restrict__ count, int C, int max_segments,
+                                                          const unsigned char* __restrict__ ws, long slice, int32_t* __restrict__ overlap) {
+    const int c = blockIdx.y, k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int n = count[c];
+    n = n < 0 || n > max_segments ? max_segments : n;
+    if (k >= n) return;  // wave-uniform
+    const int s = seg_start[(long)c * max_segments + k], e = seg_end[(long)c * max_segments + k];
+    int acc = 0;
+    for (int t = s + lane; t < e; t += 64) {
+        int any = 0;
+        for (int o = 0; o < C; ++o)
+            if (o != c) any |= ws[(long)o * slice + t];
+        acc += any;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) overlap[(long)c * max_segments + k] = acc;
+}
 }  // namespace
 
 size_t vad_workspace_bytes(long F) {
@@ -251,6 +344,38 @@ hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_s
     int32_t* bnd = reinterpret_cast<int32_t*>(mask + mask_bytes);
     int32_t* rid = reinterpret_cast<int32_t*>(mask + mask_bytes + bnd_bytes);
     hipLaunchKernelGGL(vad_segments_kernel, dim3(1), dim3(kVadThreads), 0, s, db, a, seg_start, seg_end, count, threshold_db, mask, bnd, rid);
+    return hipGetLastError();
+}
+
+// a channel's slice: the mono workspace, rounded up so that every slice starts 16-byte aligned
+static size_t vad_channel_slice_bytes(long F) { return (vad_workspace_bytes(F) + 15) & ~(size_t)15; }
+
+size_t vad_channels_workspace_bytes(int C, long F) {
+    if (C < 1 || C > kVadMaxChannels || F < 1 || F > kVadMaxFrames) return 0;
+    return (size_t)C * vad_channel_slice_bytes(F);
+}
+
+hipError_t launch_frame_energy_db_channels(const float* wav, int C, long n, long stride, float* db, hipStream_t s) {
+    if (n < kVadWindow || C < 1 || C > kVadMaxChannels || stride < n) return hipErrorInvalidValue;
+    const long F = (n - (kVadWindow - kVadHop)) / kVadHop;
+    hipLaunchKernelGGL(frame_energy_db_channels_kernel, dim3((unsigned)((F + 3) / 4), (unsigned)C), dim3(256), 0, s, wav, stride, F, db);
+    return hipGetLastError();
+}
+
+hipError_t launch_vad_segments_channels(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end,
+                                        int32_t* overlap, int32_t* count, float* threshold_db, void* ws, hipStream_t s) {
+    if (C < 1 || C > kVadMaxChannels || a.F < 1 || a.F > kVadMaxFrames || a.max_segments < 1 || a.min_frames < 1 || a.max_frames <= a.min_frames ||
+        a.k_noise < 1 || a.k_peak < a.k_noise || a.k_peak > a.F || !(crosstalk_db >= 0.f))
+        return hipErrorInvalidValue;
+    const long slice = (long)vad_channel_slice_bytes(a.F);
+    const long mask_bytes = (long)(((size_t)a.F + 15) & ~(size_t)15), bnd_bytes = (long)((((size_t)a.F + 1) * 4 + 15) & ~(size_t)15);
+    hipLaunchKernelGGL(vad_segments_channels_kernel, dim3((unsigned)C), dim3(kVadThreads), 0, s, db, C, crosstalk_db, a, seg_start, seg_end, count,
+                       threshold_db, static_cast<unsigned char*>(ws), slice, mask_bytes, mask_bytes + bnd_bytes);
+    if (const hipError_t e = hipGetLastError()) return e;
+    if (overlap) {
+        hipLaunchKernelGGL(vad_overlap_kernel, dim3((unsigned)((a.max_segments + 3) / 4), (unsigned)C), dim3(256), 0, s, seg_start, seg_end, count, C,
+                           a.max_segments, static_cast<const unsigned char*>(ws), slice, overlap);
+    }
     return hipGetLastError();
 }
 

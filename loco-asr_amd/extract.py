@@ -69,6 +69,17 @@ def read_pcm_wav(path: str):
     SLURP's .wav files and this repo's synthetic corpora use -- or None for anything else (the caller falls back to scipy).
     One read, one frombuffer, one scaling pass: the loader threads share the interpreter lock with the thread that feeds the GPU,
     so the Python spent per file matters more than the bytes."""
+    got = _read_pcm_wav_interleaved(path)
+    if got is None:
+        return None
+    rate, channels, x = got
+    if channels > 1:
+        x = x[:x.size // channels * channels].reshape(-1, channels).mean(axis=1)
+    return rate, x
+
+
+def _read_pcm_wav_interleaved(path: str):
+    """(rate, channels, float32 samples as the file interleaves them) -- read_pcm_wav before the channels are averaged -- or None."""
     import struct
     with open(path, "rb") as fh:
         raw = fh.read()
@@ -96,9 +107,7 @@ def read_pcm_wav(path: str):
         x = np.frombuffer(raw, dtype="<f4", count=data[1] // 4, offset=data[0]).astype(np.float32)
     else:
         return None
-    if channels > 1:
-        x = x[:x.size // channels * channels].reshape(-1, channels).mean(axis=1)
-    return int(rate), x
+    return int(rate), int(channels), x
 
 
 def read_flac(path: str):
@@ -158,6 +167,55 @@ def load_audio_16k(path: str, device=None):
             if x.ndim == 2:
                 x = x.mean(axis=1)
     except Exception as e:  # a corpus of 100 000 files: the message must say WHICH one
+        raise RuntimeError(str(e) if path in str(e) else f"cannot decode {path}: {e}") from e
+    if sr != 16000:
+        return importlib.import_module("loco-asr_amd.resample").resample_to_16k(x, int(sr), device=device)
+    return x
+
+
+def read_flac_channels(path: str):
+    """(rate, float32 [channels, n]) of a FLAC file: the library's interleaved int32 ``pcm`` output times 2^-(bits-1), which is what
+    soundfile.read(dtype='float32') gives per channel; CRCs and the MD5 signature verified as in read_flac."""
+    import ctypes as C
+    lib = importlib.import_module("loco-asr_amd._lib").load()
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    sr, ch, bits, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    if lib.loco_flac_info(raw, len(raw), C.byref(sr), C.byref(ch), C.byref(bits), C.byref(total)):
+        raise RuntimeError(f"{path}: {lib.loco_flac_last_error().decode()}")
+    cap = int(total.value) if total.value > 0 else 8 * len(raw)
+    while True:
+        pcm = np.empty((cap, ch.value), dtype=np.int32)
+        n = C.c_int64()
+        rc = lib.loco_flac_decode(raw, len(raw), None, pcm.ctypes.data_as(C.c_void_p), cap, C.byref(n), 1)
+        if rc == -3 and total.value <= 0:
+            cap *= 4
+            continue
+        if rc:
+            raise RuntimeError(f"{path}: {lib.loco_flac_last_error().decode()}")
+        x = pcm[:n.value].T.astype(np.float32)
+        x *= np.float32(2.0 ** -(bits.value - 1))
+        return int(sr.value), np.ascontiguousarray(x)
+
+
+def load_audio_channels_16k(path: str, device=None):
+    """float32 [channels, n] at 16 kHz: ``load_audio_16k`` without the mix-down, for recordings with one speaker per channel (a
+    two-channel telephone call).  WAV (the formats of read_pcm_wav) and FLAC are decoded here; files at another rate are converted ON
+    THE DEVICE with the channels as the resampler's batch rows and come back as a CUDA tensor, 16 kHz files stay a numpy array on the
+    host.  The mean over the channels of the result is ``load_audio_16k``'s output."""
+    try:
+        low = path.lower()
+        if low.endswith(".wav"):
+            got = _read_pcm_wav_interleaved(path)
+            if got is None:
+                raise RuntimeError("not 16 / 32-bit PCM or 32-bit float RIFF/WAVE")
+            sr, channels, x = got
+            x = np.ascontiguousarray(x[:x.size // channels * channels].reshape(-1, channels).T)
+        elif low.endswith(".flac"):
+            sr, x = read_flac_channels(path)
+        else:
+            raise RuntimeError("per-channel reading takes .wav and .flac files")
+    except Exception as e:
         raise RuntimeError(str(e) if path in str(e) else f"cannot decode {path}: {e}") from e
     if sr != 16000:
         return importlib.import_module("loco-asr_amd.resample").resample_to_16k(x, int(sr), device=device)

@@ -3,6 +3,7 @@ pauses, so that ``SpeechT5ForSpeechToTextMI355X.transcribe_long`` can hand each 
 
     db = frame_energy_db(wave)             # f32 [F], the encoder's frames: frame t covers samples [320 t, 320 t + 400)
     seg = segment(wave, max_segment_s=15)  # Segments: frame and sample bounds on the device, count and threshold on the host
+    seg = segment_channels(waves, crosstalk_db=15.0)  # [C, n], one speaker per channel: each channel cut on its own, ChannelSegments
 
 Parity unpinned: the reference has no counterpart; the rules are pinned by the numpy restatement in tests/segment_ref.py.  CUDA
 tensors only: without a GPU both functions raise.
@@ -147,11 +148,122 @@ def segment(wave: torch.Tensor, vad=None, **params) -> Segments:
                     end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), threshold_db=t, count=k, samples=n)
 
 
+MAX_CHANNELS = 8
+DEFAULT_CROSSTALK_DB = 15.0  # this project's own rule, like the gate itself; not validated on real two-channel telephone audio
+
+
+@dataclass
+class ChannelSegments:
+    """What ``segment_channels`` returns: the segments of all channels merged into (start, channel) order.  ``channel`` i32 [count],
+    ``start_frames`` / ``end_frames`` i32 [count] (end exclusive), ``start_samples`` / ``end_samples`` i64 [count] as in Segments,
+    ``overlap_frames`` i32 [count] -- the frames of the segment in which another channel's cleaned speech mask is set -- all on the
+    device; ``threshold_db`` and ``counts``: one entry per channel, on the host; ``count`` = sum(counts)."""
+    channel: torch.Tensor
+    start_frames: torch.Tensor
+    end_frames: torch.Tensor
+    start_samples: torch.Tensor
+    end_samples: torch.Tensor
+    overlap_frames: torch.Tensor
+    threshold_db: list
+    counts: list
+    count: int
+    samples: int = 0  # of every channel
+    channels: int = 0
+
+
+def _check_crosstalk(crosstalk_db):
+    v = float(crosstalk_db)
+    if not v >= 0.0:
+        raise ValueError(f"crosstalk_db = {v:g} is NaN or negative (inf switches the gate off)")
+    return v
+
+
+def _waves(waves, what):
+    if not torch.is_tensor(waves) or not waves.is_cuda:
+        raise RuntimeError(f"{what} runs on an AMD GPU only: the waveforms must be a CUDA tensor (there is no CPU path)")
+    if waves.dim() != 2:
+        raise ValueError(f"{what}: expected waveforms [channels, samples], got {tuple(waves.shape)}")
+    if not 1 <= waves.shape[0] <= MAX_CHANNELS:
+        raise ValueError(f"{what}: {waves.shape[0]} channels are outside 1 .. {MAX_CHANNELS}")
+    if waves.shape[1] < WINDOW:
+        raise ValueError(f"{what}: {waves.shape[1]} samples are shorter than one encoder frame ({WINDOW})")
+    return waves.to(torch.float32).contiguous()
+
+
+def frame_energy_db_channels(waves: torch.Tensor) -> torch.Tensor:
+    """f32 [C, F]: ``frame_energy_db`` of every row of a [C, samples] 16 kHz CUDA tensor in one launch; a row's bits are the mono op's."""
+    waves = _waves(waves, "frame_energy_db_channels")
+    lib = _lib.load()
+    ch, n = int(waves.shape[0]), int(waves.shape[1])
+    db = torch.empty((ch, int(lib.loco_output_frames(n))), dtype=torch.float32, device=waves.device)
+    with torch.cuda.device(waves.device):
+        _lib.check(lib.loco_op_frame_energy_db_channels(C.c_void_p(waves.data_ptr()), ch, n, int(waves.stride(0)), C.c_void_p(db.data_ptr()),
+                                                        C.c_void_p(torch.cuda.current_stream(waves.device).cuda_stream)),
+                   "loco_op_frame_energy_db_channels")
+    return db
+
+
+def segments_channels_from_db(db: torch.Tensor, params: VadParams, crosstalk_db: float = DEFAULT_CROSSTALK_DB,
+                              max_segments: Optional[int] = None, overlap: bool = True):
+    """The per-channel segmentation kernel (and the overlap kernel) on a given f32 [C, F] CUDA tensor: (start_frames i32
+    [C, max_segments], end_frames, overlap_frames or None, count i32 [C], threshold f32 [C]), all on the device, nothing read back."""
+    crosstalk_db = _check_crosstalk(crosstalk_db)
+    if not torch.is_tensor(db) or not db.is_cuda or db.dim() != 2 or db.dtype != torch.float32:
+        raise RuntimeError("segments_channels_from_db: db must be a 2-D float32 CUDA tensor [channels, frames] (there is no CPU path)")
+    db = db.contiguous()
+    lib = _lib.load()
+    ch, F = int(db.shape[0]), int(db.shape[1])
+    maxf, minf = params.frames()[:2]
+    if max_segments is None:
+        max_segments = F // min(minf + 1, maxf // 2) + 1
+    dev = db.device
+    start = torch.empty((ch, max(int(max_segments), 0)), dtype=torch.int32, device=dev)
+    end = torch.empty_like(start)
+    over = torch.zeros_like(start) if overlap else None
+    count = torch.empty(ch, dtype=torch.int32, device=dev)
+    thr = torch.empty(ch, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.loco_vad_channels_workspace_bytes(ch, F))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.loco_op_vad_segments_channels(C.c_void_p(db.data_ptr()), ch, F, C.byref(params.to_c()), crosstalk_db, C.c_void_p(start.data_ptr()),
+                                                     C.c_void_p(end.data_ptr()), C.c_void_p(over.data_ptr()) if overlap else None, int(max_segments),
+                                                     C.c_void_p(count.data_ptr()), C.c_void_p(thr.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "loco_op_vad_segments_channels")
+    return start, end, over, count, thr
+
+
+def segment_channels(waves: torch.Tensor, crosstalk_db: float = DEFAULT_CROSSTALK_DB, vad=None, **params) -> ChannelSegments:
+    """Cut every channel of a [C, samples] 16 kHz CUDA tensor at its own pauses (one speaker per channel): three launches (energies,
+    one workgroup per channel, overlap), then the counts and the thresholds are read back together.  A frame of a channel is not speech
+    when another channel is louder there by more than ``crosstalk_db`` (inf: no gate).  Parameters as ``segment``."""
+    p = resolve_params(vad, **params)
+    crosstalk_db = _check_crosstalk(crosstalk_db)
+    waves = _waves(waves, "segment_channels")
+    ch, n = int(waves.shape[0]), int(waves.shape[1])
+    db = frame_energy_db_channels(waves)
+    start, end, over, count, thr = segments_channels_from_db(db, p, crosstalk_db)
+    host = torch.cat([count.to(torch.float64), thr.to(torch.float64)]).cpu().tolist()  # the one read-back: both are exact in float64
+    counts, thrs = [int(v) for v in host[:ch]], host[ch:]
+    for c, k in enumerate(counts):
+        if k < 0:
+            raise _lib.LocoError(f"segment_channels: {-k} segments of channel {c} exceed the {start.shape[1]} the rules allow for {db.shape[1]} frames")
+    dev = waves.device
+    chan = torch.cat([torch.full((k,), c, dtype=torch.int32, device=dev) for c, k in enumerate(counts)])
+    flat = lambda t: torch.cat([t[c, :k] for c, k in enumerate(counts)])  # noqa: E731
+    start, end, over = flat(start), flat(end), flat(over)
+    order = torch.argsort(start.to(torch.int64) * MAX_CHANNELS + chan.to(torch.int64))  # the keys are distinct: (start, channel) order
+    chan, start, end, over = chan[order], start[order], end[order], over[order]
+    return ChannelSegments(channel=chan, start_frames=start, end_frames=end, start_samples=start.to(torch.int64) * HOP,
+                           end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), overlap_frames=over,
+                           threshold_db=thrs, counts=counts, count=sum(counts), samples=n, channels=ch)
+
+
 @dataclass
 class LongSegment:
     """One segment of a LongTranscript: ``start_s`` / ``end_s`` in recording time, ``ids`` a 1-D LongTensor (host) as ``generate_many``
     returns it; ``token_logprobs`` [len - 1] (device), ``logprob`` and ``avg_logprob`` with ``return_scores``; ``token_times`` f32
-    [len - 1, 2] (host), start and end of every generated token in recording time, with ``timestamps``."""
+    [len - 1, 2] (host), start and end of every generated token in recording time, with ``timestamps``.  From ``transcribe_channels``
+    also ``channel`` (the index of the segment's channel) and ``overlap_s``, the seconds of it in which another channel speaks."""
     start_s: float
     end_s: float
     ids: torch.Tensor
@@ -159,11 +271,14 @@ class LongSegment:
     logprob: Optional[float] = None
     avg_logprob: Optional[float] = None
     token_times: Optional[torch.Tensor] = None
+    channel: Optional[int] = None
+    overlap_s: Optional[float] = None
 
 
 @dataclass
 class LongTranscript:
-    """What ``transcribe_long`` returns: the segments in time order, the recording's length and the speech threshold used."""
+    """What ``transcribe_long`` returns: the segments in time order, the recording's length and the speech threshold used.  From
+    ``transcribe_channels``: the segments of all channels in (start, channel) order and ``threshold_db`` a list, one per channel."""
     segments: list
     duration_s: float
     threshold_db: float

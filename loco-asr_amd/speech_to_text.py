@@ -484,6 +484,43 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                 o.token_times = torch.stack([al.start_times, al.end_times], dim=1).cpu() + o.start_s
         return seg.LongTranscript(segments=out, duration_s=duration, threshold_db=segs.threshold_db)
 
+    @torch.no_grad()
+    def transcribe_channels(self, waveforms: torch.Tensor, crosstalk_db: float = seg.DEFAULT_CROSSTALK_DB, vad=None, max_length: Optional[int] = None,
+                            slots: int = 64, pack: int = 8, return_scores: bool = False, timestamps: bool = False, do_normalize: bool = False):
+        """``transcribe_long`` for a recording with one speaker per channel (a two-channel telephone call): ``waveforms`` is a
+        [channels, samples] 16 kHz CUDA tensor.  Every channel is cut at its own pauses (segment.segment_channels; a frame in which
+        another channel is louder by more than ``crosstalk_db`` is not speech), and every segment of every channel is a batch of ONE
+        clip, ``waveforms[c, s:e][None]``: all of them go through one ``generate_many`` (and one ``align_many`` with ``timestamps``), so
+        a segment's ids depend on its own samples alone.
+
+        Returns a segment.LongTranscript in (start, channel) order; its segments also carry ``channel`` and ``overlap_s``, and its
+        ``threshold_db`` is a list with one threshold per channel."""
+        self._require_decoder("transcribe_channels()")
+        params = seg.resolve_params(vad)
+        cap = dec.resolve_max_length(dec.MAX_TEXT_POSITIONS if max_length is None else max_length)
+        segs = seg.segment_channels(waveforms, crosstalk_db, params)
+        duration = segs.samples / seg.SAMPLE_RATE
+        if segs.count == 0:
+            return seg.LongTranscript(segments=[], duration_s=duration, threshold_db=segs.threshold_db)
+        from .feature_extractor import SpeechT5FeatureExtractorMI355X
+        fe = SpeechT5FeatureExtractorMI355X(do_normalize=do_normalize)
+        table = torch.stack([segs.channel.to(torch.int64), segs.start_samples, segs.end_samples, segs.overlap_frames.to(torch.int64)]).cpu().tolist()
+        bounds = list(zip(*table))  # one read-back: (channel, start, end, overlap frames) per segment
+        waves = waveforms.to(torch.float32)
+        batches = [fe(audio=[waves[c, s:e]], sampling_rate=seg.SAMPLE_RATE) for c, s, e, _ in bounds]
+        rows = self.generate_many(batches, max_length=cap, slots=slots, pack=pack, return_scores=return_scores)
+        ids, scores = rows if return_scores else (rows, None)
+        out = [seg.LongSegment(start_s=s / seg.SAMPLE_RATE, end_s=e / seg.SAMPLE_RATE, ids=r, channel=c, overlap_s=o / seg.FRAME_RATE)
+               for (c, s, e, o), r in zip(bounds, ids)]
+        if return_scores:
+            sums = [float(v) for v in torch.stack([t.double().sum() for t in scores]).cpu().tolist()]  # one read-back
+            for o, t, v in zip(out, scores, sums):
+                o.token_logprobs, o.logprob, o.avg_logprob = t, v, v / max(int(t.shape[0]), 1)
+        if timestamps:
+            for o, al in zip(out, self.align_many(batches, [r[1:] for r in ids], pack=pack)):
+                o.token_times = torch.stack([al.start_times, al.end_times], dim=1).cpu() + o.start_s
+        return seg.LongTranscript(segments=out, duration_s=duration, threshold_db=segs.threshold_db)
+
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, precision: str = "f16x3", **_unused):
         """``SpeechT5ForSpeechToText.from_pretrained(...)`` of the fine-tuned script (…finetuned…py:95) for a checkpoint ON

@@ -18,6 +18,11 @@ or ``--random-init`` (the deterministic synthetic weights).
 ``--max-segment-s``, ``--min-silence-s``, ``--vad-margin-db``, ``--no-trim``) and its segments are decoded in the slot pool
 (``transcribe_long``; ``--slots`` defaults to 64).  One JSON line per recording: {"id", "duration_s", "threshold_db", "segments":
 [{"start_s", "end_s", "token_ids", "text"?, "logprob"?, "avg_logprob"?, "token_times"?}], "text"?}, the times in recording time.
+``--channels split`` (default ``mix``: the channels are averaged, as ever) cuts and decodes every channel of a file on its own -- one
+speaker per channel, as in a two-channel telephone call (``transcribe_channels``; ``--crosstalk-db X``: a frame is not speech when
+another channel is louder by more than X dB, default 15).  Segments then also carry "channel" ("A", "B", ... by index) and "overlap_s",
+they come in (start, channel) order, and "threshold_db" is a list per channel.  ``--kaldi-text FILE`` (with ``split`` and a tokenizer
+on disk) also writes one Kaldi line per segment with text, ``<rec>-<A|B>-<%06d start>-<%06d end> <text>`` in centiseconds: eval_ppl's input.
 """
 from __future__ import annotations
 
@@ -123,6 +128,73 @@ def build_model(args):
     return model.to("cuda")
 
 
+def channel_name(index):
+    """"A", "B", ... by channel index, as Fisher's data preparation names channel 1 and channel 2."""
+    return chr(ord("A") + int(index))
+
+
+def kaldi_rec_id(path):
+    """The recording id of a file: its base name without the extension, ``-`` and whitespace replaced by ``_`` -- eval_ppl takes an
+    utterance id up to its first ``-`` as the recording."""
+    return "".join("_" if ch == "-" or ch.isspace() else ch for ch in os.path.splitext(os.path.basename(path))[0])
+
+
+def kaldi_text_lines(rec_id, segments):
+    """Kaldi ``utt_id text`` lines of one recording, ``<rec>-<A|B|..>-<%06d start>-<%06d end> <text>`` with start and end in
+    centiseconds: start = start_samples // 160, end = ceil(end_samples / 160), integers both.  ``segments``: (channel index,
+    start_samples, end_samples, text) in the order to write; a segment whose text is empty (or blank) is left out.  A pure function."""
+    lines = []
+    for channel, start, end, text in segments:
+        text = " ".join(str(text).split())
+        if text:
+            lines.append(f"{rec_id}-{channel_name(channel)}-{int(start) // 160:06d}-{-(-int(end) // 160):06d} {text}")
+    return lines
+
+
+def main_long_split(args, vad, slots):
+    """``--long --channels split``: every channel of every FILE is cut and decoded on its own (``transcribe_channels``)."""
+    from .extract import load_audio_channels_16k
+    tok = load_tokenizer(args.tokenizer)
+    if args.kaldi_text and tok is None:
+        raise SystemExit("--kaldi-text needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): its lines are text")
+    model = build_model(args)
+    device = torch.device("cuda", torch.cuda.current_device())
+    fh = sys.stdout if args.out == "-" else open(args.out, "w")
+    kh = open(args.kaldi_text, "w", encoding="utf-8") if args.kaldi_text else None
+    try:
+        for path in args.files:
+            x = load_audio_channels_16k(path, device=device)
+            x = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))
+            res = model.transcribe_channels(x.to(device), crosstalk_db=args.crosstalk_db, vad=vad, max_length=args.max_length, slots=slots,
+                                            pack=args.pack, return_scores=args.scores, timestamps=args.timestamps, do_normalize=args.do_normalize)
+            rec = {"id": os.path.splitext(os.path.basename(path))[0], "duration_s": round(res.duration_s, 4),
+                   "threshold_db": [t if math.isfinite(t) else None for t in res.threshold_db], "segments": []}  # JSON has no infinities
+            kaldi = []
+            for sg in res.segments:
+                row = sg.ids.tolist()
+                one = {"channel": channel_name(sg.channel), "start_s": round(sg.start_s, 4), "end_s": round(sg.end_s, 4),
+                       "overlap_s": round(sg.overlap_s, 4), "token_ids": row}
+                if tok is not None:
+                    one["text"] = tok.decode(strip_special(row))
+                    kaldi.append((sg.channel, round(sg.start_s * 16000), round(sg.end_s * 16000), one["text"]))
+                if args.scores:
+                    one["logprob"], one["avg_logprob"] = sg.logprob, sg.avg_logprob
+                if args.timestamps:
+                    one["token_times"] = [[round(a, 4), round(b, 4)] for a, b in sg.token_times.tolist()]
+                rec["segments"].append(one)
+            if tok is not None:
+                rec["text"] = " ".join(one["text"] for one in rec["segments"])
+            fh.write(json.dumps(rec) + "\n")
+            if kh is not None:
+                kh.writelines(line + "\n" for line in kaldi_text_lines(kaldi_rec_id(path), kaldi))
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
+        if kh is not None:
+            kh.close()
+    return 0
+
+
 def main_long(args, ap):
     """``--long``: every FILE is one recording.  Flag combinations and segmentation parameters are refused before a model is built."""
     from .segment import resolve_params
@@ -141,6 +213,15 @@ def main_long(args, ap):
         vad = resolve_params(None, trim=not args.no_trim, **given)
     except ValueError as e:
         raise SystemExit(f"--max-segment-s / --min-silence-s / --vad-margin-db: {e}")
+    if args.channels != "split":
+        for flag, v in (("--crosstalk-db", args.crosstalk_db), ("--kaldi-text", args.kaldi_text)):
+            if v is not None:
+                raise SystemExit(f"{flag} needs --channels split: only there does a segment have a channel")
+    else:
+        args.crosstalk_db = 15.0 if args.crosstalk_db is None else args.crosstalk_db
+        if not args.crosstalk_db >= 0.0:
+            raise SystemExit(f"--crosstalk-db: crosstalk_db = {args.crosstalk_db:g} is NaN or negative (inf switches the gate off)")
+        return main_long_split(args, vad, slots)
     model = build_model(args)
     tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
@@ -205,11 +286,18 @@ def main(argv=None):
     ap.add_argument("--min-silence-s", type=float, default=None, help="with --long: shortest pause that counts as one (default 0.3)")
     ap.add_argument("--vad-margin-db", type=float, default=None, help="with --long: speech is this far above the noise level (default 10)")
     ap.add_argument("--no-trim", action="store_true", help="with --long: keep each segment's leading and trailing silence (segments then tile the recording)")
+    ap.add_argument("--channels", choices=["mix", "split"], default=None, help="with --long: mix (default) averages a file's channels into one "
+                    "recording; split cuts and decodes every channel on its own (one speaker per channel, as in a two-channel telephone call)")
+    ap.add_argument("--crosstalk-db", type=float, default=None, help="with --channels split: a frame is not speech when another channel is louder "
+                    "there by more than this (default 15; inf = no gate)")
+    ap.add_argument("--kaldi-text", default=None, metavar="FILE", help="with --channels split and a tokenizer on disk: also write Kaldi 'utt_id text' "
+                    "lines, <rec>-<A|B>-<start>-<end> in centiseconds, the input of eval_ppl")
     args = ap.parse_args(argv)
     if args.long:
         return main_long(args, ap)
     for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
-                    ("--no-trim", args.no_trim or None)):
+                    ("--no-trim", args.no_trim or None), ("--channels", args.channels), ("--crosstalk-db", args.crosstalk_db),
+                    ("--kaldi-text", args.kaldi_text)):
         if v is not None:
             raise SystemExit(f"{flag} needs --long")
     if args.batch_size < 1:
