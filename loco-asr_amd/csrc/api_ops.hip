@@ -318,55 +318,33 @@ int loco_vad_frames(const LocoVadParams* p, int32_t* frames) {
 }
 
 size_t loco_vad_workspace_bytes(int64_t F) { return vad_workspace_bytes((long)F); }
-
-int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream) {
-    const char* fn = "loco_op_frame_energy_db";
-    if (!wav || !db) return fail(LOCO_E_INVALID, "%s: null argument", fn);
-    if (n < kVadWindow) return fail(LOCO_E_INVALID, "%s: n = %lld samples is shorter than one frame (400)", fn, (long long)n);
-    if (loco_output_frames(n) > kVadMaxFrames)
-        return fail(LOCO_E_INVALID, "%s: n = %lld samples exceed %ld frames", fn, (long long)n, kVadMaxFrames);
-    HIP_TRY(launch_frame_energy_db(wav, (long)n, db, (hipStream_t)stream));
-    return LOCO_OK;
-}
-
-int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
-                         int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "loco_op_vad_segments";
-    if (!db || !params || !seg_start || !seg_end || !count || !threshold_db || !workspace) return fail(LOCO_E_INVALID, "%s: null argument", fn);
-    if (F < 1 || F > kVadMaxFrames) return fail(LOCO_E_INVALID, "%s: F = %lld is outside 1 .. %ld frames", fn, (long long)F, kVadMaxFrames);
-    if (max_segments < 1) return fail(LOCO_E_INVALID, "%s: max_segments = %d must be >= 1", fn, max_segments);
-    int32_t fr[5];
-    if (const int rc = loco_vad_frames(params, fr)) return rc;
-    if (workspace_bytes < vad_workspace_bytes((long)F))
-        return fail(LOCO_E_INVALID, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, vad_workspace_bytes((long)F));
-    const auto rank = [F](double q) {
-        const int64_t k = (int64_t)std::ceil(q * (double)F);
-        return (int)(k < 1 ? 1 : (k > F ? F : k));
-    };
-    VadArgs a{(int)F, fr[0], fr[1], fr[2], fr[3], fr[4], params->trim ? 1 : 0, rank(params->noise_quantile), rank(params->peak_quantile),
-              (float)params->margin_db, (float)params->abs_floor_db, (float)params->min_dynamic_db, max_segments};
-    HIP_TRY(launch_vad_segments(db, a, seg_start, seg_end, count, threshold_db, workspace, (hipStream_t)stream));
-    return LOCO_OK;
-}
-
 size_t loco_vad_channels_workspace_bytes(int32_t C, int64_t F) { return vad_channels_workspace_bytes((int)C, (long)F); }
 
-int loco_op_frame_energy_db_channels(const float* wav, int32_t C, int64_t n, int64_t stride, float* db, void* stream) {
-    const char* fn = "loco_op_frame_energy_db_channels";
+// Both energy entries, fn = the entry's name; the mono entry is C = 1 with stride = n.
+static int frame_energy_db_checked(const char* fn, const float* wav, int32_t C, int64_t n, int64_t stride, float* db, void* stream) {
     if (!wav || !db) return fail(LOCO_E_INVALID, "%s: null argument", fn);
     if (C < 1 || C > kVadMaxChannels) return fail(LOCO_E_INVALID, "%s: C = %d is outside 1 .. %d channels", fn, C, kVadMaxChannels);
     if (n < kVadWindow) return fail(LOCO_E_INVALID, "%s: n = %lld samples is shorter than one frame (400)", fn, (long long)n);
     if (loco_output_frames(n) > kVadMaxFrames)
         return fail(LOCO_E_INVALID, "%s: n = %lld samples exceed %ld frames", fn, (long long)n, kVadMaxFrames);
     if (stride < n) return fail(LOCO_E_INVALID, "%s: stride = %lld is below n = %lld", fn, (long long)stride, (long long)n);
-    HIP_TRY(launch_frame_energy_db_channels(wav, (int)C, (long)n, (long)stride, db, (hipStream_t)stream));
+    HIP_TRY(launch_frame_energy_db(wav, (int)C, (long)n, (long)stride, db, (hipStream_t)stream));
     return LOCO_OK;
 }
 
-int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const LocoVadParams* params, float crosstalk_db, int32_t* seg_start,
-                                  int32_t* seg_end, int32_t* overlap, int32_t max_segments, int32_t* count, float* threshold_db, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    const char* fn = "loco_op_vad_segments_channels";
+int loco_op_frame_energy_db(const float* wav, int64_t n, float* db, void* stream) {
+    return frame_energy_db_checked("loco_op_frame_energy_db", wav, 1, n, n, db, stream);
+}
+
+int loco_op_frame_energy_db_channels(const float* wav, int32_t C, int64_t n, int64_t stride, float* db, void* stream) {
+    return frame_energy_db_checked("loco_op_frame_energy_db_channels", wav, C, n, stride, db, stream);
+}
+
+// Both segmentation entries, fn = the entry's name, need = the workspace the entry asks for; the mono entry is C = 1 with the gate off
+// (+inf), no overlap and need = loco_vad_workspace_bytes(F), which is all a one-channel launch touches.
+static int vad_segments_checked(const char* fn, const float* db, int32_t C, int64_t F, const LocoVadParams* params, float crosstalk_db,
+                                int32_t* seg_start, int32_t* seg_end, int32_t* overlap, int32_t max_segments, int32_t* count, float* threshold_db,
+                                void* workspace, size_t workspace_bytes, size_t need, void* stream) {
     if (!db || !params || !seg_start || !seg_end || !count || !threshold_db || !workspace) return fail(LOCO_E_INVALID, "%s: null argument", fn);
     if (C < 1 || C > kVadMaxChannels) return fail(LOCO_E_INVALID, "%s: C = %d is outside 1 .. %d channels", fn, C, kVadMaxChannels);
     if (!(crosstalk_db >= 0.f)) return fail(LOCO_E_INVALID, "%s: crosstalk_db = %g is NaN or negative (+inf switches the gate off)", fn, (double)crosstalk_db);
@@ -374,16 +352,28 @@ int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const L
     if (max_segments < 1) return fail(LOCO_E_INVALID, "%s: max_segments = %d must be >= 1", fn, max_segments);
     int32_t fr[5];
     if (const int rc = loco_vad_frames(params, fr)) return rc;
-    if (workspace_bytes < vad_channels_workspace_bytes((int)C, (long)F))
-        return fail(LOCO_E_INVALID, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, vad_channels_workspace_bytes((int)C, (long)F));
+    if (workspace_bytes < need) return fail(LOCO_E_INVALID, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
     const auto rank = [F](double q) {
         const int64_t k = (int64_t)std::ceil(q * (double)F);
         return (int)(k < 1 ? 1 : (k > F ? F : k));
     };
     VadArgs a{(int)F, fr[0], fr[1], fr[2], fr[3], fr[4], params->trim ? 1 : 0, rank(params->noise_quantile), rank(params->peak_quantile),
               (float)params->margin_db, (float)params->abs_floor_db, (float)params->min_dynamic_db, max_segments};
-    HIP_TRY(launch_vad_segments_channels(db, (int)C, a, crosstalk_db, seg_start, seg_end, overlap, count, threshold_db, workspace, (hipStream_t)stream));
+    HIP_TRY(launch_vad_segments(db, (int)C, a, crosstalk_db, seg_start, seg_end, overlap, count, threshold_db, workspace, (hipStream_t)stream));
     return LOCO_OK;
+}
+
+int loco_op_vad_segments(const float* db, int64_t F, const LocoVadParams* params, int32_t* seg_start, int32_t* seg_end, int32_t max_segments,
+                         int32_t* count, float* threshold_db, void* workspace, size_t workspace_bytes, void* stream) {
+    return vad_segments_checked("loco_op_vad_segments", db, 1, F, params, INFINITY, seg_start, seg_end, nullptr, max_segments, count, threshold_db,
+                                workspace, workspace_bytes, vad_workspace_bytes((long)F), stream);
+}
+
+int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const LocoVadParams* params, float crosstalk_db, int32_t* seg_start,
+                                  int32_t* seg_end, int32_t* overlap, int32_t max_segments, int32_t* count, float* threshold_db, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return vad_segments_checked("loco_op_vad_segments_channels", db, C, F, params, crosstalk_db, seg_start, seg_end, overlap, max_segments, count,
+                                threshold_db, workspace, workspace_bytes, vad_channels_workspace_bytes((int)C, (long)F), stream);
 }
 
 }  // extern "C"

@@ -441,21 +441,18 @@ struct VadArgs {  // by value; everything the host derives from LocoVadParams an
     float margin_db, abs_floor_db, min_dynamic_db;
     int max_segments;
 };
-// db[t] = 10 log10(mean of x^2 over frame t + 1e-12) for t < (n - 80) / 320; n >= 400
-hipError_t launch_frame_energy_db(const float* wav, long n, float* db, hipStream_t s);
-size_t vad_workspace_bytes(long F);
-// one recording, one workgroup: seg_start / seg_end i32 [max_segments], count i32 [1] (negative: -needed > max_segments), threshold_db
-// f32 [1] (+inf: silent recording, -inf: no usable silence), all on the device; ws >= vad_workspace_bytes(F)
-hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
-                               void* ws, hipStream_t s);
-// the same per channel of a C-channel recording, with the cross-talk gate (segment.hip): wav [C, stride] -> db [C, F]; db [C, F] ->
-// seg_start / seg_end / overlap (null: not computed) i32 [C, max_segments], count i32 [C], threshold_db f32 [C];
-// ws >= vad_channels_workspace_bytes(C, F)
 constexpr int kVadMaxChannels = 8;
-hipError_t launch_frame_energy_db_channels(const float* wav, int C, long n, long stride, float* db, hipStream_t s);
+// wav [C, stride] -> db [C, F]: db[c][t] = 10 log10(mean of x^2 over frame t of row c + 1e-12) for t < F = (n - 80) / 320; n >= 400,
+// stride >= n.  A mono recording is C = 1.
+hipError_t launch_frame_energy_db(const float* wav, int C, long n, long stride, float* db, hipStream_t s);
+// one workgroup per channel, with the cross-talk gate between channels (segment.hip): db [C, F] -> seg_start / seg_end / overlap (null:
+// not computed, no second launch) i32 [C, max_segments], count i32 [C] (negative: -needed > max_segments), threshold_db f32 [C] (+inf:
+// silent channel, -inf: no usable silence), all on the device; ws >= vad_channels_workspace_bytes(C, F).  A mono recording is C = 1 with
+// crosstalk_db = +inf, and touches no more than vad_workspace_bytes(F) of ws.
+size_t vad_workspace_bytes(long F);
 size_t vad_channels_workspace_bytes(int C, long F);
-hipError_t launch_vad_segments_channels(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end,
-                                        int32_t* overlap, int32_t* count, float* threshold_db, void* ws, hipStream_t s);
+hipError_t launch_vad_segments(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end, int32_t* overlap,
+                               int32_t* count, float* threshold_db, void* ws, hipStream_t s);
 
 // ---- GPT-2 language-model scorer (lm.hip) ----
 constexpr int kLmChunk = 1024;  // vocabulary columns of one lm_head_nll workgroup: fixed, part of the result's bits

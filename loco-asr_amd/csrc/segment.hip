@@ -5,26 +5,27 @@
 //
 // Frames are the encoder's: frame t covers samples [320 t, 320 t + 400), F = loco_output_frames(n) = (n - 80) / 320.
 //
-//   frame_energy_db_kernel   db[t] = 10 log10(mean(x^2) + 1e-12): one wave per frame, lane l squares samples l, l + 64, ... in that
-//                            order with fmaf, the lanes meet in wave_sum -- a frame's bits do not depend on where it is computed.
-//   vad_segments_kernel      ONE workgroup of 1024 threads per recording.  Parallel across the workgroup: the histogram (LDS integer
-//                            atomics), the speech mask, the run boundaries (chunked count + block scan, three times: raw mask, gaps
-//                            filled, short speech dropped) and each step's scan of its window.  Sequential: the walk over cuts, at
-//                            most F / min(min_frames + 1, max_frames / 2) steps of two or three barriers each.
-// A recording of C channels with one speaker per channel (a two-channel telephone call) is cut per channel, by the same rules -- each
-// rule above is ONE __device__ function that the mono and the channel kernels share -- with one addition, the cross-talk gate
-// (restated by tests/segment_channels_ref.py; this project's own rule like the rest, its 15 dB default not validated on real calls):
-//   frame_energy_db_channels_kernel   db[c][t] for wav [C, stride]: the grid's y is the channel, a row's bits are the mono kernel's.
-//   vad_segments_channels_kernel      one workgroup per channel, the grid is C.  Channel c runs the steps above on db[c]; at the raw-mask
-//                            step a frame is also required NOT to have another channel louder by more than crosstalk_db (the maximum
-//                            over the other channels, NaN ignored; one fp32 subtraction, a strict >).  The threshold stays the
-//                            channel's own, ungated.  The other rows of db are inputs only: no workgroup waits for another.  The
-//                            cleaned mask stays in the channel's workspace slice (all zero for a silent channel).
+// A recording has C channels with one speaker per channel (a two-channel telephone call); a mono recording is C = 1, the same kernels
+// launched with one channel.  Every channel is cut on its own, by the same rules:
+//   frame_energy_db_kernel   db[c][t] = 10 log10(mean(x^2) + 1e-12) for wav [C, stride]: the grid's y is the channel, one wave per frame,
+//                            lane l squares samples l, l + 64, ... in that order with fmaf, the lanes meet in wave_sum -- a frame's bits
+//                            do not depend on where it is computed.
+//   vad_segments_kernel      ONE workgroup of 1024 threads per channel, the grid is C.  Parallel across the workgroup: the histogram (LDS
+//                            integer atomics), the speech mask, the run boundaries (chunked count + block scan, three times: raw mask,
+//                            gaps filled, short speech dropped) and each step's scan of its window.  Sequential: the walk over cuts, at
+//                            most F / min(min_frames + 1, max_frames / 2) steps of two or three barriers each.  With C > 1 there is one
+//                            addition, the cross-talk gate (restated by tests/segment_channels_ref.py; this project's own rule like the
+//                            rest, its 15 dB default not validated on real calls): at the raw-mask step a frame is also required NOT to
+//                            have another channel louder by more than crosstalk_db (the maximum over the other channels, NaN ignored;
+//                            one fp32 subtraction, a strict >).  The threshold stays the channel's own, ungated.  The other rows of db
+//                            are inputs only: no workgroup waits for another, and a one-channel launch (the kernel template's other
+//                            instantiation, compiled without the gate) reads no other row.  The cleaned mask stays in the channel's
+//                            workspace slice (all zero for a silent channel).
 //   vad_overlap_kernel       a second launch, one wave per (channel, segment): the frames of the segment in which any other channel's
 //                            cleaned mask is set.
 // Channels are addressed by strides from one base pointer; there is no array of pointers in an argument struct.
-// Memory: F bytes of mask, F + 1 run boundaries and F run indices in the workspace (global; read back by other waves of the same
-// workgroup only behind __syncthreads()).  Nothing here is larger than 180 000 frames x 9 bytes for an hour of audio.
+// Memory: per channel F bytes of mask, F + 1 run boundaries and F run indices in the workspace (vad_layout; global, read back by other
+// waves of the same workgroup only behind __syncthreads()).  Nothing here is larger than 180 000 frames x 9 bytes for an hour of audio.
 #include <cmath>
 
 #include "loco_kernels.h"
@@ -46,16 +47,8 @@ __device__ __forceinline__ float frame_energy_db_of(const float* __restrict__ x,
     return mean == 0.f ? -120.f : 10.f * log10f(mean + 1e-12f);
 }
 
-__global__ __launch_bounds__(256) void frame_energy_db_kernel(const float* __restrict__ wav, long F, float* __restrict__ db) {
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= F) return;  // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const float v = frame_energy_db_of(wav + t * kVadHop, lane);
-    if (lane == 0) db[t] = v;
-}
-
-// the same for C channels: wav [C, stride], db [C, F]; blockIdx.y = the channel
-__global__ __launch_bounds__(256) void frame_energy_db_channels_kernel(const float* __restrict__ wav, long stride, long F, float* __restrict__ db) {
+// wav [C, stride] -> db [C, F]; blockIdx.y = the channel
+__global__ __launch_bounds__(256) void frame_energy_db_kernel(const float* __restrict__ wav, long stride, long F, float* __restrict__ db) {
     const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= F) return;  // wave-uniform
     const int lane = threadIdx.x & 63;
@@ -152,19 +145,31 @@ __device__ __forceinline__ bool vad_crosstalk_gated(const float* __restrict__ db
     return any && (other - v > crosstalk_db);
 }
 
-// The rules of one recording (or one channel of C), run by one workgroup of kVadThreads: db = dball + c F is the channel's own row,
-// the other rows are read by the gate alone.  C == 1 is the mono kernel: no gate.  zero_silent: a silent channel leaves an all-zero
-// mask behind, for vad_overlap_kernel.
-__device__ __forceinline__ void vad_segments_body(const float* __restrict__ dball, int C, int c, float crosstalk_db, bool zero_silent, const VadArgs& a,
-                                                  int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
-                                                  float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
+// The rules of one channel, run by one workgroup of kVadThreads: channel ch = blockIdx.x owns row ch of dball [C, F], of seg_start /
+// seg_end [C, max_segments], count [C] and thr_out [C], and the ch-th slice of the workspace (vad_layout: the mask at 0, bnd at
+// bnd_off, rid at rid_off); the other rows of dball are read by the gate alone.  kMono is the C == 1 launch, compiled without the gate
+// and with ch = 0 (as one kernel with a uniform `C > 1 &&` in front of the gate the one-channel launch measured about 1 % slower):
+// it reads no other row and touches nothing beyond the one slice's vad_layout().bytes.  A silent channel leaves an all-zero mask
+// behind, for vad_overlap_kernel -- with kMono too, where nothing reads it: F bytes of caller-provided scratch, no output depends on them.
+template <bool kMono>
+__global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* __restrict__ dball, int C, float crosstalk_db, VadArgs a,
+                                                                    int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end,
+                                                                    int32_t* __restrict__ count, float* __restrict__ thr_out, unsigned char* ws,
+                                                                    long slice, long bnd_off, long rid_off) {
     __shared__ int hist[kVadBins];
     __shared__ int sh_i[kVadWaves];
     __shared__ u64 sh_q[kVadWaves];
     __shared__ int sh_mode;
     __shared__ float sh_thr;
-    const int tid = threadIdx.x, F = a.F;
-    const float* __restrict__ db = dball + (long)c * F;
+    const int tid = threadIdx.x, F = a.F, ch = kMono ? 0 : blockIdx.x;
+    const float* __restrict__ db = dball + (long)ch * F;
+    unsigned char* mask = ws + (long)ch * slice;
+    int32_t* bnd = reinterpret_cast<int32_t*>(mask + bnd_off);
+    int32_t* rid = reinterpret_cast<int32_t*>(mask + rid_off);
+    seg_start += (long)ch * a.max_segments;
+    seg_end += (long)ch * a.max_segments;
+    count += ch;
+    thr_out += ch;
 
     // ---- threshold: the channel's own histogram, not gated ----
     for (int i = tid; i < kVadBins; i += kVadThreads) hist[i] = 0;
@@ -197,8 +202,7 @@ __device__ __forceinline__ void vad_segments_body(const float* __restrict__ dbal
     const int mode = sh_mode;
     const float thr = sh_thr;
     if (mode == kVadSilent) {  // uniform
-        if (zero_silent)
-            for (int t = tid; t < F; t += kVadThreads) mask[t] = 0;
+        for (int t = tid; t < F; t += kVadThreads) mask[t] = 0;
         return;
     }
 
@@ -206,7 +210,7 @@ __device__ __forceinline__ void vad_segments_body(const float* __restrict__ dbal
     for (int t = tid; t < F; t += kVadThreads) {
         const float v = db[t];
         const bool base = mode == kVadAllSpeech ? v == v : v > thr;
-        mask[t] = (base && !(C > 1 && vad_crosstalk_gated(dball, C, c, F, t, v, crosstalk_db))) ? 1 : 0;
+        mask[t] = (base && !(!kMono && vad_crosstalk_gated(dball, C, ch, F, t, v, crosstalk_db))) ? 1 : 0;
     }
     __syncthreads();
     int R = build_runs(mask, F, bnd, rid, sh_i);
@@ -279,27 +283,8 @@ __device__ __forceinline__ void vad_segments_body(const float* __restrict__ dbal
     if (tid == 0) *count = n <= a.max_segments ? n : -n;
 }
 
-__global__ __launch_bounds__(kVadThreads) void vad_segments_kernel(const float* __restrict__ db, VadArgs a, int32_t* __restrict__ seg_start,
-                                                                    int32_t* __restrict__ seg_end, int32_t* __restrict__ count,
-                                                                    float* __restrict__ thr_out, unsigned char* mask, int32_t* bnd, int32_t* rid) {
-    vad_segments_body(db, 1, 0, INFINITY, false, a, seg_start, seg_end, count, thr_out, mask, bnd, rid);
-}
-
-// One workgroup per channel: channel c = blockIdx.x owns row c of db [C, F], of seg_start / seg_end [C, max_segments], count [C] and
-// thr_out [C], and the c-th slice of the workspace (slice bytes each, laid out as the mono kernel's).  The channels are addressed
-// by strides from one base pointer each.
-__global__ __launch_bounds__(kVadThreads) void vad_segments_channels_kernel(const float* __restrict__ db, int C, float crosstalk_db, VadArgs a,
-                                                                             int32_t* __restrict__ seg_start, int32_t* __restrict__ seg_end,
-                                                                             int32_t* __restrict__ count, float* __restrict__ thr_out,
-                                                                             unsigned char* ws, long slice, long bnd_off, long rid_off) {
-    const int c = blockIdx.x;
-    unsigned char* mask = ws + (long)c * slice;
-    vad_segments_body(db, C, c, crosstalk_db, true, a, seg_start + (long)c * a.max_segments, seg_end + (long)c * a.max_segments, count + c,
-                      thr_out + c, mask, reinterpret_cast<int32_t*>(mask + bnd_off), reinterpret_cast<int32_t*>(mask + rid_off));
-}
-
 // One wave per (channel, segment): overlap[c][k] = the frames of [seg_start[c][k], seg_end[c][k]) in which the cleaned mask of any
-// other channel is 1.  Runs behind vad_segments_channels_kernel on the same stream; a count beyond max_segments covers the written ones.
+// other channel is 1.  Runs behind vad_segments_kernel on the same stream; a count beyond max_segments covers the written ones.
 __global__ __launch_bounds__(256) void vad_overlap_kernel(const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_end,
                                                           const int32_t* __restrict__ count, int C, int max_segments,
                                                           const unsigned char* __restrict__ ws, long slice, int32_t* __restrict__ overlap) {
@@ -321,60 +306,42 @@ __global__ __launch_bounds__(256) void vad_overlap_kernel(const int32_t* __restr
 }
 }  // namespace
 
-size_t vad_workspace_bytes(long F) {
-    if (F < 1 || F > kVadMaxFrames) return 0;
-    const size_t mask = ((size_t)F + 15) & ~(size_t)15, bnd = (((size_t)F + 1) * 4 + 15) & ~(size_t)15;
-    return mask + bnd + (size_t)F * 4;
+// A channel's part of the workspace: the mask (F bytes) at 0, F + 1 run boundaries at bnd_off, F run indices at rid_off, `bytes` in all
+// -- what a one-channel launch touches at most; channel c's part starts at c * slice, so that every slice is 16-byte aligned.
+struct VadLayout {
+    long bnd_off, rid_off, bytes, slice;
+};
+static VadLayout vad_layout(long F) {
+    const long bnd_off = (F + 15) & ~15L, rid_off = bnd_off + (((F + 1) * 4 + 15) & ~15L), bytes = rid_off + F * 4;
+    return {bnd_off, rid_off, bytes, (bytes + 15) & ~15L};
 }
 
-hipError_t launch_frame_energy_db(const float* wav, long n, float* db, hipStream_t s) {
-    if (n < kVadWindow) return hipErrorInvalidValue;
-    const long F = (n - (kVadWindow - kVadHop)) / kVadHop;  // 320 (F - 1) + 399 <= n - 1
-    hipLaunchKernelGGL(frame_energy_db_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, wav, F, db);
-    return hipGetLastError();
-}
-
-hipError_t launch_vad_segments(const float* db, const VadArgs& a, int32_t* seg_start, int32_t* seg_end, int32_t* count, float* threshold_db,
-                               void* ws, hipStream_t s) {
-    if (a.F < 1 || a.F > kVadMaxFrames || a.max_segments < 1 || a.min_frames < 1 || a.max_frames <= a.min_frames || a.k_noise < 1 ||
-        a.k_peak < a.k_noise || a.k_peak > a.F)
-        return hipErrorInvalidValue;
-    unsigned char* mask = static_cast<unsigned char*>(ws);
-    const size_t mask_bytes = ((size_t)a.F + 15) & ~(size_t)15, bnd_bytes = (((size_t)a.F + 1) * 4 + 15) & ~(size_t)15;
-    int32_t* bnd = reinterpret_cast<int32_t*>(mask + mask_bytes);
-    int32_t* rid = reinterpret_cast<int32_t*>(mask + mask_bytes + bnd_bytes);
-    hipLaunchKernelGGL(vad_segments_kernel, dim3(1), dim3(kVadThreads), 0, s, db, a, seg_start, seg_end, count, threshold_db, mask, bnd, rid);
-    return hipGetLastError();
-}
-
-// a channel's slice: the mono workspace, rounded up so that every slice starts 16-byte aligned
-static size_t vad_channel_slice_bytes(long F) { return (vad_workspace_bytes(F) + 15) & ~(size_t)15; }
+size_t vad_workspace_bytes(long F) { return F < 1 || F > kVadMaxFrames ? 0 : (size_t)vad_layout(F).bytes; }
 
 size_t vad_channels_workspace_bytes(int C, long F) {
-    if (C < 1 || C > kVadMaxChannels || F < 1 || F > kVadMaxFrames) return 0;
-    return (size_t)C * vad_channel_slice_bytes(F);
+    return C < 1 || C > kVadMaxChannels || F < 1 || F > kVadMaxFrames ? 0 : (size_t)C * (size_t)vad_layout(F).slice;
 }
 
-hipError_t launch_frame_energy_db_channels(const float* wav, int C, long n, long stride, float* db, hipStream_t s) {
+hipError_t launch_frame_energy_db(const float* wav, int C, long n, long stride, float* db, hipStream_t s) {
     if (n < kVadWindow || C < 1 || C > kVadMaxChannels || stride < n) return hipErrorInvalidValue;
-    const long F = (n - (kVadWindow - kVadHop)) / kVadHop;
-    hipLaunchKernelGGL(frame_energy_db_channels_kernel, dim3((unsigned)((F + 3) / 4), (unsigned)C), dim3(256), 0, s, wav, stride, F, db);
+    const long F = (n - (kVadWindow - kVadHop)) / kVadHop;  // 320 (F - 1) + 399 <= n - 1
+    hipLaunchKernelGGL(frame_energy_db_kernel, dim3((unsigned)((F + 3) / 4), (unsigned)C), dim3(256), 0, s, wav, stride, F, db);
     return hipGetLastError();
 }
 
-hipError_t launch_vad_segments_channels(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end,
-                                        int32_t* overlap, int32_t* count, float* threshold_db, void* ws, hipStream_t s) {
+hipError_t launch_vad_segments(const float* db, int C, const VadArgs& a, float crosstalk_db, int32_t* seg_start, int32_t* seg_end, int32_t* overlap,
+                               int32_t* count, float* threshold_db, void* ws, hipStream_t s) {
     if (C < 1 || C > kVadMaxChannels || a.F < 1 || a.F > kVadMaxFrames || a.max_segments < 1 || a.min_frames < 1 || a.max_frames <= a.min_frames ||
         a.k_noise < 1 || a.k_peak < a.k_noise || a.k_peak > a.F || !(crosstalk_db >= 0.f))
         return hipErrorInvalidValue;
-    const long slice = (long)vad_channel_slice_bytes(a.F);
-    const long mask_bytes = (long)(((size_t)a.F + 15) & ~(size_t)15), bnd_bytes = (long)((((size_t)a.F + 1) * 4 + 15) & ~(size_t)15);
-    hipLaunchKernelGGL(vad_segments_channels_kernel, dim3((unsigned)C), dim3(kVadThreads), 0, s, db, C, crosstalk_db, a, seg_start, seg_end, count,
-                       threshold_db, static_cast<unsigned char*>(ws), slice, mask_bytes, mask_bytes + bnd_bytes);
+    const VadLayout l = vad_layout(a.F);
+    const auto kernel = C == 1 ? vad_segments_kernel<true> : vad_segments_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)C), dim3(kVadThreads), 0, s, db, C, crosstalk_db, a, seg_start, seg_end, count, threshold_db,
+                       static_cast<unsigned char*>(ws), l.slice, l.bnd_off, l.rid_off);
     if (const hipError_t e = hipGetLastError()) return e;
     if (overlap) {
         hipLaunchKernelGGL(vad_overlap_kernel, dim3((unsigned)((a.max_segments + 3) / 4), (unsigned)C), dim3(256), 0, s, seg_start, seg_end, count, C,
-                           a.max_segments, static_cast<const unsigned char*>(ws), slice, overlap);
+                           a.max_segments, static_cast<const unsigned char*>(ws), l.slice, overlap);
     }
     return hipGetLastError();
 }

@@ -85,69 +85,6 @@ class Segments:
     samples: int = 0  # of the waveform
 
 
-def _wave(wave, what):
-    if not torch.is_tensor(wave) or not wave.is_cuda:
-        raise RuntimeError(f"{what} runs on an AMD GPU only: the waveform must be a CUDA tensor (there is no CPU path)")
-    if wave.dim() != 1:
-        raise ValueError(f"{what}: expected a 1-D waveform [samples], got {tuple(wave.shape)}")
-    if wave.shape[0] < WINDOW:
-        raise ValueError(f"{what}: {wave.shape[0]} samples are shorter than one encoder frame ({WINDOW})")
-    return wave.to(torch.float32).contiguous()
-
-
-def frame_energy_db(wave: torch.Tensor) -> torch.Tensor:
-    """f32 [F]: 10 log10(mean(x^2) + 1e-12) of every encoder frame of a 1-D 16 kHz CUDA waveform."""
-    wave = _wave(wave, "frame_energy_db")
-    lib = _lib.load()
-    n = int(wave.shape[0])
-    db = torch.empty(int(lib.loco_output_frames(n)), dtype=torch.float32, device=wave.device)
-    with torch.cuda.device(wave.device):
-        _lib.check(lib.loco_op_frame_energy_db(C.c_void_p(wave.data_ptr()), n, C.c_void_p(db.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)), "loco_op_frame_energy_db")
-    return db
-
-
-def segments_from_db(db: torch.Tensor, params: VadParams, max_segments: Optional[int] = None):
-    """The segmentation kernel on a given f32 [F] CUDA tensor: (start_frames i32 [max_segments], end_frames, count i32 [1], threshold
-    f32 [1]), all on the device and nothing read back.  ``max_segments`` None = the most the rules can produce for F frames."""
-    if not torch.is_tensor(db) or not db.is_cuda or db.dim() != 1 or db.dtype != torch.float32:
-        raise RuntimeError("segments_from_db: db must be a 1-D float32 CUDA tensor (there is no CPU path)")
-    db = db.contiguous()
-    lib = _lib.load()
-    F = int(db.shape[0])
-    maxf, minf = params.frames()[:2]
-    if max_segments is None:  # every step but the last advances by at least min(min_frames + 1, max_frames // 2) frames
-        max_segments = F // min(minf + 1, maxf // 2) + 1
-    dev = db.device
-    start = torch.empty(max(int(max_segments), 0), dtype=torch.int32, device=dev)
-    end = torch.empty_like(start)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    thr = torch.empty(1, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.loco_vad_workspace_bytes(F))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.loco_op_vad_segments(C.c_void_p(db.data_ptr()), F, C.byref(params.to_c()), C.c_void_p(start.data_ptr()), C.c_void_p(end.data_ptr()),
-                                            int(max_segments), C.c_void_p(count.data_ptr()), C.c_void_p(thr.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                            ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "loco_op_vad_segments")
-    return start, end, count, thr
-
-
-def segment(wave: torch.Tensor, vad=None, **params) -> Segments:
-    """Cut a 1-D 16 kHz CUDA waveform at pauses: two launches (energy, segmentation), then the count and the threshold are
-    read back.  Parameters: the fields of VadParams, as keywords or as ``vad`` (a VadParams or a dict)."""
-    p = resolve_params(vad, **params)
-    wave = _wave(wave, "segment")
-    n = int(wave.shape[0])
-    db = frame_energy_db(wave)
-    start, end, count, thr = segments_from_db(db, p)
-    k, t = int(count.item()), float(thr.item())
-    if k < 0:
-        raise _lib.LocoError(f"segment: {-k} segments exceed the {start.shape[0]} the rules allow for {db.shape[0]} frames")
-    start, end = start[:k], end[:k]
-    return Segments(start_frames=start, end_frames=end, start_samples=start.to(torch.int64) * HOP,
-                    end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), threshold_db=t, count=k, samples=n)
-
-
 MAX_CHANNELS = 8
 DEFAULT_CROSSTALK_DB = 15.0  # this project's own rule, like the gate itself; not validated on real two-channel telephone audio
 
@@ -171,6 +108,8 @@ class ChannelSegments:
     channels: int = 0
 
 
+# A mono recording is the one-channel case: everything below works on [C, ...] tensors, and with ``mono`` on the same tensors without
+# the leading dimension -- C = 1, no extra view or row-0 operation on the way, the messages and the C entry point the mono function's own.
 def _check_crosstalk(crosstalk_db):
     v = float(crosstalk_db)
     if not v >= 0.0:
@@ -178,84 +117,135 @@ def _check_crosstalk(crosstalk_db):
     return v
 
 
-def _waves(waves, what):
+def _waves(waves, what, mono=False):
+    """The checked waveforms as contiguous f32 [C, samples]; ``mono``: [samples]."""
     if not torch.is_tensor(waves) or not waves.is_cuda:
-        raise RuntimeError(f"{what} runs on an AMD GPU only: the waveforms must be a CUDA tensor (there is no CPU path)")
-    if waves.dim() != 2:
-        raise ValueError(f"{what}: expected waveforms [channels, samples], got {tuple(waves.shape)}")
-    if not 1 <= waves.shape[0] <= MAX_CHANNELS:
+        raise RuntimeError(f"{what} runs on an AMD GPU only: the waveform{'' if mono else 's'} must be a CUDA tensor (there is no CPU path)")
+    if waves.dim() != (1 if mono else 2):
+        raise ValueError(f"{what}: expected {'a 1-D waveform [samples]' if mono else 'waveforms [channels, samples]'}, got {tuple(waves.shape)}")
+    if not mono and not 1 <= waves.shape[0] <= MAX_CHANNELS:
         raise ValueError(f"{what}: {waves.shape[0]} channels are outside 1 .. {MAX_CHANNELS}")
-    if waves.shape[1] < WINDOW:
-        raise ValueError(f"{what}: {waves.shape[1]} samples are shorter than one encoder frame ({WINDOW})")
+    if waves.shape[-1] < WINDOW:
+        raise ValueError(f"{what}: {waves.shape[-1]} samples are shorter than one encoder frame ({WINDOW})")
     return waves.to(torch.float32).contiguous()
 
 
-def frame_energy_db_channels(waves: torch.Tensor) -> torch.Tensor:
-    """f32 [C, F]: ``frame_energy_db`` of every row of a [C, samples] 16 kHz CUDA tensor in one launch; a row's bits are the mono op's."""
-    waves = _waves(waves, "frame_energy_db_channels")
+def _energy(waves, mono=False):
+    """f32 [C, F] of checked waveforms [C, samples] in one launch."""
     lib = _lib.load()
-    ch, n = int(waves.shape[0]), int(waves.shape[1])
-    db = torch.empty((ch, int(lib.loco_output_frames(n))), dtype=torch.float32, device=waves.device)
+    ch, n, F = 1 if mono else int(waves.shape[0]), int(waves.shape[-1]), int(lib.loco_output_frames(int(waves.shape[-1])))
+    db = torch.empty((F,) if mono else (ch, F), dtype=torch.float32, device=waves.device)  # a plain tuple: a torch.Size parses slower
     with torch.cuda.device(waves.device):
-        _lib.check(lib.loco_op_frame_energy_db_channels(C.c_void_p(waves.data_ptr()), ch, n, int(waves.stride(0)), C.c_void_p(db.data_ptr()),
-                                                        C.c_void_p(torch.cuda.current_stream(waves.device).cuda_stream)),
-                   "loco_op_frame_energy_db_channels")
+        stream = torch.cuda.current_stream(waves.device).cuda_stream  # pointers go as plain integers: the argtypes say void*
+        if mono:
+            _lib.check(lib.loco_op_frame_energy_db(waves.data_ptr(), n, db.data_ptr(), stream), "loco_op_frame_energy_db")
+        else:
+            _lib.check(lib.loco_op_frame_energy_db_channels(waves.data_ptr(), ch, n, int(waves.stride(0)), db.data_ptr(), stream),
+                       "loco_op_frame_energy_db_channels")
     return db
+
+
+def _segments_from_db(db, params, crosstalk_db, max_segments, overlap, mono=False):
+    """The segmentation launch (and the overlap launch) on a checked f32 [C, F] CUDA tensor: (start_frames i32 [C, max_segments],
+    end_frames, overlap_frames or None, count i32 [C], threshold f32 [C]), all on the device and nothing read back."""
+    db = db.contiguous()
+    lib = _lib.load()
+    ch, F = 1 if mono else int(db.shape[0]), int(db.shape[-1])
+    maxf, minf = params.frames()[:2]
+    if max_segments is None:  # every step but the last advances by at least min(min_frames + 1, max_frames // 2) frames
+        max_segments = F // min(minf + 1, maxf // 2) + 1
+    dev = db.device
+    start = torch.empty((max(int(max_segments), 0),) if mono else (ch, max(int(max_segments), 0)), dtype=torch.int32, device=dev)
+    end = torch.empty_like(start)
+    over = torch.zeros_like(start) if overlap else None
+    count = torch.empty(ch, dtype=torch.int32, device=dev)
+    thr = torch.empty(ch, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.loco_vad_workspace_bytes(F) if mono else lib.loco_vad_channels_workspace_bytes(ch, F))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        par = C.byref(params.to_c())
+        tail = (int(max_segments), count.data_ptr(), thr.data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
+        if mono:
+            _lib.check(lib.loco_op_vad_segments(db.data_ptr(), F, par, start.data_ptr(), end.data_ptr(), *tail), "loco_op_vad_segments")
+        else:
+            _lib.check(lib.loco_op_vad_segments_channels(db.data_ptr(), ch, F, par, crosstalk_db, start.data_ptr(), end.data_ptr(),
+                                                         over.data_ptr() if overlap else None, *tail), "loco_op_vad_segments_channels")
+    return start, end, over, count, thr
+
+
+def _segment(waves, params, crosstalk_db, what, mono=False):
+    """``segment_channels`` on checked arguments; ``mono``: one channel, no overlap launch and ``overlap_frames`` None."""
+    ch, n = 1 if mono else int(waves.shape[0]), int(waves.shape[-1])
+    db = _energy(waves, mono)
+    start, end, over, count, thr = _segments_from_db(db, params, crosstalk_db, None, not mono, mono)
+    if mono:
+        start, end = start[None], end[None]
+    host = torch.cat([count.to(torch.float64), thr.to(torch.float64)]).cpu().tolist()  # the one read-back: both are exact in float64
+    counts, thrs = [int(v) for v in host[:ch]], host[ch:]
+    for c, k in enumerate(counts):
+        if k < 0:
+            raise _lib.LocoError(f"{what}: {-k} segments{'' if mono else f' of channel {c}'} exceed the {start.shape[1]} the rules allow "
+                                 f"for {db.shape[-1]} frames")
+    dev = waves.device
+    chan = torch.cat([torch.full((k,), c, dtype=torch.int32, device=dev) for c, k in enumerate(counts)])
+    flat = lambda t: torch.cat([t[c, :k] for c, k in enumerate(counts)])  # noqa: E731
+    start, end, over = flat(start), flat(end), None if mono else flat(over)
+    if ch > 1:
+        order = torch.argsort(start.to(torch.int64) * MAX_CHANNELS + chan.to(torch.int64))  # the keys are distinct: (start, channel) order
+        chan, start, end, over = chan[order], start[order], end[order], over[order]
+    return ChannelSegments(channel=chan, start_frames=start, end_frames=end, start_samples=start.to(torch.int64) * HOP,
+                           end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), overlap_frames=over,
+                           threshold_db=thrs, counts=counts, count=sum(counts), samples=n, channels=ch)
+
+
+def frame_energy_db_channels(waves: torch.Tensor) -> torch.Tensor:
+    """f32 [C, F]: 10 log10(mean(x^2) + 1e-12) of every encoder frame of every row of a [C, samples] 16 kHz CUDA tensor in one launch; a
+    row's bits do not depend on the rows beside it."""
+    return _energy(_waves(waves, "frame_energy_db_channels"))
+
+
+def frame_energy_db(wave: torch.Tensor) -> torch.Tensor:
+    """f32 [F]: ``frame_energy_db_channels`` of a 1-D 16 kHz CUDA waveform, the one-channel case."""
+    return _energy(_waves(wave, "frame_energy_db", mono=True), mono=True)
 
 
 def segments_channels_from_db(db: torch.Tensor, params: VadParams, crosstalk_db: float = DEFAULT_CROSSTALK_DB,
                               max_segments: Optional[int] = None, overlap: bool = True):
     """The per-channel segmentation kernel (and the overlap kernel) on a given f32 [C, F] CUDA tensor: (start_frames i32
-    [C, max_segments], end_frames, overlap_frames or None, count i32 [C], threshold f32 [C]), all on the device, nothing read back."""
+    [C, max_segments], end_frames, overlap_frames or None, count i32 [C], threshold f32 [C]), all on the device, nothing read back.
+    ``max_segments`` None = the most the rules can produce for F frames."""
     crosstalk_db = _check_crosstalk(crosstalk_db)
     if not torch.is_tensor(db) or not db.is_cuda or db.dim() != 2 or db.dtype != torch.float32:
         raise RuntimeError("segments_channels_from_db: db must be a 2-D float32 CUDA tensor [channels, frames] (there is no CPU path)")
-    db = db.contiguous()
-    lib = _lib.load()
-    ch, F = int(db.shape[0]), int(db.shape[1])
-    maxf, minf = params.frames()[:2]
-    if max_segments is None:
-        max_segments = F // min(minf + 1, maxf // 2) + 1
-    dev = db.device
-    start = torch.empty((ch, max(int(max_segments), 0)), dtype=torch.int32, device=dev)
-    end = torch.empty_like(start)
-    over = torch.zeros_like(start) if overlap else None
-    count = torch.empty(ch, dtype=torch.int32, device=dev)
-    thr = torch.empty(ch, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.loco_vad_channels_workspace_bytes(ch, F))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.loco_op_vad_segments_channels(C.c_void_p(db.data_ptr()), ch, F, C.byref(params.to_c()), crosstalk_db, C.c_void_p(start.data_ptr()),
-                                                     C.c_void_p(end.data_ptr()), C.c_void_p(over.data_ptr()) if overlap else None, int(max_segments),
-                                                     C.c_void_p(count.data_ptr()), C.c_void_p(thr.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes,
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "loco_op_vad_segments_channels")
-    return start, end, over, count, thr
+    return _segments_from_db(db, params, crosstalk_db, max_segments, overlap)
+
+
+def segments_from_db(db: torch.Tensor, params: VadParams, max_segments: Optional[int] = None):
+    """The one-channel case on a given f32 [F] CUDA tensor, without gate and overlap: (start_frames i32 [max_segments], end_frames,
+    count i32 [1], threshold f32 [1])."""
+    if not torch.is_tensor(db) or not db.is_cuda or db.dim() != 1 or db.dtype != torch.float32:
+        raise RuntimeError("segments_from_db: db must be a 1-D float32 CUDA tensor (there is no CPU path)")
+    start, end, _, count, thr = _segments_from_db(db, params, float("inf"), max_segments, False, mono=True)
+    return start, end, count, thr
 
 
 def segment_channels(waves: torch.Tensor, crosstalk_db: float = DEFAULT_CROSSTALK_DB, vad=None, **params) -> ChannelSegments:
     """Cut every channel of a [C, samples] 16 kHz CUDA tensor at its own pauses (one speaker per channel): three launches (energies,
     one workgroup per channel, overlap), then the counts and the thresholds are read back together.  A frame of a channel is not speech
-    when another channel is louder there by more than ``crosstalk_db`` (inf: no gate).  Parameters as ``segment``."""
+    when another channel is louder there by more than ``crosstalk_db`` (inf: no gate).  Parameters: the fields of VadParams, as
+    keywords or as ``vad`` (a VadParams or a dict)."""
     p = resolve_params(vad, **params)
     crosstalk_db = _check_crosstalk(crosstalk_db)
-    waves = _waves(waves, "segment_channels")
-    ch, n = int(waves.shape[0]), int(waves.shape[1])
-    db = frame_energy_db_channels(waves)
-    start, end, over, count, thr = segments_channels_from_db(db, p, crosstalk_db)
-    host = torch.cat([count.to(torch.float64), thr.to(torch.float64)]).cpu().tolist()  # the one read-back: both are exact in float64
-    counts, thrs = [int(v) for v in host[:ch]], host[ch:]
-    for c, k in enumerate(counts):
-        if k < 0:
-            raise _lib.LocoError(f"segment_channels: {-k} segments of channel {c} exceed the {start.shape[1]} the rules allow for {db.shape[1]} frames")
-    dev = waves.device
-    chan = torch.cat([torch.full((k,), c, dtype=torch.int32, device=dev) for c, k in enumerate(counts)])
-    flat = lambda t: torch.cat([t[c, :k] for c, k in enumerate(counts)])  # noqa: E731
-    start, end, over = flat(start), flat(end), flat(over)
-    order = torch.argsort(start.to(torch.int64) * MAX_CHANNELS + chan.to(torch.int64))  # the keys are distinct: (start, channel) order
-    chan, start, end, over = chan[order], start[order], end[order], over[order]
-    return ChannelSegments(channel=chan, start_frames=start, end_frames=end, start_samples=start.to(torch.int64) * HOP,
-                           end_samples=torch.clamp(end.to(torch.int64) * HOP + (WINDOW - HOP), max=n), overlap_frames=over,
-                           threshold_db=thrs, counts=counts, count=sum(counts), samples=n, channels=ch)
+    return _segment(_waves(waves, "segment_channels"), p, crosstalk_db, "segment_channels")
+
+
+def segment(wave: torch.Tensor, vad=None, **params) -> Segments:
+    """Cut a 1-D 16 kHz CUDA waveform at pauses, the one-channel case: two launches (energy, segmentation), then the count and the
+    threshold are read back together.  Parameters as ``segment_channels``."""
+    p = resolve_params(vad, **params)
+    s = _segment(_waves(wave, "segment", mono=True), p, float("inf"), "segment", mono=True)
+    return Segments(start_frames=s.start_frames, end_frames=s.end_frames, start_samples=s.start_samples, end_samples=s.end_samples,
+                    threshold_db=s.threshold_db[0], count=s.count, samples=s.samples)
 
 
 @dataclass

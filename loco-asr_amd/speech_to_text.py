@@ -307,15 +307,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         token (both: (ids, logits, scores))."""
         dec.check_generate_kwargs(kwargs)
         self._require_decoder("generate_many()")
-        batches = list(batches)
-        sizes = [int(b["input_values"].shape[0]) for b in batches]
-        total = sum(sizes)
-        caps = dec.resolve_caps(total, max_length, max_new_tokens)
-        if int(pack) < 1:
-            raise ValueError("pack must be >= 1")
-        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
-        if not 1 <= int(slots) <= most:
-            raise ValueError(f"generate_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        batches, total, caps = self._corpus_args("generate_many", batches, max_length, max_new_tokens, slots, pack)
         extras = int(bool(return_logits)) + int(bool(return_scores))
         if total == 0:
             return ([],) * (1 + extras) if extras else []
@@ -326,6 +318,19 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         if return_scores:
             out.append([results[k][2] for k in range(total)])
         return tuple(out) if extras else out[0]
+
+    def _corpus_args(self, what, batches, max_length, max_new_tokens, slots, pack):
+        """What ``generate_many`` and ``sample_many`` (``what``: the name their messages carry) ask of their arguments before anything is
+        built: (the batches as a list, their utterances in all, every utterance's cap of tokens)."""
+        batches = list(batches)
+        total = sum(int(b["input_values"].shape[0]) for b in batches)
+        caps = dec.resolve_caps(total, max_length, max_new_tokens)
+        if int(pack) < 1:
+            raise ValueError("pack must be >= 1")
+        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
+        if not 1 <= int(slots) <= most:
+            raise ValueError(f"{what}: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        return batches, total, caps
 
     def _decode_corpus(self, batches, caps, slots, pack, return_logits, return_scores, copies=1, sample=None, greedy_first=False, first_utterance=0):
         """The walk ``generate_many`` and ``sample_many`` share over checked arguments: encode ``pack`` batches at a time, decode in one
@@ -384,15 +389,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         (hyps, logits, scores)."""
         self._require_decoder("sample_many()")
         n, config = dec.check_sample_args(num_return_sequences, temperature, top_k, top_p, seed)
-        batches = list(batches)
-        sizes = [int(b["input_values"].shape[0]) for b in batches]
-        total = sum(sizes)
-        caps = dec.resolve_caps(total, max_length, max_new_tokens)
-        if int(pack) < 1:
-            raise ValueError("pack must be >= 1")
-        most = int(self.speecht5.encoder._lib.loco_decoder_max_batch())
-        if not 1 <= int(slots) <= most:
-            raise ValueError(f"sample_many: slots = {slots} is outside 1 .. {most}, the decode step's limit of rows")
+        batches, total, caps = self._corpus_args("sample_many", batches, max_length, max_new_tokens, slots, pack)
         if not 0 <= int(first_utterance) <= 2 ** 32 - 1 - total:
             raise ValueError(f"sample_many: first_utterance = {first_utterance} leaves no room for {total} utterances below 2^32")
         results = self._decode_corpus(batches, caps, slots, pack, return_logits, return_scores, copies=n, sample=config,
@@ -459,30 +456,11 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         Returns a segment.LongTranscript whose ``segments[k]`` carries ``start_s`` / ``end_s``, ``ids``, with ``return_scores``
         ``token_logprobs`` (device), ``logprob`` and ``avg_logprob``, and with ``timestamps`` ``token_times`` [len - 1, 2] in
         recording time (``align_many``'s times plus ``start_s``).  ``do_normalize``: each segment is normalised on its own."""
-        self._require_decoder("transcribe_long()")
-        params = seg.resolve_params(vad)
-        cap = dec.resolve_max_length(dec.MAX_TEXT_POSITIONS if max_length is None else max_length)
-        segs = seg.segment(waveform, params)
-        duration = segs.samples / seg.SAMPLE_RATE
-        if segs.count == 0:
-            return seg.LongTranscript(segments=[], duration_s=duration, threshold_db=segs.threshold_db)
-        from .feature_extractor import SpeechT5FeatureExtractorMI355X
-        fe = SpeechT5FeatureExtractorMI355X(do_normalize=do_normalize)
-        bounds = list(zip(segs.start_samples.cpu().tolist(), segs.end_samples.cpu().tolist()))  # one read-back
-        wave = waveform.to(torch.float32)
-        batches = [fe(audio=[wave[s:e]], sampling_rate=seg.SAMPLE_RATE) for s, e in bounds]
-        rows = self.generate_many(batches, max_length=cap, slots=slots, pack=pack, return_scores=return_scores)
-        ids, scores = rows if return_scores else (rows, None)
-        out = [seg.LongSegment(start_s=s / seg.SAMPLE_RATE, end_s=e / seg.SAMPLE_RATE, ids=r)
-               for (s, e), r in zip(bounds, ids)]
-        if return_scores:
-            sums = [float(v) for v in torch.stack([t.double().sum() for t in scores]).cpu().tolist()]  # one read-back
-            for o, t, v in zip(out, scores, sums):
-                o.token_logprobs, o.logprob, o.avg_logprob = t, v, v / max(int(t.shape[0]), 1)
-        if timestamps:
-            for o, al in zip(out, self.align_many(batches, [r[1:] for r in ids], pack=pack)):
-                o.token_times = torch.stack([al.start_times, al.end_times], dim=1).cpu() + o.start_s
-        return seg.LongTranscript(segments=out, duration_s=duration, threshold_db=segs.threshold_db)
+        def cut(params):
+            segs = seg.segment(waveform, params)
+            wave = waveform.to(torch.float32)
+            return segs, [segs.start_samples, segs.end_samples], lambda s, e: wave[s:e]
+        return self._transcribe_cut("transcribe_long()", cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize)
 
     @torch.no_grad()
     def transcribe_channels(self, waveforms: torch.Tensor, crosstalk_db: float = seg.DEFAULT_CROSSTALK_DB, vad=None, max_length: Optional[int] = None,
@@ -495,23 +473,36 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
 
         Returns a segment.LongTranscript in (start, channel) order; its segments also carry ``channel`` and ``overlap_s``, and its
         ``threshold_db`` is a list with one threshold per channel."""
-        self._require_decoder("transcribe_channels()")
+        def cut(params):
+            segs = seg.segment_channels(waveforms, crosstalk_db, params)
+            waves = waveforms.to(torch.float32)
+            return (segs, [segs.start_samples, segs.end_samples, segs.channel.to(torch.int64), segs.overlap_frames.to(torch.int64)],
+                    lambda s, e, c, _: waves[c, s:e])
+        return self._transcribe_cut("transcribe_channels()", cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize)
+
+    def _transcribe_cut(self, what, cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize):
+        """``transcribe_long`` and ``transcribe_channels`` (``what``) but for the cut itself.  ``cut(params)`` cuts the recording and
+        returns (the Segments / ChannelSegments, the per-segment table as device columns -- start samples, end samples and, per channel,
+        channel and overlap frames --, a callable that takes a row of that table to the segment's samples).  Everything else is here: the
+        one-clip batches, ``generate_many``, the score sums, ``align_many``, the LongTranscript."""
+        self._require_decoder(what)
         params = seg.resolve_params(vad)
         cap = dec.resolve_max_length(dec.MAX_TEXT_POSITIONS if max_length is None else max_length)
-        segs = seg.segment_channels(waveforms, crosstalk_db, params)
+        segs, columns, clip = cut(params)
         duration = segs.samples / seg.SAMPLE_RATE
         if segs.count == 0:
             return seg.LongTranscript(segments=[], duration_s=duration, threshold_db=segs.threshold_db)
         from .feature_extractor import SpeechT5FeatureExtractorMI355X
         fe = SpeechT5FeatureExtractorMI355X(do_normalize=do_normalize)
-        table = torch.stack([segs.channel.to(torch.int64), segs.start_samples, segs.end_samples, segs.overlap_frames.to(torch.int64)]).cpu().tolist()
-        bounds = list(zip(*table))  # one read-back: (channel, start, end, overlap frames) per segment
-        waves = waveforms.to(torch.float32)
-        batches = [fe(audio=[waves[c, s:e]], sampling_rate=seg.SAMPLE_RATE) for c, s, e, _ in bounds]
+        table = list(zip(*torch.stack(columns).cpu().tolist()))  # one read-back: a row per segment
+        batches = [fe(audio=[clip(*row)], sampling_rate=seg.SAMPLE_RATE) for row in table]
         rows = self.generate_many(batches, max_length=cap, slots=slots, pack=pack, return_scores=return_scores)
         ids, scores = rows if return_scores else (rows, None)
-        out = [seg.LongSegment(start_s=s / seg.SAMPLE_RATE, end_s=e / seg.SAMPLE_RATE, ids=r, channel=c, overlap_s=o / seg.FRAME_RATE)
-               for (c, s, e, o), r in zip(bounds, ids)]
+        out = []
+        for (s, e, *rest), r in zip(table, ids):
+            out.append(seg.LongSegment(start_s=s / seg.SAMPLE_RATE, end_s=e / seg.SAMPLE_RATE, ids=r))
+            if rest:
+                out[-1].channel, out[-1].overlap_s = rest[0], rest[1] / seg.FRAME_RATE
         if return_scores:
             sums = [float(v) for v in torch.stack([t.double().sum() for t in scores]).cpu().tolist()]  # one read-back
             for o, t, v in zip(out, scores, sums):

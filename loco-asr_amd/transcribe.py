@@ -151,52 +151,9 @@ def kaldi_text_lines(rec_id, segments):
     return lines
 
 
-def main_long_split(args, vad, slots):
-    """``--long --channels split``: every channel of every FILE is cut and decoded on its own (``transcribe_channels``)."""
-    from .extract import load_audio_channels_16k
-    tok = load_tokenizer(args.tokenizer)
-    if args.kaldi_text and tok is None:
-        raise SystemExit("--kaldi-text needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): its lines are text")
-    model = build_model(args)
-    device = torch.device("cuda", torch.cuda.current_device())
-    fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    kh = open(args.kaldi_text, "w", encoding="utf-8") if args.kaldi_text else None
-    try:
-        for path in args.files:
-            x = load_audio_channels_16k(path, device=device)
-            x = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))
-            res = model.transcribe_channels(x.to(device), crosstalk_db=args.crosstalk_db, vad=vad, max_length=args.max_length, slots=slots,
-                                            pack=args.pack, return_scores=args.scores, timestamps=args.timestamps, do_normalize=args.do_normalize)
-            rec = {"id": os.path.splitext(os.path.basename(path))[0], "duration_s": round(res.duration_s, 4),
-                   "threshold_db": [t if math.isfinite(t) else None for t in res.threshold_db], "segments": []}  # JSON has no infinities
-            kaldi = []
-            for sg in res.segments:
-                row = sg.ids.tolist()
-                one = {"channel": channel_name(sg.channel), "start_s": round(sg.start_s, 4), "end_s": round(sg.end_s, 4),
-                       "overlap_s": round(sg.overlap_s, 4), "token_ids": row}
-                if tok is not None:
-                    one["text"] = tok.decode(strip_special(row))
-                    kaldi.append((sg.channel, round(sg.start_s * 16000), round(sg.end_s * 16000), one["text"]))
-                if args.scores:
-                    one["logprob"], one["avg_logprob"] = sg.logprob, sg.avg_logprob
-                if args.timestamps:
-                    one["token_times"] = [[round(a, 4), round(b, 4)] for a, b in sg.token_times.tolist()]
-                rec["segments"].append(one)
-            if tok is not None:
-                rec["text"] = " ".join(one["text"] for one in rec["segments"])
-            fh.write(json.dumps(rec) + "\n")
-            if kh is not None:
-                kh.writelines(line + "\n" for line in kaldi_text_lines(kaldi_rec_id(path), kaldi))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
-        if kh is not None:
-            kh.close()
-    return 0
-
-
 def main_long(args, ap):
-    """``--long``: every FILE is one recording.  Flag combinations and segmentation parameters are refused before a model is built."""
+    """``--long``: every FILE is one recording; with ``--channels split`` every channel of it is cut and decoded on its own
+    (``transcribe_channels``).  Flag combinations and segmentation parameters are refused before a model is built."""
     from .segment import resolve_params
     for flag, given in (("--split", bool(args.split)), ("--synthetic", args.synthetic > 0), ("--nbest", args.nbest != 0),
                         ("--batch-size", args.batch_size != ap.get_default("batch_size"))):
@@ -213,7 +170,8 @@ def main_long(args, ap):
         vad = resolve_params(None, trim=not args.no_trim, **given)
     except ValueError as e:
         raise SystemExit(f"--max-segment-s / --min-silence-s / --vad-margin-db: {e}")
-    if args.channels != "split":
+    split = args.channels == "split"
+    if not split:
         for flag, v in (("--crosstalk-db", args.crosstalk_db), ("--kaldi-text", args.kaldi_text)):
             if v is not None:
                 raise SystemExit(f"{flag} needs --channels split: only there does a segment have a channel")
@@ -221,25 +179,36 @@ def main_long(args, ap):
         args.crosstalk_db = 15.0 if args.crosstalk_db is None else args.crosstalk_db
         if not args.crosstalk_db >= 0.0:
             raise SystemExit(f"--crosstalk-db: crosstalk_db = {args.crosstalk_db:g} is NaN or negative (inf switches the gate off)")
-        return main_long_split(args, vad, slots)
-    model = build_model(args)
     tok = load_tokenizer(args.tokenizer)
+    if args.kaldi_text and tok is None:
+        raise SystemExit("--kaldi-text needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): its lines are text")
+    model = build_model(args)
     device = torch.device("cuda", torch.cuda.current_device())
-    from .extract import load_audio_16k
+    from .extract import load_audio_16k, load_audio_channels_16k
+    common = dict(vad=vad, max_length=args.max_length, slots=slots, pack=args.pack, return_scores=args.scores, timestamps=args.timestamps,
+                  do_normalize=args.do_normalize)
+    finite = lambda t: t if math.isfinite(t) else None  # noqa: E731 -- JSON has no infinities
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
+    kh = open(args.kaldi_text, "w", encoding="utf-8") if args.kaldi_text else None
     try:
         for path in args.files:
-            x = load_audio_16k(path, device=device)
-            x = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))
-            res = model.transcribe_long(x.to(device), vad=vad, max_length=args.max_length, slots=slots, pack=args.pack, return_scores=args.scores,
-                                        timestamps=args.timestamps, do_normalize=args.do_normalize)
+            x = (load_audio_channels_16k if split else load_audio_16k)(path, device=device)
+            x = (x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))).to(device)
+            res = model.transcribe_channels(x, crosstalk_db=args.crosstalk_db, **common) if split else model.transcribe_long(x, **common)
             rec = {"id": os.path.splitext(os.path.basename(path))[0], "duration_s": round(res.duration_s, 4),
-                   "threshold_db": res.threshold_db if math.isfinite(res.threshold_db) else None, "segments": []}  # JSON has no infinities
+                   "threshold_db": [finite(t) for t in res.threshold_db] if split else finite(res.threshold_db), "segments": []}
+            kaldi = []
             for sg in res.segments:
                 row = sg.ids.tolist()
-                one = {"start_s": round(sg.start_s, 4), "end_s": round(sg.end_s, 4), "token_ids": row}
+                one = {"channel": channel_name(sg.channel)} if split else {}
+                one.update(start_s=round(sg.start_s, 4), end_s=round(sg.end_s, 4))
+                if split:
+                    one["overlap_s"] = round(sg.overlap_s, 4)
+                one["token_ids"] = row
                 if tok is not None:
                     one["text"] = tok.decode(strip_special(row))
+                    if kh is not None:
+                        kaldi.append((sg.channel, round(sg.start_s * 16000), round(sg.end_s * 16000), one["text"]))
                 if args.scores:
                     one["logprob"], one["avg_logprob"] = sg.logprob, sg.avg_logprob
                 if args.timestamps:
@@ -248,9 +217,13 @@ def main_long(args, ap):
             if tok is not None:
                 rec["text"] = " ".join(one["text"] for one in rec["segments"])
             fh.write(json.dumps(rec) + "\n")
+            if kh is not None:
+                kh.writelines(line + "\n" for line in kaldi_text_lines(kaldi_rec_id(path), kaldi))
     finally:
         if fh is not sys.stdout:
             fh.close()
+        if kh is not None:
+            kh.close()
     return 0
 
 

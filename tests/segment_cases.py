@@ -69,3 +69,17 @@ def recording():
     for a, b in BURSTS:
         x[a:b] = 0.1 * np.sin(2 * np.pi * 440.0 * t) + 0.01 * rng.standard_normal(32000)
     return x.astype(np.float32)
+
+
+# ---- the mono entry's workspace and output contract (tests/test_gpu_segment.py; the names are checked on the host by
+# tests/test_segment_ref.py).  F = 1: the smallest recording; 601: the workspace size is no multiple of 16 and there are fewer frames
+# than threads; 1025: the first size with two frames per thread and threads past the end; 6001: the walk over cuts takes many steps ----
+CONTRACT_F = (1, 601, 1025, 6001)
+CONTRACT_PARAMS = dict(max_segment_s=4.0, min_segment_s=0.4)  # 200 frames at most, so that 601 frames are cut at least twice
+
+
+def contract_inputs(F):
+    rng = np.random.default_rng(F)
+    return {"silent": (-90.0 + rng.standard_normal(F)).astype(np.float32),  # the path that zeroes the mask
+            "all_speech": (-20.0 + rng.standard_normal(F)).astype(np.float32),
+            "telegraph": R.telegraph(F, F)}

@@ -21,7 +21,7 @@ import torch
 
 import decoder_pool_cases as pc
 import segment_ref as R
-from segment_cases import BURSTS, EDGE, LONG, SMALL, recording
+from segment_cases import BURSTS, CONTRACT_F, CONTRACT_PARAMS, EDGE, LONG, SMALL, contract_inputs, recording
 
 pytestmark = pytest.mark.gpu
 
@@ -126,6 +126,67 @@ def test_overflow_is_reported_not_written(gu, seg):
     assert count.cpu().tolist() == [-len(want), -779]
     assert start.cpu().tolist() == [want[0][0], want[1][0]] + [-777] * 6
     assert end.cpu().tolist() == [want[0][1], want[1][1]] + [-778] * 6
+
+
+GUARD = 0xA5
+
+
+def guarded(n, dtype, words):
+    """A device buffer of n elements followed by ``words`` guard elements, every byte GUARD; (the buffer, the bytes from the guard on)."""
+    size = torch.empty(0, dtype=dtype).element_size()
+    raw = torch.full(((n + words) * size,), GUARD, dtype=torch.uint8, device="cuda")
+    return raw, raw[n * size:]
+
+
+@pytest.mark.parametrize("F", CONTRACT_F)
+def test_mono_entry_workspace_and_output_contract(gu, seg, F):
+    """loco_op_vad_segments given exactly loco_vad_workspace_bytes(F) bytes: the bits of the restatement, and not a byte written behind
+    the workspace (256 guard bytes), seg_start / seg_end [max_segments] (8 guard words each), count and threshold_db (one each)."""
+    lib, C = gu.lib(), importlib.import_module("ctypes")
+    p = seg.resolve_params(None, **CONTRACT_PARAMS)
+    maxf, minf = p.frames()[:2]
+    max_segments = F // min(minf + 1, maxf // 2) + 1
+    ws_bytes = int(lib.loco_vad_workspace_bytes(F))
+    assert ws_bytes >= 9 * F + 4 and (F != 601 or ws_bytes % 16 != 0)
+    for name, db in contract_inputs(F).items():
+        want, want_thr = R.segments(db, **CONTRACT_PARAMS)
+        assert len(want) <= max_segments
+        if F >= 601:
+            assert {"silent": len(want) == 0 and want_thr == np.inf, "all_speech": want_thr == -np.inf, "telegraph": len(want) >= 2}[name]
+        d = gu.dev(db)
+        start, start_g = guarded(max_segments, torch.int32, 8)
+        end, end_g = guarded(max_segments, torch.int32, 8)
+        count, count_g = guarded(1, torch.int32, 1)
+        thr, thr_g = guarded(1, torch.float32, 1)
+        ws, ws_g = guarded(ws_bytes, torch.uint8, 256)
+        gu.check(lib.loco_op_vad_segments(gu.ptr(d), F, C.byref(p.to_c()), gu.ptr(start), gu.ptr(end), max_segments, gu.ptr(count), gu.ptr(thr),
+                                          gu.ptr(ws), ws_bytes, gu.stream()), "loco_op_vad_segments")
+        k = len(want)
+        assert count.view(torch.int32)[:1].cpu().tolist() == [k], (name, F)
+        assert thr.view(torch.float32)[:1].cpu().numpy().view(np.uint32)[0] == np.float32(want_thr).view(np.uint32), (name, F)
+        got = list(zip(start.view(torch.int32)[:k].cpu().tolist(), end.view(torch.int32)[:k].cpu().tolist()))
+        assert got == want, (name, F, got[:8], want[:8])
+        for what, g in (("seg_start", start_g), ("seg_end", end_g), ("count", count_g), ("threshold_db", thr_g), ("workspace", ws_g)):
+            assert bool((g == GUARD).all()), (name, F, what)
+
+
+@pytest.mark.parametrize("n", [400, 719, 48123])
+def test_mono_energy_entry_is_row_0_of_the_channel_entry(gu, n):
+    """loco_op_frame_energy_db writes db[F] and nothing behind it, the bits of loco_op_frame_energy_db_channels with C = 1 on the same
+    samples at a row stride larger than n."""
+    lib = gu.lib()
+    F = (n - 80) // 320
+    rng = np.random.default_rng(n)
+    x = gu.dev((0.05 * rng.standard_normal(n)).astype(np.float32))
+    wide = torch.full((1, n + 37), float("nan"), device="cuda")
+    wide[0, :n] = x
+    db, db_g = guarded(F, torch.float32, 64)
+    gu.check(lib.loco_op_frame_energy_db(gu.ptr(x), n, gu.ptr(db), gu.stream()), "loco_op_frame_energy_db")
+    row, row_g = guarded(F, torch.float32, 64)
+    gu.check(lib.loco_op_frame_energy_db_channels(gu.ptr(wide), 1, n, n + 37, gu.ptr(row), gu.stream()), "loco_op_frame_energy_db_channels")
+    size = 4 * F
+    assert torch.equal(db[:size], row[:size]) and bool(torch.isfinite(db[:size].view(torch.float32)).all())
+    assert bool((db_g == GUARD).all()) and bool((row_g == GUARD).all())
 
 
 # ---- 3. end to end ---------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import segment_ref as R
-from segment_cases import EDGE, LONG, recording
+from segment_cases import CONTRACT_F, CONTRACT_PARAMS, EDGE, LONG, contract_inputs, recording
 
 # (seed, F, parameters): short maxima so that every signal is cut many times; one case without any usable silence
 CASES = [(seed, 1500 + 217 * seed, dict(max_segment_s=2.0 + 0.5 * (seed % 5), min_segment_s=0.2 + 0.1 * (seed % 3),
@@ -110,3 +110,15 @@ def test_recording_by_the_rules_on_the_host():
     assert thr == np.float32(-60.0) and starts == [0, 149, 299, 449]
     assert segs == [(14, 135), (164, 285), (314, 435), (464, 585)]
     assert [(a, b) for a, b, v in R.runs_of(mask) if v == 0][1:4] == [(125, 174), (275, 324), (425, 474)]
+
+
+@pytest.mark.parametrize("F", CONTRACT_F)
+def test_contract_inputs_are_what_their_names_say(F):
+    """The inputs of the mono entry's workspace contract test on the device: silent, without usable silence, cut more than once."""
+    dbs = contract_inputs(F)
+    segs, thr = R.segments(dbs["silent"], **CONTRACT_PARAMS)
+    assert segs == [] and thr == np.inf
+    segs, thr = R.segments(dbs["all_speech"], **CONTRACT_PARAMS)
+    assert thr == -np.inf and (F < 601 or len(segs) >= 2)
+    segs, thr = R.segments(dbs["telegraph"], **CONTRACT_PARAMS)
+    assert F < 601 or (len(segs) >= 2 and np.isfinite(thr))
