@@ -468,6 +468,12 @@ int loco_op_pos_conv_f16x3(const float* h, const void* whi, const void* wlo, con
  * [rows, dim], and nonfinite_slot (device, 8 floats, or NULL) set to +inf when a row's statistics are not finite. */
 int loco_op_layernorm_f16x3(const float* x, const float* gamma, const float* beta, float* y, void* yhi, void* ylo,
                             float* nonfinite_slot, int64_t rows, int32_t dim, float eps, void* stream);
+/* The LayerNorm behind the out-projection and the second FFN GEMM of the f16x3 forward: loco_op_layernorm_f16x3 of
+ * x + (rhi + rlo), a residual given as fp16 hi/lo planes [rows, dim] (8-byte aligned, both required).  The sum is formed in fp32,
+ * hi + lo first, before the row's mean: the bits of loco_op_layernorm_f16x3 on that sum. */
+int loco_op_layernorm_f16x3_residual(const float* x, const void* rhi, const void* rlo, const float* gamma, const float* beta,
+                                     float* y, void* yhi, void* ylo, float* nonfinite_slot, int64_t rows, int32_t dim,
+                                     float eps, void* stream);
 
 /* split-precision attention core: q, k and v as fp16 hi/lo planes [B*T,768] (q pre-scaled by 1/8) -- the layout the fused q|k|v
  * projection writes; the kernel transposes its V tiles with the LDS read; qp/frames/ctx as loco_op_attention, and the same contract

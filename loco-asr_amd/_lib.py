@@ -120,7 +120,8 @@ SIGNATURES = {
     "loco_op_gemm_f16x3_desc": (C.c_int, [C.POINTER(LocoGemmF16Desc), _vp]),
     "loco_op_pos_conv_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i32, _vp, _vp, _vp, _sz, _vp, _i32, _i32, _vp]),
     "loco_op_layernorm_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _vp]),
-    "loco_op_permute_conv_k": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "loco_op_layernorm_f16x3_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _vp]),
+    "loco_op_permute_conv_k":(C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "loco_op_conv_gemm_f16x3": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _vp]),
     "loco_op_attention_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "loco_op_attention_f16x3_pe": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i32, _i32, _vp]),

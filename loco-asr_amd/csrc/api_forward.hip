@@ -458,29 +458,29 @@ int encoder_f16x3(loco_encoder* e, Call& c, const Plan& p, float* out, float* co
         // past-clipped.  The probabilities kernel reads only formed entries: rows i >= frames + 158 read none (include/loco_asr.h)
         LOCO_TRY(run_attention_probs(e, s, nullptr, qshi, qslo, kshi, kslo, bf.qp, bf.frames_or_null, l, B, T));
         dbg_planes(e, s, "attention context planes %s", l, chi, clo, MH, kHidden);
-        // out_proj + residual, LayerNorm
-        a = split_args(M, kHidden, kHidden, kEpiResidual);
-        a.Ahi = chi; a.Alo = clo; a.bias = lw.out_proj.b;
-        a.Rhi = x0hi; a.Rlo = x0lo; a.ldr = kHidden; a.C = tmp;
+        // out_proj, then residual + LayerNorm: the GEMM stores acc + bias and the LayerNorm behind it adds x0 = hi + lo while it
+        // streams the row -- the two additions of the residual epilogue in the same order (the same bits), without twelve waves
+        // that hold the CU's LDS waiting for the planes in front of every store
+        a = split_args(M, kHidden, kHidden, kEpiNone);
+        a.Ahi = chi; a.Alo = clo; a.bias = lw.out_proj.b; a.C = tmp;
         LOCO_TRY(run_gemm_split(e, c, s, a, lw.so));
-        dbg_check(e, s, "out_proj + residual (fp32)", l, tmp, MH, false, kHidden);
-        LOCO_TRY(run_ln(e, s, tmp, lw.layer_norm.w, lw.layer_norm.b, nullptr, M, kHidden, x1hi, x1lo));
+        dbg_check(e, s, "out_proj (fp32, before the residual)", l, tmp, MH, false, kHidden);
+        LOCO_TRY(run_ln(e, s, tmp, lw.layer_norm.w, lw.layer_norm.b, nullptr, M, kHidden, x1hi, x1lo, nullptr, x0hi, x0lo));
         dbg_planes(e, s, "layer_norm planes %s", l, x1hi, x1lo, MH, kHidden);
-        // FFN + residual + final LayerNorm
+        // FFN, then residual + final LayerNorm (the residual x1 joins in the LayerNorm, as above)
         a = split_args(M, F, kHidden, kEpiGelu);
         a.Ahi = x1hi; a.Alo = x1lo; a.bias = lw.ffn_in.b;
         a.Chi = fhi; a.Clo = flo; a.range_slot = c.slot("feed_forward intermediate (GELU)", l);
         LOCO_TRY(run_gemm_split(e, c, s, a, lw.s1));
         dbg_planes(e, s, "feed_forward intermediate planes %s", l, fhi, flo, (size_t)M * F, F);
-        a = split_args(M, kHidden, F, kEpiResidual);
-        a.Ahi = fhi; a.Alo = flo; a.bias = lw.ffn_out.b;
-        a.Rhi = x1hi; a.Rlo = x1lo; a.ldr = kHidden; a.C = tmp;
+        a = split_args(M, kHidden, F, kEpiNone);
+        a.Ahi = fhi; a.Alo = flo; a.bias = lw.ffn_out.b; a.C = tmp;
         LOCO_TRY(run_gemm_split(e, c, s, a, lw.s2));
-        dbg_check(e, s, "feed_forward output + residual (fp32)", l, tmp, MH, false, kHidden);
+        dbg_check(e, s, "feed_forward output (fp32, before the residual)", l, tmp, MH, false, kHidden);
         const bool last = l == nl - 1;
         LOCO_TRY(run_ln(e, s, tmp, lw.final_layer_norm.w, lw.final_layer_norm.b, last ? out : (hidden_states ? x0 : nullptr), M, kHidden,
                         last ? nullptr : x0hi, last ? nullptr : x0lo,
-                        last && c.range_dev ? c.range_dev + (size_t)kRangeShards * kFiniteStage : nullptr));
+                        last && c.range_dev ? c.range_dev + (size_t)kRangeShards * kFiniteStage : nullptr, x1hi, x1lo));
     }
     if (nl == 0) LOCO_TRY(run_copy(e, s, out, x0, MH));
     if (hidden_states && hidden_states[nl]) LOCO_TRY(run_copy(e, s, hidden_states[nl], out, MH));

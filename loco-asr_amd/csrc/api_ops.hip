@@ -216,6 +216,16 @@ int loco_op_layernorm_f16x3(const float* x, const float* gamma, const float* bet
     return LOCO_OK;
 }
 
+int loco_op_layernorm_f16x3_residual(const float* x, const void* rhi, const void* rlo, const float* gamma, const float* beta, float* y,
+                                     void* yhi, void* ylo, float* nonfinite_slot, int64_t rows, int32_t dim, float eps, void* stream) {
+    const char* fn = "loco_op_layernorm_f16x3_residual";
+    if (!x || !rhi || !rlo || !gamma || !beta || !yhi || !ylo) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (dim != 512 && dim != 768) return fail(LOCO_E_INVALID, "%s: dim %d not in {512,768}", fn, dim);
+    if ((reinterpret_cast<uintptr_t>(rhi) | reinterpret_cast<uintptr_t>(rlo)) & 7) return fail(LOCO_E_INVALID, "%s: rhi / rlo must be 8-byte aligned", fn);
+    HIP_TRY(launch_layernorm(x, gamma, beta, y, rows, dim, eps, (hipStream_t)stream, yhi, ylo, nonfinite_slot, rhi, rlo));
+    return LOCO_OK;
+}
+
 int loco_op_attention_f16x3(const void* qhi, const void* qlo, const void* khi, const void* klo, const void* vhi, const void* vlo,
                             const float* qp, const int32_t* frames, float* ctx, int32_t B, int32_t T, void* stream) {
     if (!qhi || !qlo || !khi || !klo || !vhi || !vlo || !qp || !ctx) return fail(LOCO_E_INVALID, "loco_op_attention_f16x3: null argument");

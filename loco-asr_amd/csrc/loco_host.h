@@ -230,9 +230,10 @@ inline int run_gemm(loco_encoder* e, hipStream_t s, const float* A, long lda, co
 }
 
 inline int run_ln(loco_encoder* e, hipStream_t s, const float* x, const float* g, const float* b, float* y, long rows, int dim,
-                  _Float16* yhi = nullptr, _Float16* ylo = nullptr, float* nonfinite_slot = nullptr) {
-    Bracket br(e, s, K_LN, 8.0 * rows * dim, (y && yhi ? 12.0 : 8.0) * rows * dim);
-    HIP_TRY(launch_layernorm(x, g, b, y, rows, dim, e->cfg.ln_eps, s, yhi, ylo, nonfinite_slot));
+                  _Float16* yhi = nullptr, _Float16* ylo = nullptr, float* nonfinite_slot = nullptr, const _Float16* rhi = nullptr,
+                  const _Float16* rlo = nullptr) {
+    Bracket br(e, s, K_LN, (rhi ? 10.0 : 8.0) * rows * dim, ((y && yhi ? 12.0 : 8.0) + (rhi ? 4.0 : 0.0)) * rows * dim);
+    HIP_TRY(launch_layernorm(x, g, b, y, rows, dim, e->cfg.ln_eps, s, yhi, ylo, nonfinite_slot, rhi, rlo));
     return LOCO_OK;
 }
 

@@ -60,7 +60,8 @@ struct GemmSplitArgs {
     // [M,768] (q), [768,1536) -> the k planes, [1536,2304) -> the v planes, each pair qkv_stride halves behind the previous one (attention
     // transposes V with its LDS read)
     // kEpiResidual: the residual may also be given as fp16 hi/lo planes (same element offsets and ldr as R); it is then hi + lo,
-    // exact in fp32.  The encoder's residual stream lives only in that form between layers (LayerNorm writes no fp32 copy).
+    // exact in fp32.  The encoder's residual stream lives only in that form between layers (LayerNorm writes no fp32 copy); the
+    // encoder itself hands these planes to the LayerNorm behind the GEMM (launch_layernorm's rhi / rlo) and launches kEpiNone.
     const _Float16* Rhi = nullptr;
     const _Float16* Rlo = nullptr;
     // split-K for small problems (launch_gemm_split decides): fp32 partial sums [ks][M][N], >= kSplitKBytes when set
@@ -290,7 +291,8 @@ __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t x) {
 
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, long rows, int dim, float eps,
-                            hipStream_t s, void* yhi = nullptr, void* ylo = nullptr, float* nonfinite_slot = nullptr);
+                            hipStream_t s, void* yhi = nullptr, void* ylo = nullptr, float* nonfinite_slot = nullptr,
+                            const void* rhi = nullptr, const void* rlo = nullptr);  // rhi / rlo: normalise x + (rhi + rlo), fp16 planes [rows, dim]
 
 constexpr int kConv0Parts = 64;    // partial-moment blocks per clip
 constexpr int kConv0Moments = 65;  // 10 first + 55 second moments

@@ -10,11 +10,15 @@ typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 
 // SPLIT: additionally (or instead, when y == nullptr) write the result as fp16 hi/lo planes -- the A operand of the
 // split-precision GEMM that consumes it (gemm_f16x3.hip).
-template <int NV4, bool SPLIT>
+// RESID: the row normalised is x + (rhi + rlo), a residual given as fp16 hi/lo planes [rows, D] -- the sum the residual epilogue of
+// the GEMM in front (gemm_f16x3.hip, kEpiResidual) would have stored: the same two fp32 additions in the same order, so the
+// same bits, taken here by a streaming kernel that holds nothing else while it waits for them.
+template <int NV4, bool SPLIT, bool RESID>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, float* __restrict__ y,
                                                         _Float16* __restrict__ yhi, _Float16* __restrict__ ylo, long rows,
-                                                        float eps, float* __restrict__ nonfinite_slot) {
+                                                        float eps, float* __restrict__ nonfinite_slot,
+                                                        const _Float16* __restrict__ rhi, const _Float16* __restrict__ rlo) {
     constexpr int D = NV4 * 256;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -23,8 +27,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     float4 v[NV4];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV4; ++i) {
+    for (int i = 0; i < NV4; ++i) {  // unrolled: the compiler issues every load of the row before the first use
         v[i] = xr[lane + 64 * i];
+        if (RESID) {
+            const h4_t rh = reinterpret_cast<const h4_t*>(rhi + row * D)[lane + 64 * i];
+            const h4_t rl = reinterpret_cast<const h4_t*>(rlo + row * D)[lane + 64 * i];
+            v[i].x += (float)rh[0] + (float)rl[0];
+            v[i].y += (float)rh[1] + (float)rl[1];
+            v[i].z += (float)rh[2] + (float)rl[2];
+            v[i].w += (float)rh[3] + (float)rl[3];
+        }
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
     const float mean = wave_sum(s) * (1.0f / D);
@@ -60,21 +72,34 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 }
 
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, long rows, int dim, float eps,
-                            hipStream_t s, void* yhi, void* ylo, float* nonfinite_slot) {
+                            hipStream_t s, void* yhi, void* ylo, float* nonfinite_slot, const void* rhi, const void* rlo) {
     if (rows <= 0 || (!y && !yhi) || ((yhi == nullptr) != (ylo == nullptr))) return hipErrorInvalidValue;
+    if ((rhi == nullptr) != (rlo == nullptr)) return hipErrorInvalidValue;
+    // the residual planes are read as 8-byte pieces of 4 halves (a row is dim halves: a multiple of 8 bytes)
+    if ((reinterpret_cast<uintptr_t>(rhi) | reinterpret_cast<uintptr_t>(rlo)) & 7) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((rows + 3) / 4);
     _Float16* hi = (_Float16*)yhi;
     _Float16* lo = (_Float16*)ylo;
-    if (dim == 768 && !hi)
-        hipLaunchKernelGGL((layernorm_kernel<3, false>), dim3(grid), dim3(256), 0, s, x, g, b, y, hi, lo, rows, eps, nonfinite_slot);
-    else if (dim == 768)
-        hipLaunchKernelGGL((layernorm_kernel<3, true>), dim3(grid), dim3(256), 0, s, x, g, b, y, hi, lo, rows, eps, nonfinite_slot);
-    else if (dim == 512 && !hi)
-        hipLaunchKernelGGL((layernorm_kernel<2, false>), dim3(grid), dim3(256), 0, s, x, g, b, y, hi, lo, rows, eps, nonfinite_slot);
+    const _Float16* rh = (const _Float16*)rhi;
+    const _Float16* rl = (const _Float16*)rlo;
+#define LN_LAUNCH(NV4, SPLIT, RESID)                                                                                              \
+    hipLaunchKernelGGL((layernorm_kernel<NV4, SPLIT, RESID>), dim3(grid), dim3(256), 0, s, x, g, b, y, hi, lo, rows, eps, nonfinite_slot, \
+                       rh, rl)
+#define LN_DIM(NV4)                                   \
+    do {                                              \
+        if (rh && hi) LN_LAUNCH(NV4, true, true);     \
+        else if (rh) LN_LAUNCH(NV4, false, true);     \
+        else if (hi) LN_LAUNCH(NV4, true, false);     \
+        else LN_LAUNCH(NV4, false, false);            \
+    } while (0)
+    if (dim == 768)
+        LN_DIM(3);
     else if (dim == 512)
-        hipLaunchKernelGGL((layernorm_kernel<2, true>), dim3(grid), dim3(256), 0, s, x, g, b, y, hi, lo, rows, eps, nonfinite_slot);
+        LN_DIM(2);
     else
         return hipErrorInvalidValue;
+#undef LN_DIM
+#undef LN_LAUNCH
     return hipGetLastError();
 }
 
