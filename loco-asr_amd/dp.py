@@ -71,6 +71,29 @@ def window_units(lengths: Sequence[int], window: int, min_samples: int = 400) ->
     return units
 
 
+def pack_windows(n_packs: int, pack_window: int) -> List[Tuple[int, int]]:
+    """extract.py --pack: the packs [p0, p1) of each window.  Windows of 1, 2, 4, ... pack_window packs: the first pack can leave
+    as soon as ITS batches are decoded (a sorted window cannot be cut before its last batch is in), the steady state sorts over
+    pack_window packs."""
+    bounds, p0, size = [], 0, 1
+    while p0 < n_packs:
+        bounds.append((p0, min(n_packs, p0 + size)))
+        p0 += size
+        size = min(pack_window, 2 * size)
+    return bounds
+
+
+def cut_window(lengths: Sequence[int], first: int, n_packs: int, pack: int) -> Tuple[List[List[int]], int]:
+    """extract.py --pack: one window of ``n_packs`` packs, cut.  ``lengths`` = the padded length of each of the window's batches,
+    which are this rank's batches first, first + 1, ... (fewer than n_packs * pack, or none, when the rank has run out).  The batch
+    indices are ordered by (length, index) and cut into groups of ``pack`` -- any set of batches may share a pack, sorting only
+    removes the rows a short batch would idle in a long pack.  Returns the groups and how many empty contributions the window still
+    owes: they keep the collectives lined up."""
+    order = sorted(range(first, first + len(lengths)), key=lambda i: (lengths[i - first], i))
+    groups = [order[g0:g0 + pack] for g0 in range(0, len(order), pack)]
+    return groups, n_packs - len(groups)
+
+
 # Set (or LOCO_FORCE_COLLECTIVE=1) to issue the collectives even in a process group of ONE rank: a one-GPU box can then run
 # the real RCCL all_gather_into_tensor on device tensors next to the encoder's streams (tests/test_gpu_rccl_world1.py,
 # bench.py --force-collective).  Without a process group there is nothing to issue and the flag is ignored.

@@ -36,7 +36,9 @@ import numpy as np
 import torch
 
 from . import synth
+from .audio_io import load_audio_16k, load_audio_channels_16k
 from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_sample_args
+from .extract import read_slurp_split
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X
 
 
@@ -95,7 +97,6 @@ def gather_items(args):
     if sum(sources) != 1:
         raise SystemExit("give exactly one input: --split (with --data-path), audio FILES, or --synthetic N")
     if args.split:
-        from .extract import read_slurp_split
         return [(str(it[0]), it[2], 0) for it in read_slurp_split(args.data_path, args.split)]
     if args.files:
         return [(os.path.splitext(os.path.basename(f))[0], f, 0) for f in args.files]
@@ -105,7 +106,6 @@ def gather_items(args):
 
 def load_batch(items, first_index, processor, device):
     """One reference batch: decoded (or synthesised) clips, padded to the longest and masked as the feature extractor does."""
-    from .extract import load_audio_16k
     clips = [synth.clip(first_index + i, n) if path is None else load_audio_16k(path, device=device) for i, (_, path, n) in enumerate(items)]
     if any(torch.is_tensor(c) and c.is_cuda for c in clips):  # a resampled clip lives on the device: pad the whole batch there
         clips = [c if torch.is_tensor(c) else torch.from_numpy(np.asarray(c)).to(device) for c in clips]
@@ -184,7 +184,6 @@ def main_long(args, ap):
         raise SystemExit("--kaldi-text needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): its lines are text")
     model = build_model(args)
     device = torch.device("cuda", torch.cuda.current_device())
-    from .extract import load_audio_16k, load_audio_channels_16k
     common = dict(vad=vad, max_length=args.max_length, slots=slots, pack=args.pack, return_scores=args.scores, timestamps=args.timestamps,
                   do_normalize=args.do_normalize)
     finite = lambda t: t if math.isfinite(t) else None  # noqa: E731 -- JSON has no infinities

@@ -172,7 +172,7 @@ def test_damaged_streams_are_refused():
 
 
 def test_the_cli_loader_reads_flac_without_soundfile(tmp_path):
-    extract = importlib.import_module("loco-asr_amd.extract")
+    audio_io = importlib.import_module("loco-asr_amd.audio_io")
     pcm = speech_like(16000, 16, channels=2, seed=3)
     frames = frames_for(len(pcm), 4096, lambda k, c: dict(kind="fixed", order=2, porder=2), nch=2, assignment=lambda k: 10)
     for f in frames:
@@ -181,7 +181,7 @@ def test_the_cli_loader_reads_flac_without_soundfile(tmp_path):
                 sp["porder"] = 0
     path = tmp_path / "audio-1-headset.flac"
     path.write_bytes(fw.write_stream(pcm, 16, 16000, frames))
-    x = extract.load_audio_16k(str(path))
+    x = audio_io.load_audio_16k(str(path))
     assert isinstance(x, np.ndarray) and x.dtype == np.float32 and x.shape == (16000,)
     want = (pcm[:, 0].astype(np.float32) / np.float32(32768) + pcm[:, 1].astype(np.float32) / np.float32(32768)) / np.float32(2)
     assert np.array_equal(x, want)

@@ -325,7 +325,7 @@ def test_loader_threads_resample_on_the_ranks_own_gpu(monkeypatch, tmp_path):
     selected -- every rank > 0 would resample on GPU 0.  The rank's device must be handed down explicitly."""
     from concurrent.futures import ThreadPoolExecutor
     from scipy.io import wavfile
-    extract = importlib.import_module("loco-asr_amd.extract")
+    audio_io = importlib.import_module("loco-asr_amd.audio_io")
     resample = importlib.import_module("loco-asr_amd.resample")
     path = str(tmp_path / "a.wav")
     wavfile.write(path, 8000, (np.sin(np.arange(8000) * 0.01) * 2000).astype(np.int16))
@@ -338,7 +338,7 @@ def test_loader_threads_resample_on_the_ranks_own_gpu(monkeypatch, tmp_path):
     monkeypatch.setattr(resample, "resample_to_16k", fake)
     rank_device = torch.device("cuda", 5)
     with ThreadPoolExecutor(2) as pool:
-        y = list(pool.map(lambda _: extract.load_audio_16k(path, rank_device), range(3)))
+        y = list(pool.map(lambda _: audio_io.load_audio_16k(path, rank_device), range(3)))
     assert len(y) == 3 and seen == [(8000, rank_device, 8000)] * 3
 
 
@@ -425,3 +425,136 @@ def test_every_tool_script_still_parses():
             compile(fh.read(), path, "exec")  # syntax only: nothing is written, nothing runs
     for path in sorted(glob.glob(os.path.join(root, "tools", "**", "*.sh"), recursive=True)):
         subprocess.run(["bash", "-n", path], check=True)
+
+
+@pytest.mark.parametrize("n_packs,pack_window,want", [
+    (0, 8, []),
+    (1, 8, [(0, 1)]),
+    (5, 2, [(0, 1), (1, 3), (3, 5)]),
+    (5, 1, [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)]),
+    (7, 3, [(0, 1), (1, 3), (3, 6), (6, 7)]),
+    (40, 8, [(0, 1), (1, 3), (3, 7), (7, 15), (15, 23), (23, 31), (31, 39), (39, 40)]),
+])
+def test_pack_windows_grow_1_2_4_and_tile_the_packs(n_packs, pack_window, want):
+    """extract.py --pack: windows of 1, 2, 4, ... pack_window packs, contiguous, covering [0, n_packs)."""
+    got = dp.pack_windows(n_packs, pack_window)
+    assert got == want
+    assert [a for a, _ in got] == [0] * bool(got) + [b for _, b in got[:-1]] and all(a < b for a, b in got)
+    assert (got[-1][1] if got else 0) == n_packs
+
+
+def test_cut_window_sorts_by_length_then_index_and_owes_the_empty_rounds():
+    """extract.py --pack: a window's batches ordered by (padded length, index) and cut into groups of `pack`; a rank that ran out of
+    batches owes the window's remaining packs as empty contributions."""
+    lengths = [5, 3, 3, 9, 1, 7, 2]
+    assert dp.cut_window(lengths, 0, 3, 3) == ([[4, 6, 1], [2, 0, 5], [3]], 0)  # the tie of batches 1 and 2 is broken by index
+    assert dp.cut_window(lengths[2:6], 2, 1, 4) == ([[4, 2, 5, 3]], 0)
+    assert dp.cut_window([11], 6, 2, 3) == ([[6]], 1)  # a window of 2 packs holding a single batch
+    assert dp.cut_window([], 7, 2, 3) == ([], 2)  # a window past the rank's last batch
+
+
+def _run_ordered_with_timeout(seconds=5.0, **kw):
+    """extract.run_ordered on a thread of its own, so that a deadlock fails the test instead of hanging it."""
+    import threading
+    out = []
+    t = threading.Thread(target=lambda: out.append(extract.run_ordered(**kw)), daemon=True)
+    t.start()
+    t.join(seconds)
+    assert not t.is_alive(), "run_ordered did not return: producer or consumer is blocked"
+    return out[0]
+
+
+def _no_finish_thread():
+    import threading
+    return not any(t.name == "loco-finish-test" for t in threading.enumerate())
+
+
+@pytest.mark.parametrize("threaded", [False, True])
+@pytest.mark.parametrize("depth", [1, 3])
+def test_run_ordered_finishes_every_item_once_in_production_order(depth, threaded):
+    import threading
+    produced, seen, names, inits = [], [], set(), []
+
+    def work():
+        for i in range(20):
+            produced.append(i)
+            yield i
+
+    def finish(item):
+        names.add(threading.current_thread().name)
+        seen.append((item, len(produced) - len(seen)))  # items produced and not yet finished, this one included
+
+    failures = _run_ordered_with_timeout(work=work(), finish=finish, depth=depth, threaded=threaded, name="loco-finish-test",
+                                         init=lambda: inits.append(threading.current_thread().name))
+    assert failures == [] and [i for i, _ in seen] == list(range(20)) and _no_finish_thread()
+    if threaded:  # the initialiser ran once, on the consumer thread, which ran every finish
+        assert names == {"loco-finish-test"} and inits == ["loco-finish-test"]
+    else:  # the oldest item is finished while `depth` are pending: never more than `depth`; depth 1 = finished at once
+        assert inits == [] and max(p for _, p in seen) == depth and "loco-finish-test" not in names
+
+
+def test_run_ordered_consumer_failure_is_reported_and_never_blocks_the_producer():
+    """finish raises on the second of six items, queue depth 1: the consumer records it and keeps draining, so every put of the
+    producer returns -- whether it sees the failure at its next item (it then stops, as the loop always did) or runs to its end."""
+    produced, seen = [], []
+
+    def work():
+        for i in range(6):
+            produced.append(i)
+            yield i
+
+    def finish(item):
+        seen.append(item)
+        if item == 1:
+            raise ValueError("second item")
+
+    failures = _run_ordered_with_timeout(work=work(), finish=finish, depth=1, threaded=True, name="loco-finish-test")
+    assert len(failures) == 1 and isinstance(failures[0], ValueError) and str(failures[0]) == "second item"
+    assert seen == [0, 1] and produced[:2] == [0, 1] and produced == list(range(len(produced)))
+    assert _no_finish_thread()
+
+
+def test_run_ordered_dead_consumer_drains_a_full_queue():
+    """The same with the queue full when the consumer fails: finish fails on item 1 only once items 2 and 3 wait in the queue and item
+    4 is on its way, so the producer's next put -- item 5, or the end mark if it has seen the failure -- gets through only because
+    the dead consumer keeps draining."""
+    import threading
+    gate, produced, seen = threading.Event(), [], []
+
+    def work():
+        for i in range(6):
+            produced.append(i)
+            if i == 4:
+                gate.set()
+            yield i
+
+    def finish(item):
+        seen.append(item)
+        if item == 1:
+            gate.wait(5.0)
+            raise ValueError("second item")
+
+    failures = _run_ordered_with_timeout(work=work(), finish=finish, depth=3, threaded=True, name="loco-finish-test")
+    assert [str(f) for f in failures] == ["second item"] and seen == [0, 1] and produced[:5] == [0, 1, 2, 3, 4] and _no_finish_thread()
+
+
+@pytest.mark.parametrize("threaded", [False, True])
+def test_run_ordered_producer_failure_comes_first_and_the_items_before_it_were_finished(threaded):
+    import threading
+    gate, seen = threading.Event(), []
+
+    def work():
+        yield 0
+        yield 1
+        gate.set()
+        raise OSError("third item unreadable")
+
+    def finish(item):
+        seen.append(item)
+        if item == 1:  # fails too, and not before the producer has: whichever is recorded first, the producer's is reported first
+            gate.wait(5.0)
+            raise ValueError("consumer, later in the list")
+
+    failures = _run_ordered_with_timeout(work=work(), finish=finish, depth=3, threaded=threaded, name="loco-finish-test")
+    assert [type(f) for f in failures] == [OSError, ValueError] and str(failures[0]) == "third item unreadable"
+    assert seen == [0, 1] and _no_finish_thread()

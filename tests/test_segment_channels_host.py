@@ -15,7 +15,7 @@ import flac_writer as fw
 la = importlib.import_module("loco-asr_amd")
 seg = importlib.import_module("loco-asr_amd.segment")
 lm = importlib.import_module("loco-asr_amd.lm")
-extract = importlib.import_module("loco-asr_amd.extract")
+audio_io = importlib.import_module("loco-asr_amd.audio_io")
 transcribe = importlib.import_module("loco-asr_amd.transcribe")
 _libmod = importlib.import_module("loco-asr_amd._lib")
 
@@ -118,10 +118,10 @@ def test_wav_reader_keeps_the_channels(tmp_path):
         fh.setsampwidth(2)
         fh.setframerate(16000)
         fh.writeframes(pcm.astype("<i2").tobytes())
-    x = extract.load_audio_channels_16k(path)
+    x = audio_io.load_audio_channels_16k(path)
     assert isinstance(x, np.ndarray) and x.shape == (2, len(pcm)) and x.dtype == np.float32 and x.flags["C_CONTIGUOUS"]
     assert np.array_equal(x, (pcm.T.astype(np.float32) * np.float32(1 / 32768)))
-    mono = extract.load_audio_16k(path)
+    mono = audio_io.load_audio_16k(path)
     assert np.array_equal(x.mean(axis=0), mono) and mono.dtype == np.float32
 
 
@@ -135,12 +135,12 @@ def test_flac_reader_keeps_the_channels(tmp_path):
     path = str(tmp_path / "call.flac")
     with open(path, "wb") as fh:
         fh.write(fw.write_stream(pcm, 16, 16000, frames))
-    x = extract.load_audio_channels_16k(path)
+    x = audio_io.load_audio_channels_16k(path)
     assert isinstance(x, np.ndarray) and x.shape == (2, len(pcm)) and x.dtype == np.float32 and x.flags["C_CONTIGUOUS"]
     assert np.array_equal(x, (pcm.T.astype(np.float32) * np.float32(1 / 32768)))
-    assert np.array_equal(x.mean(axis=0), extract.load_audio_16k(path))
+    assert np.array_equal(x.mean(axis=0), audio_io.load_audio_16k(path))
     with pytest.raises(RuntimeError, match="call.ogg"):
-        extract.load_audio_channels_16k(str(tmp_path / "call.ogg"))
+        audio_io.load_audio_channels_16k(str(tmp_path / "call.ogg"))
 
 
 # ---- Kaldi text ------------------------------------------------------------------------------------------------------------------------
