@@ -945,6 +945,42 @@ int loco_lm_ctx_step(loco_lm* lm, loco_lm_cache* cache, const int32_t* tokens, c
 int loco_op_lm_ctx_attention(const float* qkv, const float* kcache, const float* vcache, int64_t slot_stride, const int32_t* seqs, int32_t N,
                              int32_t slots, float* out, void* stream);
 
+/* ---- error rates: edit distance over symbol sequences, n-best risk (edit_distance.hip) ------------------------------------------
+ * The rule is integer and exact.  For a reference a[0..n) and a hypothesis b[0..m) of int32 symbols a cell is the pair (cost, S),
+ * compared lexicographically:
+ *     D[i][0] = (i, 0)        D[0][j] = (j, 0)
+ *     D[i][j] = min( D[i-1][j-1] + (a[i-1] == b[j-1] ? (0,0) : (1,1)),    hit / substitution
+ *                    D[i-1][j]   + (1,0),                                  deletion
+ *                    D[i][j-1]   + (1,0) )                                 insertion
+ * and the result is (cost, S) = D[n][m]: the minimum edit distance and, among the alignments of that cost, the fewest substitutions.
+ * D - I = n - m and D + I = cost - S give D and I; hits = n - S - D.  For a fixed cost the fewest substitutions is the most hits:
+ * MINIMUM COST, THEN MOST CORRECT SYMBOLS.  Swapping the two sides keeps cost and S and swaps D with I.  The result is a property of
+ * the pair, not of a traceback order.  It is this library's own tie rule: cost, and so every error RATE, is what sclite and Kaldi
+ * compute, while the split into S / D / I can differ from theirs where alignments tie.
+ *
+ * loco_op_edit_distance: `symbols` int32 [n_symbols] and `spans` int32 [P][4] = ref_start, ref_len, hyp_start, hyp_len on the device
+ * (spans may overlap or coincide); counts int32 [P][4] = S, D, I, hits.  A side holds at most loco_edit_max_len() = LOCO_EDIT_MAX_LEN
+ * symbols.  `max_len` (0 .. LOCO_EDIT_MAX_LEN) is the longest min(ref_len, hyp_len) the caller expects among the pairs: it sizes the
+ * row state a wave keeps in LDS (LOCO_EDIT_MAX_LEN always serves; a close bound is faster).  A pair gets counts = -1, -1, -1, -1, and
+ * nothing of it is read, when a length is negative or above the cap, a span leaves [0, n_symbols), or min(ref_len, hyp_len) > max_len.
+ * ref_len = 0 or hyp_len = 0 is legal (all insertions / all deletions).  A pair's four numbers depend on its own two spans alone --
+ * not on P, on its place in the launch, on max_len or on its neighbours.
+ * loco_op_nbest_risk: group u holds the hypotheses group_offsets[u] .. group_offsets[u + 1] (int32 [U + 1], ascending); `counts` is
+ * loco_op_edit_distance's output for every group's N (N - 1) / 2 pairs (i < j) in row-major order, group after group.
+ *     risk[h] = (sum over h' != h of w[h'] * cost(h, h')) / (sum over h' of w[h']),   cost = S + D + I,
+ * in double, h' ascending, every product and every sum rounded on its own (no fused multiply-add); `weights` double [total] or NULL
+ * = all 1 (Monte-Carlo MBR over samples of the model).  best[u] = the first index within the group of least risk; one hypothesis
+ * gives risk 0 and best 0, an empty group best -1.  risk double [total], best int32 [U].
+ * LOCO_E_INVALID before any device work: a null pointer (weights excepted), P < 0, U < 0, n_symbols outside 0 .. 2^31 - 1, max_len
+ * outside 0 .. LOCO_EDIT_MAX_LEN, symbols / counts / group_offsets / best not 4-byte aligned, spans not 16-byte aligned, weights /
+ * risk not 8-byte aligned.  P = 0 and U = 0 do nothing.  No allocation, no synchronisation; the caller's stream. */
+#define LOCO_EDIT_MAX_LEN 16384
+int32_t loco_edit_max_len(void);
+int loco_op_edit_distance(const int32_t* symbols, int64_t n_symbols, const int32_t* spans, int32_t P, int32_t max_len, int32_t* counts,
+                          void* stream);
+int loco_op_nbest_risk(const int32_t* counts, const int32_t* group_offsets, const double* weights, int32_t U, double* risk, int32_t* best,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,9 @@ SIGNATURES = {
     "loco_lm_ctx_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "loco_lm_ctx_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _i32, _vp, _vp, _sz, _vp]),
     "loco_op_lm_ctx_attention": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_i32), _i32, _i32, _vp, _vp]),
+    "loco_edit_max_len": (_i32, []),
+    "loco_op_edit_distance": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "loco_op_nbest_risk": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

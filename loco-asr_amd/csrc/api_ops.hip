@@ -1,6 +1,6 @@
 // C ABI (include/loco_asr.h), the operators that take no handle: single kernels behind loco_op_* for the parity tests and tools
 // (LayerNorm, GEMMs, conv0, positional conv, attention, normalize, resample, split / permute), the GEMM knobs reload, and the
-// long-form segmentation (VAD parameters and the two segment operators).
+// long-form segmentation (VAD parameters and the two segment operators) and the error-rate operators (edit distance, n-best risk).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -384,6 +384,46 @@ int loco_op_vad_segments_channels(const float* db, int32_t C, int64_t F, const L
                                   size_t workspace_bytes, void* stream) {
     return vad_segments_checked("loco_op_vad_segments_channels", db, C, F, params, crosstalk_db, seg_start, seg_end, overlap, max_segments, count,
                                 threshold_db, workspace, workspace_bytes, vad_channels_workspace_bytes((int)C, (long)F), stream);
+}
+
+// ---- error rates (edit_distance.hip) ----
+static_assert(LOCO_EDIT_MAX_LEN == kEditMaxLen, "the header's cap is the kernel's");
+
+int32_t loco_edit_max_len(void) { return kEditMaxLen; }
+
+static bool misaligned(const void* p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }
+
+int loco_op_edit_distance(const int32_t* symbols, int64_t n_symbols, const int32_t* spans, int32_t P, int32_t max_len, int32_t* counts,
+                          void* stream) {
+    const char* fn = "loco_op_edit_distance";
+    if (!symbols) return fail(LOCO_E_INVALID, "%s: symbols is null", fn);
+    if (!spans) return fail(LOCO_E_INVALID, "%s: spans is null", fn);
+    if (!counts) return fail(LOCO_E_INVALID, "%s: counts is null", fn);
+    if (P < 0) return fail(LOCO_E_INVALID, "%s: P = %d is negative", fn, P);
+    if (n_symbols < 0 || n_symbols > INT32_MAX) return fail(LOCO_E_INVALID, "%s: n_symbols = %lld is outside 0 .. 2^31 - 1", fn, (long long)n_symbols);
+    if (max_len < 0 || max_len > kEditMaxLen) return fail(LOCO_E_INVALID, "%s: max_len = %d is outside 0 .. %d", fn, max_len, kEditMaxLen);
+    if (misaligned(symbols, 4)) return fail(LOCO_E_INVALID, "%s: symbols is not 4-byte aligned", fn);
+    if (misaligned(spans, 16)) return fail(LOCO_E_INVALID, "%s: spans is not 16-byte aligned", fn);
+    if (misaligned(counts, 4)) return fail(LOCO_E_INVALID, "%s: counts is not 4-byte aligned", fn);
+    HIP_TRY(launch_edit_distance(symbols, (long)n_symbols, spans, P, max_len, counts, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_nbest_risk(const int32_t* counts, const int32_t* group_offsets, const double* weights, int32_t U, double* risk, int32_t* best,
+                       void* stream) {
+    const char* fn = "loco_op_nbest_risk";
+    if (!counts) return fail(LOCO_E_INVALID, "%s: counts is null", fn);
+    if (!group_offsets) return fail(LOCO_E_INVALID, "%s: group_offsets is null", fn);
+    if (!risk) return fail(LOCO_E_INVALID, "%s: risk is null", fn);
+    if (!best) return fail(LOCO_E_INVALID, "%s: best is null", fn);
+    if (U < 0) return fail(LOCO_E_INVALID, "%s: U = %d is negative", fn, U);
+    if (misaligned(counts, 4)) return fail(LOCO_E_INVALID, "%s: counts is not 4-byte aligned", fn);
+    if (misaligned(group_offsets, 4)) return fail(LOCO_E_INVALID, "%s: group_offsets is not 4-byte aligned", fn);
+    if (misaligned(best, 4)) return fail(LOCO_E_INVALID, "%s: best is not 4-byte aligned", fn);
+    if (misaligned(weights, 8)) return fail(LOCO_E_INVALID, "%s: weights is not 8-byte aligned", fn);
+    if (misaligned(risk, 8)) return fail(LOCO_E_INVALID, "%s: risk is not 8-byte aligned", fn);
+    HIP_TRY(launch_nbest_risk(counts, group_offsets, weights, U, risk, best, (hipStream_t)stream));
+    return LOCO_OK;
 }
 
 }  // extern "C"

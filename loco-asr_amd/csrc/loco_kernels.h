@@ -502,6 +502,19 @@ hipError_t launch_lm_ctx_gather(const float* x, const int32_t* tokens, const LmC
 // last[slot[n], :] = x's last row of every sequence with kLmCtxCommit
 hipError_t launch_lm_ctx_last(const float* x, const LmCtxSeqs& seqs, float* last, hipStream_t s);
 
+// ---- edit distance and n-best risk (edit_distance.hip) ----
+constexpr int kEditMaxLen = 16384;  // symbols per side: cost and S of a cell stay below 2^16, the row state below 64 KiB
+// counts[p] = S, D, I, hits of the pair spans[p] = ref_start, ref_len, hyp_start, hyp_len into `symbols` (minimum cost, then most
+// correct symbols); -1 x 4, nothing of the pair read, for a negative length, a length above kEditMaxLen, a span outside
+// [0, n_symbols) or min(ref_len, hyp_len) > max_len.  max_len (0 .. kEditMaxLen) sizes the launch's LDS row state.  One wave per pair;
+// a pair's numbers depend on its own two spans alone.
+hipError_t launch_edit_distance(const int32_t* symbols, long n_symbols, const int32_t* spans, int P, int max_len, int32_t* counts, hipStream_t s);
+// Group u holds hypotheses group_offsets[u] .. group_offsets[u + 1]; `counts` holds every group's N (N - 1) / 2 pairs (i < j) row-major,
+// group after group.  risk[h] = sum over h' != h (ascending) of w[h'] cost(h, h') / sum over h' (ascending) of w[h'] in double, each
+// product and sum rounded on its own; weights null = all 1; best[u] = the first index of least risk (-1 for an empty group).
+hipError_t launch_nbest_risk(const int32_t* counts, const int32_t* group_offsets, const double* weights, int U, double* risk, int32_t* best,
+                             hipStream_t s);
+
 // the C ABI's error string (loco_last_error) for translation units other than loco_api.hip
 int api_fail(int code, const char* fmt, ...);
 

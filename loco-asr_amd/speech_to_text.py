@@ -1,7 +1,8 @@
 """``SpeechT5ForSpeechToTextMI355X``: HuggingFace's speech-to-text model over the speech encoder (encoder.py) and, when decoder
 weights are loaded, the text decoder (decoder.py) -- ``forward(decoder_input_ids= / labels=)``, ``generate``, ``score``, ``align`` and
 their corpus forms ``generate_many`` / ``score_many`` / ``align_many``, which share one walk over the corpus (``corpus_packs``);
-``sample`` / ``sample_many`` draw n-best lists in ``generate_many``'s slot pool; ``transcribe_long`` cuts a recording at pauses
+``sample`` / ``sample_many`` draw n-best lists in ``generate_many``'s slot pool and ``mbr_many`` picks from them the hypothesis of
+least expected edit distance to the others (metrics.py); ``transcribe_long`` cuts a recording at pauses
 (segment.py) and hands the segments to ``generate_many`` / ``align_many``."""
 from __future__ import annotations
 
@@ -373,7 +374,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                     greedy_first: bool = False, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, pack: int = 8,
                     return_logits: bool = False, return_scores: bool = False, first_utterance: int = 0):
         """``num_return_sequences`` sampled transcripts of every utterance of a corpus -- an n-best list for ``score_many`` to rescore,
-        or for confidence by agreement.  ``batches``, ``max_length`` (an int or one per utterance), ``slots`` and ``pack`` are
+        or for confidence by agreement (``mbr_many``, metrics.mbr_select).  ``batches``, ``max_length`` (an int or one per utterance), ``slots`` and ``pack`` are
         ``generate_many``'s; the N hypotheses of an utterance are N rows of the same slot pool.  Each token is drawn on the device
         (csrc/decoder_sample.hip): logits / ``temperature``, ``top_k`` (0 = off; ties at the threshold survive), ``top_p`` (1 = off;
         HF's TopPLogitsWarper, equal logits kept or dropped together), then one draw from the softmax of what is kept.  The uniform
@@ -405,6 +406,39 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         res = dec.SampledResults([hyps] + out[1:])
         res.seed = hyps.seed
         return res
+
+    @torch.no_grad()
+    def mbr_many(self, batches, num_return_sequences: int = 8, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
+                 greedy_first: bool = False, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, pack: int = 8,
+                 unit: str = "token", delimiter_id: Optional[int] = None, weights=None, return_scores: bool = False, first_utterance: int = 0):
+        """Minimum-Bayes-risk transcripts of a corpus: ``sample_many`` with the same arguments and the same seed contract, then
+        ``metrics.mbr_select`` over every utterance's ``num_return_sequences`` hypotheses -- the one of least expected edit distance
+        to the others (``unit``, ``delimiter_id``: what is compared; ``weights``: None = every sample counts 1, ``"logprob"`` = the
+        softmax of the hypotheses' sequence log-probabilities within the list).  Ties go to the lowest index, so with ``greedy_first``
+        the greedy transcript wins them.  Because a hypothesis does not depend on ``slots`` and the distances are integers, the same
+        seed gives the same choice at any ``slots``.
+
+        Returns a metrics.MbrTranscripts: ``ids[u]`` the chosen hypothesis (a 1-D LongTensor, host), ``best[u]`` its index, ``risk[u]``
+        the risk of every hypothesis of the utterance (float64, device), ``hypotheses`` what ``sample_many`` returned, ``seed`` the seed
+        used, and with ``return_scores`` ``scores[u][h]``, the hypotheses' per-token log-probabilities."""
+        from . import metrics
+        if weights is not None and weights != "logprob":
+            raise ValueError(f"mbr_many: weights = {weights!r} is not None or 'logprob'")
+        need_scores = bool(return_scores) or weights == "logprob"
+        if unit == "word" and delimiter_id is None:  # refused before anything is decoded
+            raise ValueError("mbr_many: unit='word' needs delimiter_id, the id of the checkpoint's word-boundary token (there is no default)")
+        if unit not in ("token", "word"):
+            raise ValueError(f"mbr_many: unit = {unit!r} is not 'token' or 'word'")
+        res = self.sample_many(batches, num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                               greedy_first=greedy_first, max_length=max_length, max_new_tokens=max_new_tokens, slots=slots, pack=pack,
+                               return_scores=need_scores, first_utterance=first_utterance)
+        hyps, scores = res if need_scores else (res, None)
+        if not len(hyps):
+            return metrics.MbrTranscripts(ids=[], best=[], risk=[], hypotheses=hyps, seed=hyps.seed, scores=scores if return_scores else None)
+        sel = metrics.mbr_select(hyps, weights=weights, unit=unit, delimiter_id=delimiter_id, scores=scores if weights == "logprob" else None)
+        best = sel.best.cpu().tolist()  # the one read-back
+        return metrics.MbrTranscripts(ids=[per[b] for per, b in zip(hyps, best)], best=best, risk=sel.risk, hypotheses=hyps, seed=hyps.seed,
+                                      scores=scores if return_scores else None)
 
     @torch.no_grad()
     def sample(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, num_return_sequences: int = 1,

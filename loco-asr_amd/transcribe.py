@@ -9,7 +9,10 @@ Utterances go through the model in the reference's pairs (batch_size 2, corpus o
 slot to the next utterance (``generate_many``); the lines written are the same.  ``--nbest N`` (with ``--slots``) adds "nbest": N
 sampled transcripts of the utterance (``sample_many``: ``--temperature``, ``--top-k``, ``--top-p``, ``--seed``), each {"ids", "logprob",
 "avg_logprob"} (and "text"), sorted by "logprob", best first.  The line's other fields are then hypothesis 0: the greedy transcript only
-with ``--greedy-first``, a sampled one otherwise.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
+with ``--greedy-first``, a sampled one otherwise; ``--select mbr`` makes them the hypothesis of least expected edit distance to the
+list's others instead (metrics.mbr_select) and adds "mbr_risk" to every "nbest" entry.  ``--ref FILE`` (Kaldi ``utt_id text``; needs a
+tokenizer on disk) or ``--ref-ids FILE`` (``utt_id id id ...``) adds "errors": {"cer", "wer"?, "sub", "del", "ins", "ref_len"} to every
+line that has a reference and writes the corpus ``%CER`` / ``%WER`` lines to stderr.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
 ``--synthetic N`` seeded clips; weights: ``--pretrained DIR`` (a HuggingFace speech-to-text checkpoint directory with the decoder)
 or ``--random-init`` (the deterministic synthetic weights).
@@ -35,7 +38,7 @@ import sys
 import numpy as np
 import torch
 
-from . import synth
+from . import metrics, synth
 from .audio_io import load_audio_16k, load_audio_channels_16k
 from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_sample_args
 from .extract import read_slurp_split
@@ -151,6 +154,80 @@ def kaldi_text_lines(rec_id, segments):
     return lines
 
 
+class RefScorer:
+    """``--ref`` / ``--ref-ids``: every line's "errors" and the corpus totals (metrics.edit_counts: minimum cost, then most correct
+    symbols).  ``refs``: {utt_id: text} or, with ``ids_mode``, {utt_id: [id, ...]}.  Text is compared by character ("cer"; runs of
+    whitespace count as one blank) and by word ("wer"); ids by token ("cer" alone; <s>, </s> and <pad> dropped on both sides).  The
+    line's sub / del / ins / ref_len are the "cer" comparison's.  An utterance without a reference is named once and not counted."""
+
+    def __init__(self, refs, ids_mode):
+        self.refs, self.ids_mode = refs, bool(ids_mode)
+        self.missing, self.scored = [], 0
+        self.totals = {"CER": [0, 0, 0, 0]} if ids_mode else {"CER": [0, 0, 0, 0], "WER": [0, 0, 0, 0]}
+
+    def errors(self, uids, rows, texts):
+        """One "errors" dict per row (None without a reference): one device pass per unit for the whole call."""
+        for uid in uids:
+            if uid not in self.refs and uid not in self.missing:
+                self.missing.append(uid)
+                print(f"no reference for {uid}: not counted", file=sys.stderr)
+        have = [k for k, uid in enumerate(uids) if uid in self.refs]
+        out = [None] * len(uids)
+        if not have:
+            return out
+        if self.ids_mode:
+            passes = [("CER", [metrics.strip_specials(self.refs[uids[k]]) for k in have], [metrics.strip_specials(rows[k]) for k in have])]
+        else:
+            both = [" ".join(self.refs[uids[k]].split()) for k in have] + [" ".join(texts[k].split()) for k in have]
+            passes = [(name, units[:len(have)], units[len(have):]) for name, units in
+                      (("CER", metrics.text_units(both, "char")), ("WER", metrics.text_units(both, "word")))]
+        tables = {}
+        for name, ref_units, hyp_units in passes:
+            c = metrics.edit_counts(ref_units, hyp_units)
+            tables[name] = torch.stack([c.sub, c.dele, c.ins, c.ref_len]).cpu().tolist()  # one read-back per unit
+            for f in range(4):
+                self.totals[name][f] += sum(tables[name][f])
+        rate = lambda t, n: (t[0][n] + t[1][n] + t[2][n]) / t[3][n] if t[3][n] else None  # noqa: E731 -- JSON has no nan
+        for n, k in enumerate(have):
+            t = tables["CER"]
+            rec = {"cer": rate(t, n)}
+            if "WER" in tables:
+                rec["wer"] = rate(tables["WER"], n)
+            rec.update({"sub": t[0][n], "del": t[1][n], "ins": t[2][n], "ref_len": t[3][n]})
+            out[k] = rec
+        self.scored += len(have)
+        return out
+
+    def report(self):
+        """The corpus totals as Kaldi lines, then how many utterances were compared and how many had no reference."""
+        lines = [metrics.format_kaldi_line(name, *tot) for name, tot in self.totals.items()]
+        return lines + [f"scored {self.scored} utterances, {len(self.missing)} without a reference"]
+
+
+def load_references(args, tok):
+    """The RefScorer of ``--ref`` / ``--ref-ids``, or None; SystemExit naming what is missing."""
+    if args.ref_ids is not None:
+        from .lm import read_key_text
+        refs = {}
+        for uid, text in read_key_text(args.ref_ids).items():
+            try:
+                refs[uid] = [int(t) for t in text.split()]
+            except ValueError:
+                raise SystemExit(f"--ref-ids {args.ref_ids}: the line of {uid} is not 'utt_id id id ...'")
+        return RefScorer(refs, ids_mode=True)
+    if args.ref is None:
+        return None
+    if tok is None:
+        raise SystemExit("--ref needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): it compares text; "
+                         "--ref-ids compares token ids without one")
+    if args.ref:
+        from .lm import read_key_text
+        return RefScorer(dict(read_key_text(args.ref)), ids_mode=False)
+    if not args.split:
+        raise SystemExit("--ref without a FILE needs --split: the references are then the SLURP sentences of the split")
+    return RefScorer({str(it[0]): str(it[1]) for it in read_slurp_split(args.data_path, args.split)}, ids_mode=False)
+
+
 def main_long(args, ap):
     """``--long``: every FILE is one recording; with ``--channels split`` every channel of it is cut and decoded on its own
     (``transcribe_channels``).  Flag combinations and segmentation parameters are refused before a model is built."""
@@ -159,6 +236,8 @@ def main_long(args, ap):
                         ("--batch-size", args.batch_size != ap.get_default("batch_size"))):
         if given:
             raise SystemExit(f"--long does not go with {flag}: every segment of a recording is a batch of one, decoded greedily")
+    if args.ref is not None or args.ref_ids is not None:
+        raise SystemExit("--long does not go with --ref / --ref-ids: score_errors --long compares a recording's joined segments with its reference")
     if not args.files:
         raise SystemExit("--long needs audio FILES")
     slots = args.slots or 64
@@ -226,7 +305,7 @@ def main_long(args, ap):
     return 0
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m loco-asr_amd.transcribe", description=__doc__.split("\n\n")[0])
     ap.add_argument("--pretrained", default=None, metavar="DIR", help="HuggingFace SpeechT5ForSpeechToText checkpoint on disk (never downloaded)")
     ap.add_argument("--random-init", action="store_true", help="deterministic synthetic weights (no checkpoint available)")
@@ -264,7 +343,24 @@ def main(argv=None):
                     "there by more than this (default 15; inf = no gate)")
     ap.add_argument("--kaldi-text", default=None, metavar="FILE", help="with --channels split and a tokenizer on disk: also write Kaldi 'utt_id text' "
                     "lines, <rec>-<A|B>-<start>-<end> in centiseconds, the input of eval_ppl")
+    ap.add_argument("--select", choices=["first", "mbr"], default=None, help="with --nbest: which hypothesis the line's own fields are: first "
+                    "(default) = hypothesis 0, as ever; mbr = the one of least expected edit distance to the list's others (token ids, every "
+                    "sample weighing 1), and every \"nbest\" entry also carries \"mbr_risk\"")
+    ap.add_argument("--ref", nargs="?", const="", default=None, metavar="FILE", help="Kaldi 'utt_id text' references: every line with one also gets "
+                    "\"errors\" (cer, wer and the character-level sub / del / ins / ref_len), the corpus %%CER / %%WER go to stderr; without FILE, "
+                    "with --split, the SLURP sentences of the split.  Needs a tokenizer on disk (--tokenizer): the comparison is of text")
+    ap.add_argument("--ref-ids", default=None, metavar="FILE", help="'utt_id id id ...' references: as --ref on token ids (<s>, </s>, <pad> dropped on "
+                    "both sides), no tokenizer needed; \"errors\" then has no wer")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.select is not None and not args.nbest:
+        ap.error("--select needs --nbest: it chooses among the hypotheses of the n-best list")
+    if args.ref is not None and args.ref_ids is not None:
+        ap.error("give --ref or --ref-ids, not both")
     if args.long:
         return main_long(args, ap)
     for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
@@ -286,26 +382,37 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(f"--nbest / --temperature / --top-k / --top-p / --seed: {e}")
     items = gather_items(args)
+    tok = load_tokenizer(args.tokenizer)
+    scorer = load_references(args, tok)  # refused here, before a model is built
     from .feature_extractor import SpeechT5FeatureExtractorMI355X
     processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
     model = build_model(args)
-    tok = load_tokenizer(args.tokenizer)
     device = torch.device("cuda", torch.cuda.current_device())
     fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    def nbest_records(hyps, sums):
-        """One utterance's "nbest": its hypotheses by log-probability, best first, ties by hypothesis index."""
+    def nbest_records(hyps, sums, risk=None):
+        """One utterance's "nbest": its hypotheses by log-probability, best first, ties by hypothesis index; ``risk``: per hypothesis
+        its "mbr_risk"."""
         recs = []
         for h in sorted(range(len(hyps)), key=lambda h: (-sums[h], h)):
             row = hyps[h].tolist()
             rec = {"ids": row, "logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)}
             if tok is not None:
                 rec["text"] = tok.decode(strip_special(row))
+            if risk is not None:
+                rec["mbr_risk"] = risk[h]
             recs.append(rec)
         return recs
 
-    def write(chunk, ids, scores=None, times=None, nbest=None):
+    def line_errors(chunks_items, rows):
+        """Per row its "errors" (None without a reference), one device pass for all of ``rows``; None without --ref / --ref-ids."""
+        if scorer is None:
+            return None
+        texts = [tok.decode(strip_special(r)) for r in rows] if tok is not None else None
+        return scorer.errors([uid for uid, _, _ in chunks_items], rows, texts)
+
+    def write(chunk, ids, scores=None, times=None, nbest=None, errors=None):
         """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated); ``times``: per row the pairs;
-        ``nbest``: per row the records of its hypotheses."""
+        ``nbest``: per row the records of its hypotheses; ``errors``: per row its "errors" or None."""
         for i, ((uid, _, _), row) in enumerate(zip(chunk, ids)):
             rec = {"id": uid, "token_ids": row}
             if tok is not None:
@@ -318,6 +425,8 @@ def main(argv=None):
                 rec["token_times"] = times[i]
             if nbest is not None:
                 rec["nbest"] = nbest[i]
+            if errors is not None and errors[i] is not None:
+                rec["errors"] = errors[i]
             fh.write(json.dumps(rec) + "\n")
 
     try:
@@ -335,10 +444,15 @@ def main(argv=None):
                     flat = torch.cat([t for per in hyp_scores for t in per]).cpu().tolist()  # one read-back per window
                     ends = np.cumsum([t.shape[0] for per in hyp_scores for t in per]).tolist()
                     hyp_sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
-                    lists = [nbest_records(per, hyp_sums[u * args.nbest:(u + 1) * args.nbest]) for u, per in enumerate(hyps)]
-                    rows = [per[0] for per in hyps]
+                    pick, risks = [0] * len(hyps), [None] * len(hyps)
+                    if args.select == "mbr":  # the line's own fields are the hypothesis of least risk; ties to the lowest index
+                        sel = metrics.mbr_select(hyps)
+                        pick = sel.best.cpu().tolist()
+                        risks = [r.cpu().tolist() for r in sel.risk]
+                    lists = [nbest_records(per, hyp_sums[u * args.nbest:(u + 1) * args.nbest], risks[u]) for u, per in enumerate(hyps)]
+                    rows = [per[b] for per, b in zip(hyps, pick)]
                     if args.scores:
-                        rows = (rows, [per[0] for per in hyp_scores])
+                        rows = (rows, [per[b] for per, b in zip(hyp_scores, pick)])
                 else:
                     rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
                 sums = None
@@ -351,6 +465,7 @@ def main(argv=None):
                 if args.timestamps:  # the utterances' own tokens after the start token: no padding inside align_many's input
                     als = model.align_many(feats, [r[1:] for r in rows], pack=args.pack)
                     stamps = [[[round(a, 4), round(b, 4)] for a, b in zip(al.start_times.cpu().tolist(), al.end_times.cpu().tolist())] for al in als]
+                errs = line_errors([it for chunk in chunks for it in chunk], [r.tolist() for r in rows])  # one pass per window
                 for chunk in chunks:
                     ids, rows = [r.tolist() for r in rows[:len(chunk)]], rows[len(chunk):]
                     width = max(len(r) for r in ids)  # generate's rows: <pad> up to the longest row of the batch
@@ -363,7 +478,10 @@ def main(argv=None):
                     best = None
                     if lists is not None:
                         best, lists = lists[:len(chunk)], lists[len(chunk):]
-                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times, best)
+                    mine = None
+                    if errs is not None:
+                        mine, errs = errs[:len(chunk)], errs[len(chunk):]
+                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times, best, mine)
         else:
             for b0 in starts:
                 chunk = items[b0:b0 + args.batch_size]
@@ -380,10 +498,13 @@ def main(argv=None):
                 if args.timestamps:
                     al = model.align(x, m, labels=timestamp_labels(ids))
                     times = [token_times(al, i, row_length(r) - 1) for i, r in enumerate(ids)]
-                write(chunk, ids, scores, times)
+                write(chunk, ids, scores, times, errors=line_errors(chunk, ids))
     finally:
         if fh is not sys.stdout:
             fh.close()
+    if scorer is not None:
+        for line in scorer.report():
+            print(line, file=sys.stderr)
     return 0
 
 
