@@ -239,6 +239,18 @@ def edit_counts(refs, hyps) -> EditCounts:
     return EditCounts(sub=counts[:, 0], dele=counts[:, 1], ins=counts[:, 2], hits=counts[:, 3], ref_len=ref_len)
 
 
+def count_table(refs, hyps, unit: Optional[str] = None) -> List[List[int]]:
+    """The ``[sub, del, ins, ref_len]`` lists of ``edit_counts(refs, hyps)``, one entry per pair, on the host after ONE read-back.
+    ``unit=None``: symbol sequences as ``edit_counts`` takes them; ``"word"`` / ``"char"``: strings, runs of whitespace as one blank,
+    turned into symbols by one ``text_units`` call over both sides (one dictionary of words for the call)."""
+    refs, hyps = list(refs), list(hyps)
+    if unit is not None:
+        units = text_units([" ".join(s.split()) for s in refs + hyps], unit)
+        refs, hyps = units[:len(refs)], units[len(refs):]
+    c = edit_counts(refs, hyps)
+    return torch.stack([c.sub, c.dele, c.ins, c.ref_len]).cpu().tolist()
+
+
 def _fold(counts: EditCounts, pairs: int) -> ErrorRate:
     tot = torch.stack([counts.sub, counts.dele, counts.ins, counts.ref_len]).to(torch.int64).sum(dim=1)
     rate = (tot[0] + tot[1] + tot[2]).to(torch.float64) / tot[3].to(torch.float64)

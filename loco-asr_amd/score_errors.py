@@ -39,7 +39,8 @@ def build_parser():
 
 
 def rec_key(name: str) -> str:
-    """A recording's id as transcribe's --kaldi-text writes it: ``-`` and whitespace as ``_``."""
+    """A recording's id from its name: ``-`` and whitespace as ``_``, so that ``rec_id_of`` (an utterance id up to its first ``-``) finds
+    it again.  THE definition: transcribe's --kaldi-text ids (``kaldi_rec_id``) and --long's JSON ids here go through it."""
     return "".join("_" if ch == "-" or ch.isspace() else ch for ch in name)
 
 
@@ -99,17 +100,12 @@ def main(argv=None):
         print(f"no {what} matched: {only_ref} only in --ref, {only_hyp} only in --hyp", file=sys.stderr)
         return 1
     from . import metrics
-    import torch
-    clean = lambda s: " ".join(s.split())  # noqa: E731
-    both = [clean(refs[u]) for u in ids] + [clean(hyps[u]) for u in ids]
     per = open(args.per_utt, "w", encoding="utf-8") if args.per_utt else None
     try:
         for unit, name in (("word", "WER"), ("char", "CER")):
             if args.unit not in (None, unit):
                 continue
-            units = metrics.text_units(both, unit)
-            c = metrics.edit_counts(units[:len(ids)], units[len(ids):])
-            table = torch.stack([c.sub, c.dele, c.ins, c.ref_len]).cpu().tolist()
+            table = metrics.count_table([refs[u] for u in ids], [hyps[u] for u in ids], unit)
             print(metrics.format_kaldi_line(name, *(sum(row) for row in table)))
             if per is not None:
                 for n, u in enumerate(ids):

@@ -30,10 +30,13 @@ on disk) also writes one Kaldi line per segment with text, ``<rec>-<A|B>-<%06d s
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import os
 import sys
+from dataclasses import dataclass
+from typing import Any, Optional
 
 import numpy as np
 import torch
@@ -42,6 +45,10 @@ from . import metrics, synth
 from .audio_io import load_audio_16k, load_audio_channels_16k
 from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_sample_args
 from .extract import read_slurp_split
+from .feature_extractor import SpeechT5FeatureExtractorMI355X
+from .lm import read_key_text
+from .score_errors import rec_key
+from .segment import resolve_params
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X
 
 
@@ -88,10 +95,14 @@ def timestamp_labels(rows):
     return lab
 
 
+def rounded_pairs(pairs):
+    """"token_times" as written: [[start_s, end_s], ...] of (start, end) pairs, to a tenth of a millisecond."""
+    return [[round(a, 4), round(b, 4)] for a, b in pairs]
+
+
 def token_times(al, i, n):
     """[[start_s, end_s], ...] of the first n tokens of row i of a TokenAlignment (one read-back)."""
-    st, en = al.start_times[i, :n].cpu().tolist(), al.end_times[i, :n].cpu().tolist()
-    return [[round(a, 4), round(b, 4)] for a, b in zip(st, en)]
+    return rounded_pairs(zip(al.start_times[i, :n].cpu().tolist(), al.end_times[i, :n].cpu().tolist()))
 
 
 def gather_items(args):
@@ -138,8 +149,8 @@ def channel_name(index):
 
 def kaldi_rec_id(path):
     """The recording id of a file: its base name without the extension, ``-`` and whitespace replaced by ``_`` -- eval_ppl takes an
-    utterance id up to its first ``-`` as the recording."""
-    return "".join("_" if ch == "-" or ch.isspace() else ch for ch in os.path.splitext(os.path.basename(path))[0])
+    utterance id up to its first ``-`` as the recording (score_errors.rec_key, which maps --long's JSON ids the same way)."""
+    return rec_key(os.path.splitext(os.path.basename(path))[0])
 
 
 def kaldi_text_lines(rec_id, segments):
@@ -152,6 +163,11 @@ def kaldi_text_lines(rec_id, segments):
         if text:
             lines.append(f"{rec_id}-{channel_name(channel)}-{int(start) // 160:06d}-{-(-int(end) // 160):06d} {text}")
     return lines
+
+
+def pair_rate(table, n):
+    """(sub + del + ins) / ref_len of pair n of a metrics.count_table; None for an empty reference -- JSON has no nan."""
+    return (table[0][n] + table[1][n] + table[2][n]) / table[3][n] if table[3][n] else None
 
 
 class RefScorer:
@@ -175,24 +191,20 @@ class RefScorer:
         out = [None] * len(uids)
         if not have:
             return out
-        if self.ids_mode:
-            passes = [("CER", [metrics.strip_specials(self.refs[uids[k]]) for k in have], [metrics.strip_specials(rows[k]) for k in have])]
+        if self.ids_mode:  # one device pass and one read-back per unit (metrics.count_table)
+            tables = {"CER": metrics.count_table([metrics.strip_specials(self.refs[uids[k]]) for k in have],
+                                                 [metrics.strip_specials(rows[k]) for k in have])}
         else:
-            both = [" ".join(self.refs[uids[k]].split()) for k in have] + [" ".join(texts[k].split()) for k in have]
-            passes = [(name, units[:len(have)], units[len(have):]) for name, units in
-                      (("CER", metrics.text_units(both, "char")), ("WER", metrics.text_units(both, "word")))]
-        tables = {}
-        for name, ref_units, hyp_units in passes:
-            c = metrics.edit_counts(ref_units, hyp_units)
-            tables[name] = torch.stack([c.sub, c.dele, c.ins, c.ref_len]).cpu().tolist()  # one read-back per unit
+            refs, hyps = [self.refs[uids[k]] for k in have], [texts[k] for k in have]
+            tables = {"CER": metrics.count_table(refs, hyps, "char"), "WER": metrics.count_table(refs, hyps, "word")}
+        for name, table in tables.items():
             for f in range(4):
-                self.totals[name][f] += sum(tables[name][f])
-        rate = lambda t, n: (t[0][n] + t[1][n] + t[2][n]) / t[3][n] if t[3][n] else None  # noqa: E731 -- JSON has no nan
+                self.totals[name][f] += sum(table[f])
         for n, k in enumerate(have):
             t = tables["CER"]
-            rec = {"cer": rate(t, n)}
+            rec = {"cer": pair_rate(t, n)}
             if "WER" in tables:
-                rec["wer"] = rate(tables["WER"], n)
+                rec["wer"] = pair_rate(tables["WER"], n)
             rec.update({"sub": t[0][n], "del": t[1][n], "ins": t[2][n], "ref_len": t[3][n]})
             out[k] = rec
         self.scored += len(have)
@@ -207,7 +219,6 @@ class RefScorer:
 def load_references(args, tok):
     """The RefScorer of ``--ref`` / ``--ref-ids``, or None; SystemExit naming what is missing."""
     if args.ref_ids is not None:
-        from .lm import read_key_text
         refs = {}
         for uid, text in read_key_text(args.ref_ids).items():
             try:
@@ -221,17 +232,152 @@ def load_references(args, tok):
         raise SystemExit("--ref needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): it compares text; "
                          "--ref-ids compares token ids without one")
     if args.ref:
-        from .lm import read_key_text
         return RefScorer(dict(read_key_text(args.ref)), ids_mode=False)
     if not args.split:
         raise SystemExit("--ref without a FILE needs --split: the references are then the SLURP sentences of the split")
     return RefScorer({str(it[0]): str(it[1]) for it in read_slurp_split(args.data_path, args.split)}, ids_mode=False)
 
 
-def main_long(args, ap):
-    """``--long``: every FILE is one recording; with ``--channels split`` every channel of it is cut and decoded on its own
-    (``transcribe_channels``).  Flag combinations and segmentation parameters are refused before a model is built."""
-    from .segment import resolve_params
+# ---- records: what a line of --out holds ---------------------------------------------------------------------------------------
+@dataclass
+class Line:
+    """One utterance on its way to --out.  ``ids``: its generated row without padding; ``logprob``: (the sum of the generated tokens'
+    log-probabilities, how many the decode path counts as generated); ``times``: its "token_times"; ``nbest``: the records of its
+    hypotheses; ``errors``: its "errors".  A field that is None is not written."""
+    uid: str
+    ids: list
+    logprob: Optional[tuple] = None
+    times: Optional[list] = None
+    nbest: Optional[list] = None
+    errors: Optional[dict] = None
+
+
+def token_fields(tok, ids, logprob=None, avg_logprob=None, times=None):
+    """What an utterance and a segment share, in the order written: token_ids, text?, logprob?, avg_logprob?, token_times?.  The
+    values are the caller's (a segment's average is ``transcribe_long``'s, an utterance's its decode path's); "text" is ``ids`` read by
+    the tokenizer, when one was found."""
+    rec = {"token_ids": ids}
+    if tok is not None:
+        rec["text"] = tok.decode(strip_special(ids))
+    if logprob is not None:
+        rec["logprob"], rec["avg_logprob"] = logprob, avg_logprob
+    if times is not None:
+        rec["token_times"] = times
+    return rec
+
+
+def utterance_record(line, tok, width=0):
+    """The JSON object of a Line: id, the token fields, nbest?, errors?; the row <pad>-ded up to ``width`` tokens."""
+    total, n = line.logprob if line.logprob is not None else (None, None)
+    rec = {"id": line.uid}
+    rec.update(token_fields(tok, line.ids + [PAD_TOKEN_ID] * (width - len(line.ids)), total, None if total is None else total / n, line.times))
+    if line.nbest is not None:
+        rec["nbest"] = line.nbest
+    if line.errors is not None:
+        rec["errors"] = line.errors
+    return rec
+
+
+def nbest_records(hyps, sums, tok, risk=None):
+    """One utterance's "nbest": its hypotheses (1-D id tensors) by log-probability ``sums[h]``, best first, ties by hypothesis index;
+    ``risk``: per hypothesis its "mbr_risk"."""
+    recs = []
+    for h in sorted(range(len(hyps)), key=lambda h: (-sums[h], h)):
+        row = hyps[h].tolist()
+        rec = {"ids": row, "logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)}
+        if tok is not None:
+            rec["text"] = tok.decode(strip_special(row))
+        if risk is not None:
+            rec["mbr_risk"] = risk[h]
+        recs.append(rec)
+    return recs
+
+
+def segment_record(sg, tok, split, scores, timestamps):
+    """The JSON object of a LongSegment: channel?, start_s, end_s, overlap_s?, then the token fields (``split``: --channels split)."""
+    rec = {"channel": channel_name(sg.channel)} if split else {}
+    rec.update(start_s=round(sg.start_s, 4), end_s=round(sg.end_s, 4))
+    if split:
+        rec["overlap_s"] = round(sg.overlap_s, 4)
+    rec.update(token_fields(tok, sg.ids.tolist(), sg.logprob if scores else None, sg.avg_logprob if scores else None,
+                            rounded_pairs(sg.token_times.tolist()) if timestamps else None))
+    return rec
+
+
+def finite_or_none(t):
+    """JSON has no infinities."""
+    return t if math.isfinite(t) else None
+
+
+def recording_record(rec_id, res, tok, split, scores, timestamps):
+    """The JSON object of a LongTranscript: id, duration_s, threshold_db (a list per channel with ``split``), segments, text?."""
+    rec = {"id": rec_id, "duration_s": round(res.duration_s, 4),
+           "threshold_db": [finite_or_none(t) for t in res.threshold_db] if split else finite_or_none(res.threshold_db),
+           "segments": [segment_record(sg, tok, split, scores, timestamps) for sg in res.segments]}
+    if tok is not None:
+        rec["text"] = " ".join(one["text"] for one in rec["segments"])
+    return rec
+
+
+def write_lines(fh, batch, tok):
+    """One reference batch of Lines to --out, as ``generate`` returns a batch: every row <pad>-ded up to the batch's longest."""
+    width = max(len(line.ids) for line in batch)
+    for line in batch:
+        fh.write(json.dumps(utterance_record(line, tok, width)) + "\n")
+
+
+def write_recording(fh, kh, path, res, run):
+    """One recording's line to --out and, with --kaldi-text, its segments' lines there (a tokenizer is on disk then)."""
+    args, split = run.args, run.args.channels == "split"
+    rec = recording_record(os.path.splitext(os.path.basename(path))[0], res, run.tok, split, args.scores, args.timestamps)
+    fh.write(json.dumps(rec) + "\n")
+    if kh is not None:
+        rows = [(sg.channel, round(sg.start_s * 16000), round(sg.end_s * 16000), one["text"]) for sg, one in zip(res.segments, rec["segments"])]
+        kh.writelines(line + "\n" for line in kaldi_text_lines(kaldi_rec_id(path), rows))
+
+
+@contextlib.contextmanager
+def open_outputs(args):
+    """(the handle of --out, the handle of --kaldi-text or None), both closed on the way out -- stdout excepted."""
+    with contextlib.ExitStack() as stack:
+        fh = sys.stdout if args.out == "-" else stack.enter_context(open(args.out, "w"))
+        kh = stack.enter_context(open(args.kaldi_text, "w", encoding="utf-8")) if args.kaldi_text else None
+        yield fh, kh
+
+
+# ---- flags: every refusal that needs no device, before a model is built --------------------------------------------------------------
+def check_args(args, ap):
+    """Refuses what the parsed arguments alone show to be wrong; without ``--long`` (whose own checks are ``check_long_args``) also
+    resolves ``--seed``: one seed for the whole corpus, whatever the windows."""
+    if args.select is not None and not args.nbest:
+        ap.error("--select needs --nbest: it chooses among the hypotheses of the n-best list")
+    if args.ref is not None and args.ref_ids is not None:
+        ap.error("give --ref or --ref-ids, not both")
+    if args.long:
+        return
+    for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
+                    ("--no-trim", args.no_trim or None), ("--channels", args.channels), ("--crosstalk-db", args.crosstalk_db),
+                    ("--kaldi-text", args.kaldi_text)):
+        if v is not None:
+            raise SystemExit(f"{flag} needs --long")
+    if args.batch_size < 1:
+        raise SystemExit("--batch-size must be >= 1")
+    if args.slots < 0 or args.pack < 1:
+        raise SystemExit("--slots must be >= 0 and --pack >= 1")
+    if args.nbest and not args.slots:
+        raise SystemExit("--nbest needs --slots: the hypotheses are rows of the decoder pool")
+    if args.nbest < 0:
+        raise SystemExit("--nbest must be >= 0")
+    if args.nbest:
+        try:
+            args.seed = int(check_sample_args(args.nbest, args.temperature, args.top_k, args.top_p, args.seed)[1].seed)
+        except ValueError as e:
+            raise SystemExit(f"--nbest / --temperature / --top-k / --top-p / --seed: {e}")
+
+
+def check_long_args(args, ap):
+    """``--long``: refuses the flags that do not go with it and bad segmentation parameters, resolves ``--slots`` (64) and, with
+    ``--channels split``, ``--crosstalk-db`` (15); returns the segmentation parameters (segment.resolve_params)."""
     for flag, given in (("--split", bool(args.split)), ("--synthetic", args.synthetic > 0), ("--nbest", args.nbest != 0),
                         ("--batch-size", args.batch_size != ap.get_default("batch_size"))):
         if given:
@@ -240,8 +386,8 @@ def main_long(args, ap):
         raise SystemExit("--long does not go with --ref / --ref-ids: score_errors --long compares a recording's joined segments with its reference")
     if not args.files:
         raise SystemExit("--long needs audio FILES")
-    slots = args.slots or 64
-    if not 1 <= slots <= 64 or args.pack < 1:
+    args.slots = args.slots or 64
+    if not 1 <= args.slots <= 64 or args.pack < 1:
         raise SystemExit("--slots must be 1 .. 64 and --pack >= 1")
     given = {k: v for k, v in (("max_segment_s", args.max_segment_s), ("min_silence_s", args.min_silence_s), ("margin_db", args.vad_margin_db))
              if v is not None}
@@ -249,8 +395,7 @@ def main_long(args, ap):
         vad = resolve_params(None, trim=not args.no_trim, **given)
     except ValueError as e:
         raise SystemExit(f"--max-segment-s / --min-silence-s / --vad-margin-db: {e}")
-    split = args.channels == "split"
-    if not split:
+    if args.channels != "split":
         for flag, v in (("--crosstalk-db", args.crosstalk_db), ("--kaldi-text", args.kaldi_text)):
             if v is not None:
                 raise SystemExit(f"{flag} needs --channels split: only there does a segment have a channel")
@@ -258,50 +403,148 @@ def main_long(args, ap):
         args.crosstalk_db = 15.0 if args.crosstalk_db is None else args.crosstalk_db
         if not args.crosstalk_db >= 0.0:
             raise SystemExit(f"--crosstalk-db: crosstalk_db = {args.crosstalk_db:g} is NaN or negative (inf switches the gate off)")
+    return vad
+
+
+def load_long_tokenizer(args):
+    """``--long``'s tokenizer (None: no "text"); ``--kaldi-text`` without one on disk is refused: its lines are text."""
     tok = load_tokenizer(args.tokenizer)
     if args.kaldi_text and tok is None:
         raise SystemExit("--kaldi-text needs a tokenizer found on disk (--tokenizer: an spm_char.model file or a directory holding one): its lines are text")
-    model = build_model(args)
-    device = torch.device("cuda", torch.cuda.current_device())
-    common = dict(vad=vad, max_length=args.max_length, slots=slots, pack=args.pack, return_scores=args.scores, timestamps=args.timestamps,
+    return tok
+
+
+# ---- decoding: both paths yield reference batches of Lines in corpus order ----------------------------------------------------------
+@dataclass
+class Run:
+    """What the stages of one command share."""
+    args: argparse.Namespace
+    tok: Any
+    scorer: Optional[RefScorer]
+    model: Any
+    processor: Any
+    device: Any
+
+
+def span_sums(spans):
+    """``math.fsum`` of every tensor of ``spans`` (1-D device tensors) after ONE read-back of them all."""
+    flat = torch.cat(spans).cpu().tolist()
+    ends = np.cumsum([t.shape[0] for t in spans]).tolist()
+    return [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
+
+
+def line_errors(run, uids, rows):
+    """Per row its "errors" (None without a reference, or without --ref / --ref-ids): one device pass for all of ``rows``."""
+    if run.scorer is None:
+        return [None] * len(rows)
+    texts = [run.tok.decode(strip_special(r)) for r in rows] if run.tok is not None else None
+    return run.scorer.errors(uids, rows, texts)
+
+
+def batches_of(lines, size):
+    """A window's Lines regrouped into the reference batches they were loaded as: ``size`` at a time, the last one what is left."""
+    return [lines[k:k + size] for k in range(0, len(lines), size)]
+
+
+def pair_lines(run, items):
+    """Without --slots: encoder + ``generate`` per reference batch (then ``align``, then the references' pass), one batch of Lines each."""
+    args, model = run.args, run.model
+    for b0 in range(0, len(items), args.batch_size):
+        chunk = items[b0:b0 + args.batch_size]
+        f = load_batch(chunk, b0, run.processor, run.device)
+        x, m = f["input_values"].to(run.device), f["attention_mask"].to(run.device)
+        if args.scores:
+            out = model.generate(x, m, max_length=args.max_length, return_dict_in_generate=True, output_scores=True)
+            generated = (model._decoder_runtime.last_lengths - 1).tolist()
+            rows, scores = out.sequences.cpu().tolist(), list(zip(out.sequence_logprobs.cpu().tolist(), generated))
+        else:
+            rows, scores = model.generate(x, m, max_length=args.max_length).cpu().tolist(), [None] * len(chunk)
+        times = [None] * len(chunk)
+        if args.timestamps:
+            al = model.align(x, m, labels=timestamp_labels(rows))
+            times = [token_times(al, i, row_length(r) - 1) for i, r in enumerate(rows)]
+        uids = [uid for uid, _, _ in chunk]
+        errs = line_errors(run, uids, rows)
+        yield [Line(uid, r[:row_length(r)], s, t, None, e) for uid, r, s, t, e in zip(uids, rows, scores, times, errs)]
+
+
+def greedy_window(run, feats):
+    """(rows, their log-probability sums or None) of one window's batches through ``generate_many``."""
+    args = run.args
+    out = run.model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
+    if not args.scores:
+        return out, None
+    rows, per_token = out
+    return rows, span_sums(per_token)  # one read-back per window
+
+
+def sampled_window(run, feats, first_utterance):
+    """--nbest: (rows, their log-probability sums, per utterance its "nbest") of one window's batches through ``sample_many``.  The row
+    is hypothesis 0 or, with --select mbr, the one of least risk (ties to the lowest index); every hypothesis is scored, so the row's
+    sum is one of the sums the list was sorted by."""
+    args = run.args
+    hyps, hyp_scores = run.model.sample_many(feats, num_return_sequences=args.nbest, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                             seed=args.seed, greedy_first=args.greedy_first, max_length=args.max_length, slots=args.slots,
+                                             pack=args.pack, return_scores=True, first_utterance=first_utterance)
+    sums = batches_of(span_sums([t for per in hyp_scores for t in per]), args.nbest)  # one read-back per window
+    pick, risks = [0] * len(hyps), [None] * len(hyps)
+    if args.select == "mbr":
+        sel = metrics.mbr_select(hyps)
+        pick = sel.best.cpu().tolist()
+        risks = [r.cpu().tolist() for r in sel.risk]
+    lists = [nbest_records(per, mine, run.tok, risk) for per, mine, risk in zip(hyps, sums, risks)]
+    return [per[b] for per, b in zip(hyps, pick)], [mine[b] for mine, b in zip(sums, pick)], lists
+
+
+def window_lines(run, items, starts):
+    """The Lines of the batches that begin at ``starts``, loaded, encoded and decoded in the pool as one window."""
+    args = run.args
+    chunks = [items[b0:b0 + args.batch_size] for b0 in starts]
+    feats = [load_batch(chunk, b0, run.processor, run.device) for chunk, b0 in zip(chunks, starts)]
+    lists = None
+    if args.nbest:
+        rows, sums, lists = sampled_window(run, feats, starts[0])
+    else:
+        rows, sums = greedy_window(run, feats)
+    ids, n = [r.tolist() for r in rows], len(rows)
+    scores = [(v, len(r) - 1) for v, r in zip(sums, ids)] if args.scores else [None] * n
+    stamps = [None] * n
+    if args.timestamps:  # the utterances' own tokens after the start token: no padding inside align_many's input
+        als = run.model.align_many(feats, [r[1:] for r in rows], pack=args.pack)
+        stamps = [rounded_pairs(zip(al.start_times.cpu().tolist(), al.end_times.cpu().tolist())) for al in als]
+    uids = [uid for chunk in chunks for uid, _, _ in chunk]
+    errs = line_errors(run, uids, ids)  # one pass per window
+    return [Line(*fields) for fields in zip(uids, ids, scores, stamps, lists or [None] * n, errs)]
+
+
+def pool_lines(run, items):
+    """With --slots: ``max(--pack, 4 * --slots)`` batches per window, each window's Lines handed on a reference batch at a time."""
+    args = run.args
+    starts = list(range(0, len(items), args.batch_size))
+    window = max(args.pack, 4 * args.slots)
+    for w0 in range(0, len(starts), window):
+        yield from batches_of(window_lines(run, items, starts[w0:w0 + window]), args.batch_size)
+
+
+def transcribe_recording(run, path, vad):
+    """The LongTranscript of one file: ``transcribe_channels`` on its channels with --channels split, ``transcribe_long`` on their mean."""
+    args, split = run.args, run.args.channels == "split"
+    x = (load_audio_channels_16k if split else load_audio_16k)(path, device=run.device)
+    x = (x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))).to(run.device)
+    common = dict(vad=vad, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores, timestamps=args.timestamps,
                   do_normalize=args.do_normalize)
-    finite = lambda t: t if math.isfinite(t) else None  # noqa: E731 -- JSON has no infinities
-    fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    kh = open(args.kaldi_text, "w", encoding="utf-8") if args.kaldi_text else None
-    try:
+    return run.model.transcribe_channels(x, crosstalk_db=args.crosstalk_db, **common) if split else run.model.transcribe_long(x, **common)
+
+
+def main_long(args, ap):
+    """``--long``: every FILE is one recording; with ``--channels split`` every channel of it is cut and decoded on its own."""
+    vad = check_long_args(args, ap)
+    tok = load_long_tokenizer(args)
+    model = build_model(args)
+    run = Run(args, tok, None, model, None, torch.device("cuda", torch.cuda.current_device()))
+    with open_outputs(args) as (fh, kh):
         for path in args.files:
-            x = (load_audio_channels_16k if split else load_audio_16k)(path, device=device)
-            x = (x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))).to(device)
-            res = model.transcribe_channels(x, crosstalk_db=args.crosstalk_db, **common) if split else model.transcribe_long(x, **common)
-            rec = {"id": os.path.splitext(os.path.basename(path))[0], "duration_s": round(res.duration_s, 4),
-                   "threshold_db": [finite(t) for t in res.threshold_db] if split else finite(res.threshold_db), "segments": []}
-            kaldi = []
-            for sg in res.segments:
-                row = sg.ids.tolist()
-                one = {"channel": channel_name(sg.channel)} if split else {}
-                one.update(start_s=round(sg.start_s, 4), end_s=round(sg.end_s, 4))
-                if split:
-                    one["overlap_s"] = round(sg.overlap_s, 4)
-                one["token_ids"] = row
-                if tok is not None:
-                    one["text"] = tok.decode(strip_special(row))
-                    if kh is not None:
-                        kaldi.append((sg.channel, round(sg.start_s * 16000), round(sg.end_s * 16000), one["text"]))
-                if args.scores:
-                    one["logprob"], one["avg_logprob"] = sg.logprob, sg.avg_logprob
-                if args.timestamps:
-                    one["token_times"] = [[round(a, 4), round(b, 4)] for a, b in sg.token_times.tolist()]
-                rec["segments"].append(one)
-            if tok is not None:
-                rec["text"] = " ".join(one["text"] for one in rec["segments"])
-            fh.write(json.dumps(rec) + "\n")
-            if kh is not None:
-                kh.writelines(line + "\n" for line in kaldi_text_lines(kaldi_rec_id(path), kaldi))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
-        if kh is not None:
-            kh.close()
+            write_recording(fh, kh, path, transcribe_recording(run, path, vad), run)
     return 0
 
 
@@ -354,157 +597,29 @@ def build_parser():
     return ap
 
 
-def main(argv=None):
-    ap = build_parser()
-    args = ap.parse_args(argv)
-    if args.select is not None and not args.nbest:
-        ap.error("--select needs --nbest: it chooses among the hypotheses of the n-best list")
-    if args.ref is not None and args.ref_ids is not None:
-        ap.error("give --ref or --ref-ids, not both")
-    if args.long:
-        return main_long(args, ap)
-    for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
-                    ("--no-trim", args.no_trim or None), ("--channels", args.channels), ("--crosstalk-db", args.crosstalk_db),
-                    ("--kaldi-text", args.kaldi_text)):
-        if v is not None:
-            raise SystemExit(f"{flag} needs --long")
-    if args.batch_size < 1:
-        raise SystemExit("--batch-size must be >= 1")
-    if args.slots < 0 or args.pack < 1:
-        raise SystemExit("--slots must be >= 0 and --pack >= 1")
-    if args.nbest and not args.slots:
-        raise SystemExit("--nbest needs --slots: the hypotheses are rows of the decoder pool")
-    if args.nbest < 0:
-        raise SystemExit("--nbest must be >= 0")
-    if args.nbest:  # refused here, before a model is built; one seed for the whole corpus, whatever the windows
-        try:
-            args.seed = int(check_sample_args(args.nbest, args.temperature, args.top_k, args.top_p, args.seed)[1].seed)
-        except ValueError as e:
-            raise SystemExit(f"--nbest / --temperature / --top-k / --top-p / --seed: {e}")
-    items = gather_items(args)
-    tok = load_tokenizer(args.tokenizer)
-    scorer = load_references(args, tok)  # refused here, before a model is built
-    from .feature_extractor import SpeechT5FeatureExtractorMI355X
-    processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
-    model = build_model(args)
-    device = torch.device("cuda", torch.cuda.current_device())
-    fh = sys.stdout if args.out == "-" else open(args.out, "w")
-    def nbest_records(hyps, sums, risk=None):
-        """One utterance's "nbest": its hypotheses by log-probability, best first, ties by hypothesis index; ``risk``: per hypothesis
-        its "mbr_risk"."""
-        recs = []
-        for h in sorted(range(len(hyps)), key=lambda h: (-sums[h], h)):
-            row = hyps[h].tolist()
-            rec = {"ids": row, "logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)}
-            if tok is not None:
-                rec["text"] = tok.decode(strip_special(row))
-            if risk is not None:
-                rec["mbr_risk"] = risk[h]
-            recs.append(rec)
-        return recs
-
-    def line_errors(chunks_items, rows):
-        """Per row its "errors" (None without a reference), one device pass for all of ``rows``; None without --ref / --ref-ids."""
-        if scorer is None:
-            return None
-        texts = [tok.decode(strip_special(r)) for r in rows] if tok is not None else None
-        return scorer.errors([uid for uid, _, _ in chunks_items], rows, texts)
-
-    def write(chunk, ids, scores=None, times=None, nbest=None, errors=None):
-        """``scores``: per row (sum of the generated tokens' log-probabilities, how many were generated); ``times``: per row the pairs;
-        ``nbest``: per row the records of its hypotheses; ``errors``: per row its "errors" or None."""
-        for i, ((uid, _, _), row) in enumerate(zip(chunk, ids)):
-            rec = {"id": uid, "token_ids": row}
-            if tok is not None:
-                rec["text"] = tok.decode(strip_special(row))
-            if scores is not None:
-                total, n = scores[i]
-                rec["logprob"] = total
-                rec["avg_logprob"] = total / n
-            if times is not None:
-                rec["token_times"] = times[i]
-            if nbest is not None:
-                rec["nbest"] = nbest[i]
-            if errors is not None and errors[i] is not None:
-                rec["errors"] = errors[i]
-            fh.write(json.dumps(rec) + "\n")
-
-    try:
-        starts = list(range(0, len(items), args.batch_size))
-        if args.slots:
-            window = max(args.pack, 4 * args.slots)  # batches loaded, encoded and decoded per generate_many call
-            for w0 in range(0, len(starts), window):
-                chunks = [items[b0:b0 + args.batch_size] for b0 in starts[w0:w0 + window]]
-                feats = [load_batch(chunk, b0, processor, device) for chunk, b0 in zip(chunks, starts[w0:w0 + window])]
-                lists = None
-                if args.nbest:  # hypothesis 0 takes generate_many's place; every hypothesis is scored
-                    hyps, hyp_scores = model.sample_many(feats, num_return_sequences=args.nbest, temperature=args.temperature, top_k=args.top_k,
-                                                         top_p=args.top_p, seed=args.seed, greedy_first=args.greedy_first, max_length=args.max_length,
-                                                         slots=args.slots, pack=args.pack, return_scores=True, first_utterance=starts[w0])
-                    flat = torch.cat([t for per in hyp_scores for t in per]).cpu().tolist()  # one read-back per window
-                    ends = np.cumsum([t.shape[0] for per in hyp_scores for t in per]).tolist()
-                    hyp_sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
-                    pick, risks = [0] * len(hyps), [None] * len(hyps)
-                    if args.select == "mbr":  # the line's own fields are the hypothesis of least risk; ties to the lowest index
-                        sel = metrics.mbr_select(hyps)
-                        pick = sel.best.cpu().tolist()
-                        risks = [r.cpu().tolist() for r in sel.risk]
-                    lists = [nbest_records(per, hyp_sums[u * args.nbest:(u + 1) * args.nbest], risks[u]) for u, per in enumerate(hyps)]
-                    rows = [per[b] for per, b in zip(hyps, pick)]
-                    if args.scores:
-                        rows = (rows, [per[b] for per, b in zip(hyp_scores, pick)])
-                else:
-                    rows = model.generate_many(feats, max_length=args.max_length, slots=args.slots, pack=args.pack, return_scores=args.scores)
-                sums = None
-                if args.scores:
-                    rows, per_token = rows
-                    flat = torch.cat(per_token).cpu().tolist()  # one read-back per window
-                    ends = np.cumsum([t.shape[0] for t in per_token]).tolist()
-                    sums = [math.fsum(flat[a:b]) for a, b in zip([0] + ends[:-1], ends)]
-                stamps = None
-                if args.timestamps:  # the utterances' own tokens after the start token: no padding inside align_many's input
-                    als = model.align_many(feats, [r[1:] for r in rows], pack=args.pack)
-                    stamps = [[[round(a, 4), round(b, 4)] for a, b in zip(al.start_times.cpu().tolist(), al.end_times.cpu().tolist())] for al in als]
-                errs = line_errors([it for chunk in chunks for it in chunk], [r.tolist() for r in rows])  # one pass per window
-                for chunk in chunks:
-                    ids, rows = [r.tolist() for r in rows[:len(chunk)]], rows[len(chunk):]
-                    width = max(len(r) for r in ids)  # generate's rows: <pad> up to the longest row of the batch
-                    scores = None
-                    if sums is not None:
-                        scores, sums = [(v, len(r) - 1) for v, r in zip(sums[:len(chunk)], ids)], sums[len(chunk):]
-                    times = None
-                    if stamps is not None:
-                        times, stamps = stamps[:len(chunk)], stamps[len(chunk):]
-                    best = None
-                    if lists is not None:
-                        best, lists = lists[:len(chunk)], lists[len(chunk):]
-                    mine = None
-                    if errs is not None:
-                        mine, errs = errs[:len(chunk)], errs[len(chunk):]
-                    write(chunk, [r + [PAD_TOKEN_ID] * (width - len(r)) for r in ids], scores, times, best, mine)
-        else:
-            for b0 in starts:
-                chunk = items[b0:b0 + args.batch_size]
-                f = load_batch(chunk, b0, processor, device)
-                x, m = f["input_values"].to(device), f["attention_mask"].to(device)
-                scores = None
-                if args.scores:
-                    out = model.generate(x, m, max_length=args.max_length, return_dict_in_generate=True, output_scores=True)
-                    generated = (model._decoder_runtime.last_lengths - 1).tolist()
-                    ids, scores = out.sequences.cpu().tolist(), list(zip(out.sequence_logprobs.cpu().tolist(), generated))
-                else:
-                    ids = model.generate(x, m, max_length=args.max_length).cpu().tolist()
-                times = None
-                if args.timestamps:
-                    al = model.align(x, m, labels=timestamp_labels(ids))
-                    times = [token_times(al, i, row_length(r) - 1) for i, r in enumerate(ids)]
-                write(chunk, ids, scores, times, errors=line_errors(chunk, ids))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
+def report(scorer):
+    """The corpus %CER / %WER lines of --ref / --ref-ids, to stderr."""
     if scorer is not None:
         for line in scorer.report():
             print(line, file=sys.stderr)
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_args(args, ap)
+    if args.long:
+        return main_long(args, ap)
+    items = gather_items(args)
+    tok = load_tokenizer(args.tokenizer)
+    scorer = load_references(args, tok)  # refused here, before a model is built
+    processor = SpeechT5FeatureExtractorMI355X(do_normalize=args.do_normalize)
+    model = build_model(args)
+    run = Run(args, tok, scorer, model, processor, torch.device("cuda", torch.cuda.current_device()))
+    with open_outputs(args) as (fh, _):
+        for batch in (pool_lines if args.slots else pair_lines)(run, items):
+            write_lines(fh, batch, tok)
+    report(scorer)
     return 0
 
 

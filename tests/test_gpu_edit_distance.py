@@ -330,3 +330,43 @@ def test_transcribe_select_and_ref_ids(gu, metrics, tmp_path, monkeypatch, capsy
     k, total = len(full) - 1, sum(len(own[u]) for u in full[:-1])
     assert f"[ {k} / {total}, 0 ins, 0 del, {k} sub ]" in err and err.count(f"no reference for {full[-1]}") == 1
     assert f"scored {k} utterances, {4 - k} without a reference" in err
+
+
+def test_transcribe_paths_write_the_same_lines_from_one_record(gu, tmp_path, monkeypatch):
+    """Both decode paths produce transcribe.Line records for one writer: five utterances, so the last batch is a single one.  Per line
+    id, token_ids and errors are equal between the pair path and the pool; the floats are each path's own (test_gpu_decoder_score.py
+    says how they relate) and only their presence and lengths are looked at.  With --nbest --scores the line's logprob IS the chosen
+    hypothesis's sum in the list -- one double, written twice."""
+    tr = importlib.import_module("loco-asr_amd.transcribe")
+    model = one_layer_model(gu)
+    monkeypatch.setattr(tr, "build_model", lambda args: model)
+    common = ["--random-init", "--synthetic", "5", "--synthetic-seconds", "1", "--max-length", "8"]
+    # references built from a first run's own ids.  With these weights a greedy row ends at its first token and leaves no id to
+    # write down, so line k's reference is its own ids with k + 1 more behind them: no two lines expect the same counts, whatever
+    # the model wrote, and line 1 gets no reference at all
+    first = [json.loads(l) for l in run_cli(tr, common, tmp_path / "first.jsonl").splitlines()]
+    assert len(first) == 5
+    ref_ids = {l["id"]: tr.strip_special(l["token_ids"]) + [10 + k] * (k + 1) for k, l in enumerate(first) if k != 1}
+    refs = tmp_path / "own.ids"
+    refs.write_text("".join(f"{k} {' '.join(map(str, v))}\n" for k, v in ref_ids.items()))
+    flags = common + ["--scores", "--timestamps", "--ref-ids", str(refs)]
+    pair = [json.loads(l) for l in run_cli(tr, flags, tmp_path / "pair.jsonl").splitlines()]
+    pool = [json.loads(l) for l in run_cli(tr, flags + ["--slots", "4", "--pack", "2"], tmp_path / "pool.jsonl").splitlines()]
+    assert len(pair) == len(pool) == 5
+    for a, b, was in zip(pair, pool, first):
+        assert a["id"] == b["id"] == was["id"] and a["token_ids"] == b["token_ids"] == was["token_ids"]
+        want = {}
+        if a["id"] in ref_ids:
+            r = ref_ids[a["id"]]
+            S, D, I, _ = ref.edit_counts(r, tr.strip_special(a["token_ids"]))
+            want = {"errors": {"cer": (S + D + I) / len(r), "sub": S, "del": D, "ins": I, "ref_len": len(r)}}
+        generated = tr.row_length(a["token_ids"]) - 1
+        for line in (a, b):
+            assert list(line) == ["id", "token_ids", "logprob", "avg_logprob", "token_times"] + list(want)
+            assert {k: line[k] for k in want} == want, line["id"]
+            assert line["avg_logprob"] == line["logprob"] / generated
+            assert len(line["token_times"]) == generated and all(len(p) == 2 for p in line["token_times"])
+    mbr = common + ["--slots", "4", "--nbest", "3", "--seed", "3", "--greedy-first", "--scores", "--select", "mbr"]
+    for line in (json.loads(l) for l in run_cli(tr, mbr, tmp_path / "mbr.jsonl").splitlines()):
+        mine = line["token_ids"][:tr.row_length(line["token_ids"])]
+        assert any(r["ids"] == mine and r["logprob"] == line["logprob"] for r in line["nbest"]), line["id"]  # exact: one double
