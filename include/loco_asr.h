@@ -722,6 +722,80 @@ int loco_decoder_pool_step_sample(loco_encoder* enc, int32_t slots, int32_t T_ca
                                   const loco_sample_config* config, float* step_logits, int32_t* step_tokens, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/* ---- decoder beam search: K beams per utterance in the slot pool -------------------------------------------------------------------
+ * The rule (csrc/decoder_beam.hip, one definition) is HF's _beam_search with flags in place of its -1e9 sentinels, scores in double
+ * and a defined tie order.  Per group: K = num_beams, V the vocabulary, cap the utterance's total length, cur the tokens every running
+ * beam holds (1 at admission); running beams 0 .. K - 1 (tokens, score run[k], alive; at admission beam 0 alone is alive, score 0), a
+ * finished list of at most K entries, best first, and a flag unsat (1).  One step:
+ *   1. lp[k][v] = the fp32 log-softmax of row k's logits by loco_decoder_score's arithmetic; candidate (k, v) of an alive beam scores
+ *      s = run[k] + (double)lp[k][v]
+ *   2. the 2K best candidates by s descending, ties to the lower flat index k V + v; a NaN after every number, NaNs by index
+ *   3. a candidate hits iff its token is </s> or cur + 1 >= cap
+ *   4. if unsat and not (early_stopping == 1 and the list holds K): every candidate of rank < K that hits enters the list with score
+ *      s / den[cur], den[n] = n ** length_penalty (a table of doubles made on the host with pow, loco_beam_den_table); the list is
+ *      sorted stably (existing entries before new ones, new ones in candidate order) and cut to K
+ *   5. the next running beams are the first K candidates that do not hit, in candidate order; fewer than K leave the rest not alive
+ *   6. cur += 1; L = cap - 1 if early_stopping == 2 and length_penalty > 0, else cur - 1; unsat &= run[0] / den[L] > worst, worst the
+ *      list's last score if it holds K, else -1e9
+ *   7. the group is done when step 5 found no beam, unsat is 0, or early_stopping == 1 and the list holds K
+ * Group g of a pool owns slots g K .. g K + K - 1 (slots / K groups); its K slots are open and finish together.
+ *   loco_beam_den_table     den_host f64 [n] (HOST): den[i] = pow(i, length_penalty), den[0] = 1.
+ *   loco_op_beam_select     the rule alone, one step for G groups on caller-supplied state, all DEVICE, rows r = g K + k:
+ *               logits f32, row r at logits + r * ld, ld >= V >= 2 K; den f64 [S_max]; status, pos, cap, cur, cnt, lengths i32 [G K]
+ *               (a group takes part iff status[g K] == 1 (open) and 0 <= pos[g K] < S_max - 1; pos is the index of the last token the
+ *               beams hold; cur / cnt as the pool keeps them); tokens i32 and token_logprobs f32 [G K, S_max]; run f64 and alive i32
+ *               [G K]; unsat and fin_count i32 [G]; fin_scores, fin_sums f64 and fin_lengths i32 [G K]; fin_tokens i32 and
+ *               fin_logprobs f32 [G K, S_max].  Outputs: logprobs f32 [G K, V] (step 1's rows), parents i32 [G K] (the slot whose rows
+ *               0 .. counts[r] - 1 slot r takes over: loco_op_beam_reorder's arguments), counts i32 [G K]; poll NULL or i32 [1] = slots
+ *               open afterwards (G K <= 64).  A new beam's token and log-probability are written at index pos + 1 of its own row; a
+ *               group that is done has status 2 and counts 0.  A group that is not open reads and writes nothing.
+ *   loco_op_beam_reorder    the gather alone: buf and shadow [layers][slots][S_max][width] of 4-byte words (DEVICE, distinct); rows
+ *               0 .. counts[r] - 1 of slot r become those of slot parents[r], clamped into r's group of K slots, for any mapping inside
+ *               a group (the rows pass through shadow); status NULL or i32 [slots]: only slots with status 1 move.  Slots whose parent
+ *               is themselves, rows >= counts[r] and other groups are not touched.  max_count >= every counts[r] sizes the launches.
+ *   loco_decoder_beam_workspace_bytes   a pool's workspace with the beam regions after every region of loco_decoder_pool_workspace_bytes
+ *               (which keep their offsets): shadow cache, finished lists, scores, parents, den, group state.  Initialise with
+ *               loco_decoder_pool_init.
+ *   loco_decoder_pool_admit_beams   n clips into the n groups group_ids (HOST, distinct, < slots / K); clip arguments as
+ *               loco_decoder_pool_admit_samples (cross k|v projected once, copied K - 1 times).  One status read-back; an open group:
+ *               LOCO_E_STATE.  The first call on a workspace after loco_decoder_pool_init fixes the config for that pool (kept by the
+ *               handle per workspace address, as the sampling mask is); it needs every slot not open; another config later: LOCO_E_STATE.
+ *   loco_decoder_pool_step_beam     loco_decoder_pool_step's launches up to the logits, then the select and reorder kernels; the same
+ *               bounds.  Optional outputs (DEVICE): step_logits f32 [slots, V], step_logprobs f32 [slots, V], step_parents i32 [slots]
+ *               (rows of groups that did not take part are not written).  Asynchronous, no host read.
+ *   loco_decoder_pool_read_beams    group's finished list into HOST buffers (pinned for an asynchronous copy), each optional: count
+ *               i32 [1], tokens i32 [K, S_max], lengths i32 [K], scores f64 [K], sum_logprobs f64 [K], token_logprobs f32 [K, S_max]
+ *               (entry t = log P of token t, entry 0 = 0).  Entries >= count are not meaningful.
+ * A beam pool is stepped with loco_decoder_pool_step_beam only: loco_decoder_pool_step, _step_sample, _admit and _admit_samples on it,
+ * and loco_decoder_pool_step_beam on a pool that is none, return LOCO_E_STATE.
+ * Errors: struct_size, num_beams outside 1 .. 16 or 2 num_beams > V, a length_penalty that is not finite, early_stopping outside 0 .. 2:
+ * LOCO_E_INVALID naming the field. */
+typedef struct loco_beam_config {
+    uint32_t struct_size;   /* sizeof(loco_beam_config) */
+    int32_t num_beams;      /* 1 .. 16 */
+    double length_penalty;  /* finite */
+    int32_t early_stopping; /* 0 false, 1 true, 2 "never" */
+    int32_t reserved;       /* 0 */
+} loco_beam_config;
+int loco_beam_den_table(double length_penalty, int32_t n, double* den_host);
+int loco_op_beam_select(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
+                        int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                        float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
+                        double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
+                        int32_t* counts, int32_t* poll, void* stream);
+int loco_op_beam_reorder(void* buf, void* shadow, int32_t layers, int32_t slots, int32_t S_max, int64_t width, const int32_t* parents,
+                         const int32_t* counts, const int32_t* status, int32_t num_beams, int32_t max_count, void* stream);
+size_t loco_decoder_beam_workspace_bytes(const loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t num_beams);
+int loco_decoder_pool_admit_beams(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, const loco_beam_config* config, int32_t n,
+                                  const int32_t* group_ids, const float* enc_out, int64_t clip_stride, const int32_t* enc_rows,
+                                  const int32_t* enc_frames, const int32_t* caps, void* workspace, size_t workspace_bytes, void* stream);
+int loco_decoder_pool_step_beam(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames,
+                                float* step_logits, float* step_logprobs, int32_t* step_parents, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int loco_decoder_pool_read_beams(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t group, int32_t* count, int32_t* tokens,
+                                 int32_t* lengths, double* scores, double* sum_logprobs, float* token_logprobs, const void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* ---- decoder scores: log-probabilities of a transcript's tokens, per-sequence sums, the labels= loss --------------------------------
  * loco_decoder_score turns logits (loco_decoder_forward's [B, S, V], or a block of step logits) into what a transcript is judged by.
  * Stateless: no handle, no workspace.  Asynchronous, reads no host memory, two launches on `stream`; it can be captured like a step.

@@ -34,6 +34,12 @@ class SampleConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class BeamConfig(C.Structure):
+    """loco_beam_config: ``struct_size`` must be ``ctypes.sizeof(BeamConfig)``; ``early_stopping`` 0 false, 1 true, 2 "never"."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_beams", C.c_int32), ("length_penalty", C.c_double), ("early_stopping", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class LocoVadParams(C.Structure):
     """LocoVadParams of include/loco_asr.h (long-form segmentation): ``loco_vad_default_params`` fills it."""
     _fields_ = [("struct_size", C.c_uint32), ("trim", C.c_int32), ("max_segment_s", C.c_double), ("min_segment_s", C.c_double),
@@ -156,6 +162,14 @@ SIGNATURES = {
     "loco_decoder_pool_admit_samples": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _i64, C.POINTER(_i32), _vp, C.POINTER(_i32),
                                                   _u32p, _u32p, C.POINTER(_i32), _vp, _sz, _vp]),
     "loco_decoder_pool_step_sample": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(SampleConfig), _vp, _vp, _vp, _sz, _vp]),
+    "loco_beam_den_table": (C.c_int, [C.c_double, _i32, C.POINTER(C.c_double)]),
+    "loco_op_beam_select": (C.c_int, [_vp, _i64, _i32, _i32, _i32, C.POINTER(BeamConfig)] + [_vp] * 23),
+    "loco_op_beam_reorder": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "loco_decoder_beam_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "loco_decoder_pool_admit_beams": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(BeamConfig), _i32, C.POINTER(_i32), _vp, _i64, C.POINTER(_i32), _vp,
+                                                C.POINTER(_i32), _vp, _sz, _vp]),
+    "loco_decoder_pool_step_beam": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "loco_decoder_pool_read_beams": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "loco_decoder_score": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),

@@ -469,6 +469,29 @@ void pool_sampled_set(loco_encoder* e, const void* ws, unsigned long long mask) 
     if (mask) v.emplace_back(ws, mask);
 }
 
+// the config of the beam pool in `ws` (null: the handle knows no such pool); loco_decoder_pool_init forgets it
+const loco_beam_config* pool_beam_config(const loco_encoder* e, const void* ws) {
+    for (const auto& it : e->pool_beam)
+        if (it.first == ws) return &it.second;
+    return nullptr;
+}
+
+void pool_beam_forget(loco_encoder* e, const void* ws) {
+    auto& v = e->pool_beam;
+    for (size_t i = 0; i < v.size(); ++i)
+        if (v[i].first == ws) {
+            v.erase(v.begin() + i);
+            return;
+        }
+}
+
+// the greedy and sampling entry points on a beam pool
+int pool_not_beam(const loco_encoder* e, const char* fn, const void* ws) {
+    if (pool_beam_config(e, ws))
+        return fail(LOCO_E_STATE, "%s: the pool holds beam groups (loco_decoder_pool_admit_beams); step it with loco_decoder_pool_step_beam", fn);
+    return LOCO_OK;
+}
+
 // what loco_decoder_pool_admit and loco_decoder_pool_admit_samples ask of clip i of n
 int pool_admit_check(const char* fn, int T_cap, int S_max, int n, int i, int rows, int cap, int64_t clip_stride) {
     if (rows < 1 || rows > T_cap)
@@ -545,6 +568,7 @@ int loco_decoder_pool_init(loco_encoder* e, int32_t slots, int32_t T_cap, int32_
     LOCO_TRY(pool_check(e, "loco_decoder_pool_init", slots, T_cap, S_max, workspace, workspace_bytes, p));
     HIP_TRY(launch_pool_init(pool_state(p, static_cast<char*>(workspace)), (hipStream_t)stream));
     pool_sampled_set(e, workspace, 0);
+    pool_beam_forget(e, workspace);
     return LOCO_OK;
 }
 
@@ -554,6 +578,7 @@ int loco_decoder_pool_admit(loco_encoder* e, int32_t slots, int32_t T_cap, int32
     const char* fn = "loco_decoder_pool_admit";
     PoolPlan p;
     LOCO_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    LOCO_TRY(pool_not_beam(e, fn, workspace));
     if (n <= 0 || n > slots) return fail(LOCO_E_INVALID, "%s: %d clips for a pool of %d slots", fn, n, slots);
     if (!slot_ids || !enc_out || !enc_rows || !caps) return fail(LOCO_E_INVALID, "%s: null argument", fn);
     if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
@@ -594,6 +619,7 @@ int loco_decoder_pool_step(loco_encoder* e, int32_t slots, int32_t T_cap, int32_
     const char* fn = "loco_decoder_pool_step";
     PoolPlan p;
     LOCO_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    LOCO_TRY(pool_not_beam(e, fn, workspace));
     LOCO_TRY(pool_step_bounds_check(fn, T_cap, S_max, max_pos, max_frames));
     if (pool_sampled_slots(e, workspace))
         return fail(LOCO_E_STATE, "%s: the pool holds slots admitted to sample (mask 0x%llx); step it with loco_decoder_pool_step_sample", fn,
@@ -614,6 +640,7 @@ int loco_decoder_pool_admit_samples(loco_encoder* e, int32_t slots, int32_t T_ca
     const char* fn = "loco_decoder_pool_admit_samples";
     PoolPlan p;
     LOCO_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    LOCO_TRY(pool_not_beam(e, fn, workspace));
     if (n <= 0 || copies <= 0 || (int64_t)n * copies > slots)
         return fail(LOCO_E_INVALID, "%s: %d clips x %d copies for a pool of %d slots", fn, n, copies, slots);
     if (!slot_ids || !enc_out || !enc_rows || !caps || !utterances || !hypotheses) return fail(LOCO_E_INVALID, "%s: null argument", fn);
@@ -664,6 +691,7 @@ int loco_decoder_pool_step_sample(loco_encoder* e, int32_t slots, int32_t T_cap,
     const char* fn = "loco_decoder_pool_step_sample";
     PoolPlan p;
     LOCO_TRY(pool_check(e, fn, slots, T_cap, S_max, workspace, workspace_bytes, p));
+    LOCO_TRY(pool_not_beam(e, fn, workspace));
     LOCO_TRY(pool_step_bounds_check(fn, T_cap, S_max, max_pos, max_frames));
     SampleRule rule;
     LOCO_TRY(sample_config_check(config, fn, rule));
@@ -686,6 +714,263 @@ int loco_op_sample_tokens(const float* logits, int64_t ld, int32_t M, int32_t V,
     SampleRule rule;
     LOCO_TRY(sample_config_check(config, fn, rule));
     HIP_TRY(launch_sample_tokens(logits, (long)ld, M, V, rule, counters, greedy, tokens, keep, uniform, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+// ---- beam search in the slot pool ------------------------------------------------------------------------------------------------
+namespace {
+
+// the beam regions of a pool's workspace, after every region of the greedy (and sampling) pool
+struct BeamPlan {
+    PoolPlan pool;
+    int K, groups;
+    size_t off_shadow, off_fin_tok, off_fin_tlp, off_fin_score, off_fin_sum, off_fin_len, off_run, off_alive, off_tlp, off_parent, off_count, off_den,
+        off_unsat, off_fin_n, off_tok_shadow, off_tlp_shadow, off_lp, total;
+};
+
+void make_beam_plan(int layers, int slots, int T, int S, int K, BeamPlan& b) {
+    make_pool_plan(layers, slots, T, S, b.pool);
+    b.K = K, b.groups = slots / K;
+    const size_t f = sizeof(float), i = sizeof(int32_t), d = sizeof(double);
+    size_t o = b.pool.total;
+    auto take = [&](size_t bytes) {
+        size_t at = o;
+        o += align_up(bytes);
+        return at;
+    };
+    b.off_shadow = take((size_t)b.pool.L * slots * S * 2 * kHidden * f);  // the self cache's shape
+    b.off_fin_tok = take((size_t)slots * S * i);
+    b.off_fin_tlp = take((size_t)slots * S * f);
+    b.off_fin_score = take(slots * d);
+    b.off_fin_sum = take(slots * d);
+    b.off_fin_len = take(slots * i);
+    b.off_run = take(slots * d);
+    b.off_alive = take(slots * i);
+    b.off_tlp = take((size_t)slots * S * f);
+    b.off_parent = take(slots * i);
+    b.off_count = take(slots * i);
+    b.off_den = take((size_t)kDecMaxPositions * d);
+    b.off_unsat = take(slots * i);
+    b.off_fin_n = take(slots * i);
+    b.off_tok_shadow = take((size_t)slots * S * i);
+    b.off_tlp_shadow = take((size_t)slots * S * f);
+    b.off_lp = take((size_t)slots * 128 * f);  // the logits region's shape
+    b.total = o;
+}
+
+BeamState beam_state(const BeamPlan& b, char* ws) {
+    auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    auto D = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    BeamState s{};
+    s.run = D(b.off_run), s.fin_score = D(b.off_fin_score), s.fin_sum = D(b.off_fin_sum), s.den = D(b.off_den);
+    s.tlp = F(b.off_tlp), s.fin_tlp = F(b.off_fin_tlp);
+    s.alive = I(b.off_alive), s.parent = I(b.off_parent), s.count = I(b.off_count), s.unsat = I(b.off_unsat), s.fin_n = I(b.off_fin_n);
+    s.fin_len = I(b.off_fin_len), s.fin_tok = I(b.off_fin_tok);
+    s.groups = b.groups, s.den_n = kDecMaxPositions;
+    return s;
+}
+
+// V <= 0: the vocabulary is not checked
+int beam_config_check(const loco_beam_config* c, const char* fn, int V, BeamRule& rule) {
+    if (!c) return fail(LOCO_E_INVALID, "%s: null loco_beam_config", fn);
+    if (c->struct_size != sizeof(loco_beam_config))
+        return fail(LOCO_E_INVALID, "%s: loco_beam_config.struct_size = %u, this library's is %zu", fn, c->struct_size, sizeof(loco_beam_config));
+    if (c->num_beams < 1 || c->num_beams > kBeamMax)
+        return fail(LOCO_E_INVALID, "%s: loco_beam_config.num_beams = %d is outside 1 .. %d", fn, c->num_beams, kBeamMax);
+    if (V > 0 && 2 * c->num_beams > V)
+        return fail(LOCO_E_INVALID, "%s: loco_beam_config.num_beams = %d needs 2 * num_beams <= V = %d candidates", fn, c->num_beams, V);
+    if (!std::isfinite(c->length_penalty))
+        return fail(LOCO_E_INVALID, "%s: loco_beam_config.length_penalty = %g must be finite", fn, c->length_penalty);
+    if (c->early_stopping < 0 || c->early_stopping > 2)
+        return fail(LOCO_E_INVALID, "%s: loco_beam_config.early_stopping = %d is not 0 (false), 1 (true) or 2 (never)", fn, c->early_stopping);
+    rule = BeamRule{c->num_beams, c->early_stopping, c->length_penalty > 0.0};
+    return LOCO_OK;
+}
+
+int beam_pool_check(const loco_encoder* e, const char* fn, int slots, int T, int S, int K, const void* ws, size_t bytes, BeamPlan& b) {
+    PoolPlan p;
+    LOCO_TRY(pool_check(e, fn, slots, T, S, ws, bytes, p));
+    if (K > slots) return fail(LOCO_E_INVALID, "%s: num_beams = %d exceeds the pool's %d slots", fn, K, slots);
+    make_beam_plan(e->dec.layers, slots, T, S, K, b);
+    if (bytes < b.total) return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes (loco_decoder_beam_workspace_bytes)", fn, bytes, b.total);
+    return LOCO_OK;
+}
+
+void fill_den_table(double length_penalty, int n, double* den) {
+    for (int i = 0; i < n; ++i) den[i] = i == 0 ? 1.0 : std::pow((double)i, length_penalty);
+}
+
+}  // namespace
+
+int loco_beam_den_table(double length_penalty, int32_t n, double* den_host) {
+    if (!den_host || n < 1 || !std::isfinite(length_penalty)) return fail(LOCO_E_INVALID, "loco_beam_den_table: null table, n < 1 or a penalty that is not finite");
+    fill_den_table(length_penalty, n, den_host);
+    return LOCO_OK;
+}
+
+size_t loco_decoder_beam_workspace_bytes(const loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t num_beams) {
+    if (!loco_decoder_pool_workspace_bytes(e, slots, T_cap, S_max) || num_beams < 1 || num_beams > kBeamMax || num_beams > slots) return 0;
+    BeamPlan b;
+    make_beam_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, num_beams, b);
+    return b.total;
+}
+
+int loco_decoder_pool_admit_beams(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, const loco_beam_config* config, int32_t n,
+                                  const int32_t* group_ids, const float* enc_out, int64_t clip_stride, const int32_t* enc_rows,
+                                  const int32_t* enc_frames, const int32_t* caps, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_admit_beams";
+    LOCO_TRY(dec_handle_check(e, fn));
+    BeamRule rule;
+    LOCO_TRY(beam_config_check(config, fn, e->dec.vocab, rule));
+    const int K = rule.K;
+    BeamPlan bp;
+    LOCO_TRY(beam_pool_check(e, fn, slots, T_cap, S_max, K, workspace, workspace_bytes, bp));
+    if (e->dec.vocab > 128) return fail(LOCO_E_INVALID, "%s: a vocabulary of %d exceeds the pool's 128 columns", fn, e->dec.vocab);
+    if (n <= 0 || n > bp.groups) return fail(LOCO_E_INVALID, "%s: %d clips for a pool of %d groups of %d slots", fn, n, bp.groups, K);
+    if (!group_ids || !enc_out || !enc_rows || !caps) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (clip_stride < 0 || (clip_stride & 3) || (reinterpret_cast<uintptr_t>(enc_out) & 15))
+        return fail(LOCO_E_INVALID, "%s: enc_out and the clip stride must be 16-byte aligned", fn);
+    const loco_beam_config* known = pool_beam_config(e, workspace);
+    if (known && (known->num_beams != config->num_beams || known->length_penalty != config->length_penalty || known->early_stopping != config->early_stopping))
+        return fail(LOCO_E_STATE, "%s: the pool's groups were admitted with another loco_beam_config; loco_decoder_pool_init comes first", fn);
+    if (pool_sampled_slots(e, workspace)) return fail(LOCO_E_STATE, "%s: the pool holds slots admitted to sample", fn);
+    PoolAdmitSamples a{};
+    a.n = n * K, a.copies = K;
+    unsigned long long seen = 0;
+    for (int i = 0; i < n; ++i) {
+        LOCO_TRY(pool_admit_check(fn, T_cap, S_max, n, i, enc_rows[i], caps[i], clip_stride));
+        const int g = group_ids[i];
+        if (g < 0 || g >= bp.groups) return fail(LOCO_E_INVALID, "%s: group %d of a pool of %d groups", fn, g, bp.groups);
+        if (seen >> g & 1) return fail(LOCO_E_INVALID, "%s: group %d is named twice", fn, g);
+        seen |= 1ull << g;
+        for (int k = 0; k < K; ++k) a.slot[i * K + k] = g * K + k, a.cap[i * K + k] = caps[i], a.rows[i * K + k] = enc_rows[i];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(bp.pool, ws);
+    // as loco_decoder_pool_admit: one read-back of the slots' status, one wait for the stream
+    std::vector<int32_t> status(slots);
+    HIP_TRY(hipMemcpyAsync(status.data(), st.status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!known) {
+        // the pool becomes a beam pool: no slot may be open under another step's rules; the den table is written while the stream idles
+        for (int r = 0; r < slots; ++r)
+            if (status[r] == kPoolOpen) return fail(LOCO_E_STATE, "%s: slot %d is open in a pool that is not a beam pool yet", fn, r);
+        std::vector<double> den(kDecMaxPositions);
+        fill_den_table(config->length_penalty, kDecMaxPositions, den.data());
+        HIP_TRY(hipMemcpyAsync(ws + bp.off_den, den.data(), den.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int k = 0; k < a.n; ++k)
+        if (status[a.slot[k]] == kPoolOpen) return fail(LOCO_E_STATE, "%s: group %d is open (its utterance has not finished)", fn, a.slot[k] / K);
+    // a clip's cross k|v: one product into the group's first slot, copies of those bytes into the other beams' regions
+    const int N = bp.pool.L * 2 * kHidden;
+    float* cross = reinterpret_cast<float*>(ws + bp.pool.off_cross);
+    for (int i = 0; i < n; ++i) {
+        float* first = cross + (size_t)a.slot[i * K] * T_cap * N;
+        LOCO_TRY(run_gemm(e, s, enc_out + (size_t)i * clip_stride, kHidden, e->dec.wckv, kHidden, e->dec.bckv, nullptr, 0, first, N, enc_rows[i], N, kHidden,
+                         kEpiNone));
+        for (int k = 1; k < K; ++k)
+            HIP_TRY(hipMemcpyAsync(cross + (size_t)a.slot[i * K + k] * T_cap * N, first, (size_t)enc_rows[i] * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(launch_pool_admit_beams(st, beam_state(bp, ws), a, enc_frames, kDecStartToken, s));
+    if (!known) e->pool_beam.emplace_back(workspace, *config);
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_step_beam(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t max_pos, int32_t max_frames,
+                                float* step_logits, float* step_logprobs, int32_t* step_parents, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    const char* fn = "loco_decoder_pool_step_beam";
+    LOCO_TRY(dec_handle_check(e, fn));
+    const loco_beam_config* config = pool_beam_config(e, workspace);
+    if (!config) return fail(LOCO_E_STATE, "%s: the pool holds no beam groups (loco_decoder_pool_admit_beams); step it with loco_decoder_pool_step", fn);
+    BeamRule rule;
+    LOCO_TRY(beam_config_check(config, fn, e->dec.vocab, rule));
+    BeamPlan bp;
+    LOCO_TRY(beam_pool_check(e, fn, slots, T_cap, S_max, rule.K, workspace, workspace_bytes, bp));
+    LOCO_TRY(pool_step_bounds_check(fn, T_cap, S_max, max_pos, max_frames));
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    const PoolState st = pool_state(bp.pool, ws);
+    const BeamState bs = beam_state(bp, ws);
+    const int V = e->dec.vocab;
+    float* logits = step_logits ? step_logits : reinterpret_cast<float*>(ws + bp.pool.off_logits);
+    float* lp = step_logprobs ? step_logprobs : reinterpret_cast<float*>(ws + bp.off_lp);
+    LOCO_TRY(pool_step_walk(e, bp.pool, ws, st, max_pos, max_frames, logits, s));
+    HIP_TRY(launch_beam_select(st, bs, rule, logits, V, V, kDecEosToken, lp, s));
+    if (step_parents) HIP_TRY(hipMemcpyAsync(step_parents, bs.parent, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    // rows 0 .. pos of the self cache, the token rows and their log-probabilities follow the parents
+    HIP_TRY(launch_beam_reorder(ws + bp.pool.off_self, ws + bp.off_shadow, bp.pool.L, slots, S_max, 2 * kHidden, bs.parent, bs.count, st.status, rule.K,
+                                max_pos + 1, s));
+    HIP_TRY(launch_beam_reorder(st.tokens, ws + bp.off_tok_shadow, 1, slots, S_max, 1, bs.parent, bs.count, st.status, rule.K, max_pos + 1, s));
+    HIP_TRY(launch_beam_reorder(bs.tlp, ws + bp.off_tlp_shadow, 1, slots, S_max, 1, bs.parent, bs.count, st.status, rule.K, max_pos + 1, s));
+    return LOCO_OK;
+}
+
+int loco_decoder_pool_read_beams(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t group, int32_t* count, int32_t* tokens,
+                                 int32_t* lengths, double* scores, double* sum_logprobs, float* token_logprobs, const void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    const char* fn = "loco_decoder_pool_read_beams";
+    LOCO_TRY(dec_handle_check(e, fn));
+    const loco_beam_config* config = pool_beam_config(e, workspace);
+    if (!config) return fail(LOCO_E_STATE, "%s: the pool holds no beam groups (loco_decoder_pool_admit_beams)", fn);
+    const int K = config->num_beams;
+    BeamPlan bp;
+    LOCO_TRY(beam_pool_check(e, fn, slots, T_cap, S_max, K, workspace, workspace_bytes, bp));
+    if (group < 0 || group >= bp.groups) return fail(LOCO_E_INVALID, "%s: group %d of a pool of %d groups", fn, group, bp.groups);
+    hipStream_t s = (hipStream_t)stream;
+    const char* ws = static_cast<const char*>(workspace);
+    const size_t r0 = (size_t)group * K;
+    auto get = [&](void* dst, size_t off, size_t first, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, ws + off + first, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(get(count, bp.off_fin_n, (size_t)group * sizeof(int32_t), sizeof(int32_t)));
+    HIP_TRY(get(tokens, bp.off_fin_tok, r0 * S_max * sizeof(int32_t), (size_t)K * S_max * sizeof(int32_t)));
+    HIP_TRY(get(lengths, bp.off_fin_len, r0 * sizeof(int32_t), K * sizeof(int32_t)));
+    HIP_TRY(get(scores, bp.off_fin_score, r0 * sizeof(double), K * sizeof(double)));
+    HIP_TRY(get(sum_logprobs, bp.off_fin_sum, r0 * sizeof(double), K * sizeof(double)));
+    HIP_TRY(get(token_logprobs, bp.off_fin_tlp, r0 * S_max * sizeof(float), (size_t)K * S_max * sizeof(float)));
+    return LOCO_OK;
+}
+
+int loco_op_beam_select(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
+                        int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                        float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
+                        double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
+                        int32_t* counts, int32_t* poll, void* stream) {
+    const char* fn = "loco_op_beam_select";
+    BeamRule rule;
+    LOCO_TRY(beam_config_check(config, fn, V, rule));
+    if (!logits || !den || !status || !pos || !cap || !cur || !cnt || !lengths || !tokens || !token_logprobs || !run || !alive || !unsat || !fin_count ||
+        !fin_scores || !fin_sums || !fin_lengths || !fin_tokens || !fin_logprobs || !logprobs || !parents || !counts)
+        return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (G < 1 || (int64_t)G * rule.K > 65535) return fail(LOCO_E_INVALID, "%s: G = %d groups of %d slots", fn, G, rule.K);
+    if (poll && G * rule.K > 64) return fail(LOCO_E_INVALID, "%s: poll counts at most 64 slots, G * num_beams = %d", fn, G * rule.K);
+    if (V > (1 << 20)) return fail(LOCO_E_INVALID, "%s: V = %d exceeds 2^20", fn, V);
+    if (ld < V) return fail(LOCO_E_INVALID, "%s: row stride ld = %lld < V = %d", fn, (long long)ld, V);
+    if (S_max < 2 || S_max > kDecMaxPositions) return fail(LOCO_E_INVALID, "%s: S_max = %d is outside 2 .. %d", fn, S_max, kDecMaxPositions);
+    PoolState p{};
+    p.poll = poll, p.status = status, p.pos = pos, p.kv_row = pos, p.cap = const_cast<int32_t*>(cap), p.lengths = lengths, p.tokens = tokens;
+    p.cur = cur, p.cnt = cnt;
+    p.slots = G * rule.K, p.S_max = S_max, p.T_cap = 0;
+    BeamState b{};
+    b.run = run, b.fin_score = fin_scores, b.fin_sum = fin_sums, b.den = den, b.tlp = token_logprobs, b.fin_tlp = fin_logprobs;
+    b.alive = alive, b.parent = parents, b.count = counts, b.unsat = unsat, b.fin_n = fin_count, b.fin_len = fin_lengths, b.fin_tok = fin_tokens;
+    b.groups = G, b.den_n = S_max;
+    HIP_TRY(launch_beam_select(p, b, rule, logits, (long)ld, V, kDecEosToken, logprobs, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_beam_reorder(void* buf, void* shadow, int32_t layers, int32_t slots, int32_t S_max, int64_t width, const int32_t* parents,
+                         const int32_t* counts, const int32_t* status, int32_t num_beams, int32_t max_count, void* stream) {
+    const char* fn = "loco_op_beam_reorder";
+    if (!buf || !shadow || buf == shadow || !parents || !counts) return fail(LOCO_E_INVALID, "%s: null argument, or buf == shadow", fn);
+    if (layers < 1 || layers > 65535 || slots < 1 || slots > 65535 || S_max < 1 || width < 1 || max_count < 0)
+        return fail(LOCO_E_INVALID, "%s: layers = %d, slots = %d, S_max = %d, width = %lld, max_count = %d", fn, layers, slots, S_max, (long long)width, max_count);
+    if (num_beams < 1 || num_beams > kBeamMax) return fail(LOCO_E_INVALID, "%s: num_beams = %d is outside 1 .. %d", fn, num_beams, kBeamMax);
+    HIP_TRY(launch_beam_reorder(buf, shadow, layers, slots, S_max, (long)width, parents, counts, status, num_beams, max_count, (hipStream_t)stream));
     return LOCO_OK;
 }
 

@@ -28,6 +28,16 @@ __device__ __forceinline__ void wave_argmax(float& bv, int& bi) {
     }
 }
 
+// ---- log-softmax of a row ---------------------------------------------------------------------------------------------------
+// log_softmax(x)[n] = (x[n] - mx) - logf(sum), mx the row's maximum (fmaxf over the lanes' columns, wave_max) and sum the row's
+// exponentials: lane l adds columns l, l + 64, ... in that order, the lanes meet in wave_sum.  All 64 lanes of the wave must call.
+__device__ __forceinline__ float row_exp_sum(const float* __restrict__ x, int V, int lane, float mx) {
+    float sum = 0.f;
+    for (int n = lane; n < V; n += 64) sum += expf(x[n] - mx);
+    return wave_sum(sum);
+}
+__device__ __forceinline__ float row_logprob(float xn, float mx, float sum) { return (xn - mx) - logf(sum); }
+
 // ---- attention -------------------------------------------------------------------------------------------------------------
 struct DecAttnRow { int i, h, b; };  // query, head, clip of row = (b * kHeads + h) * Sq + i
 __device__ __forceinline__ DecAttnRow dec_attn_row(long row, int Sq) {

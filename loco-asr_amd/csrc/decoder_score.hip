@@ -42,14 +42,12 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restr
     }
     mx = wave_max(mx);
     wave_argmax(bv, bi);
-    float sum = 0.f;
-    for (int n = lane; n < V; n += 64) sum += expf(x[n] - mx);
-    sum = wave_sum(sum);
+    const float sum = row_exp_sum(x, V, lane, mx);
     if (!targets) target = bi;
     // a label outside [0, V) is never an index: the row is NaN and counts, so the loss says so
     const float xt = (target >= 0 && target < V) ? x[target] : NAN;
     if (lane == 0) {
-        logprob[row] = (xt - mx) - logf(sum);
+        logprob[row] = row_logprob(xt, mx, sum);
         if (chosen) chosen[row] = target;
     }
 }

@@ -165,6 +165,8 @@ struct loco_encoder {
     // decoder pools that hold slots which sample: (workspace, bit r = slot r draws).  On the host because loco_decoder_pool_admit and
     // loco_decoder_pool_step enqueue what they always did: neither can mark a slot on the device.  Single caller, as the pool itself.
     std::vector<std::pair<const void*, unsigned long long>> pool_sampled;
+    // decoder pools whose slots are beam groups: (workspace, the config of loco_decoder_pool_admit_beams), kept like pool_sampled
+    std::vector<std::pair<const void*, loco_beam_config>> pool_beam;
     std::map<std::string, std::vector<int64_t>> dec_shapes;  // shapes of the decoder tensors as loaded (the vocabulary is theirs)
     // concurrency inside one forward: a batch may run as two half-batches on two streams (loco_set_streams).  The side stream and
     // its events are created on first use under side_mu; forwards in flight together serialise their second halves on it.

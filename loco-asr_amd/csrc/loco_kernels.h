@@ -409,6 +409,36 @@ hipError_t launch_pool_admit_samples(const PoolState& p, const PoolAdmitSamples&
 hipError_t launch_pool_sample_select(const PoolState& p, const uint32_t* ids, unsigned long long sampled, const SampleRule& rule, const float* logits,
                                      int vocab, int eos, int32_t* step_tokens, int ignore_index, hipStream_t s);
 
+// ---- decoder beam search (decoder_beam.hip) ----
+constexpr int kBeamMax = 16;  // beams of one group
+// K beams per group, early: 0 false, 1 true, 2 "never"; penalty_positive = (length_penalty > 0), all the device needs of it beside den
+struct BeamRule {
+    int K, early, penalty_positive;
+};
+// What a beam pool keeps beside PoolState; group g owns slots g K .. g K + K - 1.  Per slot: run f64 (accumulated score), alive i32,
+// tlp f32 [slots, S_max] (entry t = log P of token t of the slot's row, entry 0 = 0), parent i32 (the slot whose rows 0 .. count - 1
+// the slot takes over after the step) and count i32.  Per group: unsat i32, fin_n i32 and the finished list, best first, entry e of
+// group g at index g K + e: fin_score f64, fin_sum f64, fin_len i32, fin_tok i32 [., S_max], fin_tlp f32 [., S_max].
+// den f64 [den_n]: den[n] = n ** length_penalty, computed on the host.
+struct BeamState {
+    double *run, *fin_score, *fin_sum;
+    const double* den;
+    float *tlp, *fin_tlp;
+    int32_t *alive, *parent, *count, *unsat, *fin_n, *fin_len, *fin_tok;
+    int groups, den_n;
+};
+// groups of a.copies = K slots: PoolAdmitSamples' slot list (a.utterance, a.hypothesis unused), slot i the beam i % K of its group
+hipError_t launch_pool_admit_beams(const PoolState& p, const BeamState& b, const PoolAdmitSamples& a, const int32_t* frames, int start, hipStream_t s);
+// One step of the rule for every group whose first slot is open with kv_row >= 0 (the row the step wrote); logprobs f32 [slots, V] =
+// the log-softmax rows the rule used.  Rows of logits at logits + r * ld.  Ends with poll[0] = slots open.
+hipError_t launch_beam_select(const PoolState& p, const BeamState& b, const BeamRule& rule, const float* logits, long ld, int V, int eos,
+                              float* logprobs, hipStream_t s);
+// buf [layers][slots][S][W] of 4-byte words: rows 0 .. count[r] - 1 of slot r := those of slot parent[r] (clamped into r's group of K
+// slots), through shadow (same shape), for every r whose parent differs and, with open (optional, [slots]), whose open[r] is
+// kPoolOpen; max_count bounds the launches, not the copies
+hipError_t launch_beam_reorder(void* buf, void* shadow, int layers, int slots, int S, long W, const int32_t* parent, const int32_t* count,
+                               const int32_t* open, int K, int max_count, hipStream_t s);
+
 // ---- decoder scores (decoder_score.hip) ----
 // logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (decoder_common.h's rule) when targets is
 // null; 0 where targets[m] == ignore_index, NaN for another target outside [0, V); chosen (optional) [M] = the target used

@@ -175,6 +175,59 @@ def check_sample_args(num_return_sequences, temperature, top_k, top_p, seed):
     return n, _lib.SampleConfig(C.sizeof(_lib.SampleConfig), t, k, p, seed)
 
 
+MAX_BEAMS = 16
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+@dataclass
+class BeamSearchOutput:
+    """What ``beam_search`` returns, in HF's ``num_return_sequences`` layout: ``sequences`` [B * N, S] (clip b's hypotheses, best
+    first, in rows b * N .. b * N + N - 1, <pad> after the end), ``sequences_scores`` f64 [B * N] (HF's: the sum of the tokens'
+    log-probabilities over length ** length_penalty), ``token_logprobs`` [B * N, S - 1] (0 at the <pad> columns) and
+    ``sequence_logprobs`` f64 [B * N]."""
+    sequences: torch.Tensor = None
+    sequences_scores: Optional[torch.Tensor] = None
+    token_logprobs: Optional[torch.Tensor] = None
+    sequence_logprobs: Optional[torch.Tensor] = None
+
+
+class BeamHypotheses(list):
+    """``beam_search_many``'s hypotheses, ``hyps[u][h]`` best first; ``sequence_scores[u]`` f64 [N] are HF's ``sequences_scores`` and
+    ``sequence_logprobs[u]`` f64 [N] the sums of the tokens' log-probabilities."""
+    sequence_scores = None
+    sequence_logprobs = None
+
+
+def check_beam_args(num_beams, num_return_sequences=None, length_penalty=1.0, early_stopping=False, vocab=None):
+    """(K, N, a _lib.BeamConfig) of checked beam-search arguments; ValueError naming the offender.  ``num_return_sequences=None`` is
+    1, as in HF; ``early_stopping`` is False, True or "never"; ``vocab`` (when known) must hold 2 * num_beams candidates."""
+    try:
+        k = operator.index(num_beams)
+    except TypeError:
+        raise ValueError(f"num_beams must be an integer in 1 .. {MAX_BEAMS}, got {num_beams!r}") from None
+    if not 1 <= k <= MAX_BEAMS:
+        raise ValueError(f"num_beams = {k} is outside 1 .. {MAX_BEAMS}")
+    if vocab is not None and 2 * k > int(vocab):
+        raise ValueError(f"num_beams = {k} needs 2 * num_beams <= the vocabulary's {int(vocab)} tokens")
+    try:
+        n = 1 if num_return_sequences is None else operator.index(num_return_sequences)
+    except TypeError:
+        raise ValueError(f"num_return_sequences must be an integer in 1 .. num_beams, got {num_return_sequences!r}") from None
+    if not 1 <= n <= k:
+        raise ValueError(f"num_return_sequences = {n} is outside 1 .. num_beams = {k}")
+    try:
+        p = float(length_penalty)
+    except (TypeError, ValueError):
+        raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}") from None
+    if p != p or p in (float("inf"), float("-inf")):
+        raise ValueError(f"length_penalty = {length_penalty} must be finite")
+    if isinstance(early_stopping, str):
+        early_stopping = early_stopping.lower()
+    if not isinstance(early_stopping, (bool, str)) or early_stopping not in EARLY_STOPPING:
+        raise ValueError(f"early_stopping = {early_stopping!r} is not False, True or 'never'")
+    return k, n, _lib.BeamConfig(C.sizeof(_lib.BeamConfig), k, p, EARLY_STOPPING[early_stopping], 0)
+
+
 def decoder_layer_keys(layer: int):
     """(name below ``wrapped_decoder.``, shape, init) of one SpeechT5DecoderLayer (HF modeling_speecht5.py:1070-1100)."""
     b = f"layers.{layer}."
@@ -444,19 +497,30 @@ class DecoderPool:
 
     ``sample`` (a _lib.SampleConfig, decoder.check_sample_args) makes it the sampling pool: items are admitted through
     loco_decoder_pool_admit_samples -- the hypotheses of one utterance that fit the free slots together, the rest later -- and stepped
-    through loco_decoder_pool_step_sample; scores are the model's log P of the token each step appended."""
+    through loco_decoder_pool_step_sample; scores are the model's log P of the token each step appended.
+
+    ``beam`` (a _lib.BeamConfig, decoder.check_beam_args) makes it the beam pool: an item is one utterance and takes a group of
+    ``num_beams`` slots (group g = slots g K .. g K + K - 1) through loco_decoder_pool_admit_beams, the pool is stepped through
+    loco_decoder_pool_step_beam and ``collect`` yields, per finished group, the group's list of hypotheses, best first."""
 
     def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False,
-                 return_scores: bool = False, sample=None):
+                 return_scores: bool = False, sample=None, beam=None, trace: bool = False):
         self.enc, self.lib = encoder, encoder._lib
         self.sample = sample
+        self.beam = beam
+        self.K = int(beam.num_beams) if beam is not None else 1
+        self.trace = bool(trace) and beam is not None  # collect() then appends the log-probabilities [steps, K, V] every step chose from
+        assert beam is None or (sample is None and not return_logits and int(slots) >= self.K)
         self.slots, self.T_cap, self.S_max = int(slots), int(T_cap), int(S_max)
         self.device = device
         self.poll_steps = int(poll_steps)
         self.return_logits = return_logits
         self.return_scores = return_scores  # collect() then yields 4-tuples: (..., log P of every generated token [len - 1])
         self.vocab = encoder._decoder_vocab
-        need = int(self.lib.loco_decoder_pool_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max))
+        if beam is not None:
+            need = int(self.lib.loco_decoder_beam_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max, self.K))
+        else:
+            need = int(self.lib.loco_decoder_pool_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max))
         self.workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
         self._shape = (self.slots, self.T_cap, self.S_max)
         # the limits are the library's: with need == 0 the call below names the one that was crossed
@@ -468,6 +532,12 @@ class DecoderPool:
         self.waiting = []
         self._rounds = []                   # (first step, logits [k, slots, V]) of the rounds an open utterance may still need
         self._score_rounds = []             # (first step, log-probabilities [k, slots]) likewise
+        self._trace_rounds = []             # (first step, log-probabilities [k, slots, V]) of a beam pool that traces
+        if beam is not None:
+            K, S = self.K, self.S_max
+            self._fin = dict(count=torch.zeros(1, dtype=torch.int32).pin_memory(), tokens=torch.zeros((K, S), dtype=torch.int32).pin_memory(),
+                             lengths=torch.zeros(K, dtype=torch.int32).pin_memory(), scores=torch.zeros(K, dtype=torch.float64).pin_memory(),
+                             sums=torch.zeros(K, dtype=torch.float64).pin_memory(), tlp=torch.zeros((K, S), dtype=torch.float32).pin_memory())
 
     def _ws(self):
         return _ptr(self.workspace)
@@ -515,6 +585,75 @@ class DecoderPool:
         for r, it in zip(slot_ids, flat):
             self.entries[r] = (it, self.steps)
 
+    def admit_beams(self, groups, items):
+        """Clips of ONE encoder output, consecutive in it, into the given free groups (group g = slots g K .. g K + K - 1)."""
+        n, first, K = len(items), items[0], self.K
+        assert all(it.enc_out is first.enc_out and it.clip == first.clip + i for i, it in enumerate(items))
+        i32 = lambda vs: (C.c_int32 * len(vs))(*vs)  # noqa: E731
+        out = first.enc_out
+        frames = first.frames[first.clip:] if first.frames is not None else None
+        _lib.check(self.lib.loco_decoder_pool_admit_beams(
+            self.enc._handle, *self._shape, C.byref(self.beam), n, i32(groups), _ptr(out[first.clip]), out.stride(0), i32([it.rows for it in items]),
+            _ptr(frames), i32([it.cap for it in items]), self._ws(), self.workspace.numel(), self._stream()), "loco_decoder_pool_admit_beams")
+        for g, it in zip(groups, items):
+            for r in range(g * K, g * K + K):
+                self.entries[r] = (it, self.steps)
+
+    def _fill_beams(self):
+        K = self.K
+        free = [g for g in range(self.slots // K) if self.entries[g * K] is None]
+        while free and self.waiting:
+            run = [self.waiting[0]]
+            while len(run) < len(free) and len(run) < len(self.waiting) and self.waiting[len(run)].enc_out is run[0].enc_out \
+                    and self.waiting[len(run)].clip == run[0].clip + len(run):
+                run.append(self.waiting[len(run)])
+            self.admit_beams(free[:len(run)], run)
+            del self.waiting[:len(run)], free[:len(run)]
+
+    def _collect_beams(self):
+        """Finished groups since the last call: [(key, hypotheses, scores f64 [n], sums of log-probabilities f64 [n], per-token
+        log-probabilities [n] of f32 [len - 1], trace or None)], the n <= K entries of the group's list, best first."""
+        status, lengths = self.poll()
+        K, out = self.K, []
+        stream = torch.cuda.current_stream(self.device)
+        for g in range(self.slots // K):
+            if self.entries[g * K] is None or status[g * K] != 2:
+                continue
+            f = self._fin
+            _lib.check(self.lib.loco_decoder_pool_read_beams(self.enc._handle, *self._shape, g, _ptr(f["count"]), _ptr(f["tokens"]), _ptr(f["lengths"]),
+                                                             _ptr(f["scores"]), _ptr(f["sums"]), _ptr(f["tlp"]), self._ws(), self.workspace.numel(),
+                                                             self._stream()), "loco_decoder_pool_read_beams")
+            stream.synchronize()
+            it, s0 = self.entries[g * K]
+            n = int(f["count"][0])
+            lens = f["lengths"][:n].tolist()
+            hyps = [f["tokens"][e, :lens[e]].to(torch.long) for e in range(n)]
+            tlps = [f["tlp"][e, 1:lens[e]].clone() for e in range(n)]
+            tr = None
+            if self.trace:
+                steps = lengths[g * K] - 1  # the steps the group took
+                parts = [t[max(s0 - a, 0):s0 + steps - a, g * K:g * K + K] for a, t in self._trace_rounds if a < s0 + steps and a + t.shape[0] > s0]
+                tr = torch.cat(parts).cpu()
+            out.append((it.key, hyps, f["scores"][:n].clone(), f["sums"][:n].clone(), tlps, tr))
+            for r in range(g * K, g * K + K):
+                self.entries[r] = None
+        if self.trace:
+            oldest = min([s0 for e in self.entries if e is not None for _, s0 in [e]], default=self.steps)
+            self._trace_rounds = [(a, t) for a, t in self._trace_rounds if a + t.shape[0] > oldest]
+        return out
+
+    def _round_beams(self):
+        k = max(1, min(self.poll_steps, self.bounds()[2]))
+        lp = torch.empty((k, self.slots, self.vocab), dtype=torch.float32, device=self.device) if self.trace else None
+        if self.trace:
+            self._trace_rounds.append((self.steps, lp))
+        for j in range(k):
+            max_pos, max_frames, _ = self.bounds()
+            _lib.check(self.lib.loco_decoder_pool_step_beam(self.enc._handle, *self._shape, max_pos, max_frames, None, _ptr(lp[j]) if self.trace else None,
+                                                            None, self._ws(), self.workspace.numel(), self._stream()), "loco_decoder_pool_step_beam")
+            self.steps += 1
+        return self.collect()
+
     def _siblings(self, at):
         """How many waiting items from ``at`` on are hypotheses of one utterance (one clip of one encoder output)."""
         w, n = self.waiting, 1
@@ -541,6 +680,8 @@ class DecoderPool:
     def _fill(self):
         if self.sample is not None:
             return self._fill_samples()
+        if self.beam is not None:
+            return self._fill_beams()
         free = [r for r in range(self.slots) if self.entries[r] is None]
         while free and self.waiting:
             run = [self.waiting[0]]
@@ -579,6 +720,8 @@ class DecoderPool:
     def collect(self):
         """Finished utterances since the last call: [(key, ids LongTensor, step logits [len - 1, V] or None)], with ``return_scores``
         [(key, ids, logits or None, log-probabilities [len - 1])]; their slots are free."""
+        if self.beam is not None:
+            return self._collect_beams()
         status, lengths = self.poll()
         done = [r for r in range(self.slots) if self.entries[r] is not None and status[r] == 2]
         for r in done:
@@ -612,6 +755,8 @@ class DecoderPool:
         self._fill()
         if not any(e is not None for e in self.entries):
             return []
+        if self.beam is not None:
+            return self._round_beams()
         k = max(1, min(self.poll_steps, self.bounds()[2]))
         want = self.return_logits or self.return_scores
         lg = torch.empty((k, self.slots, self.vocab), dtype=torch.float32, device=self.device) if want else None

@@ -10,7 +10,10 @@ slot to the next utterance (``generate_many``); the lines written are the same. 
 sampled transcripts of the utterance (``sample_many``: ``--temperature``, ``--top-k``, ``--top-p``, ``--seed``), each {"ids", "logprob",
 "avg_logprob"} (and "text"), sorted by "logprob", best first.  The line's other fields are then hypothesis 0: the greedy transcript only
 with ``--greedy-first``, a sampled one otherwise; ``--select mbr`` makes them the hypothesis of least expected edit distance to the
-list's others instead (metrics.mbr_select) and adds "mbr_risk" to every "nbest" entry.  ``--ref FILE`` (Kaldi ``utt_id text``; needs a
+list's others instead (metrics.mbr_select) and adds "mbr_risk" to every "nbest" entry.  ``--beams K`` (with ``--slots`` >= K) decodes by
+beam search instead (``beam_search_many``: ``--length-penalty``, ``--early-stopping false|true|never``): the line's own fields are the
+best beam, ``--nbest N`` (N <= K) then lists the N best beams in the search's order, each with "score" (HF's ``sequences_scores``) beside
+"logprob" and "avg_logprob", and ``--select mbr`` works on that list; the sampling flags do not go with it.  ``--ref FILE`` (Kaldi ``utt_id text``; needs a
 tokenizer on disk) or ``--ref-ids FILE`` (``utt_id id id ...``) adds "errors": {"cer", "wer"?, "sub", "del", "ins", "ref_len"} to every
 line that has a reference and writes the corpus ``%CER`` / ``%WER`` lines to stderr.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
@@ -43,7 +46,7 @@ import torch
 
 from . import metrics, synth
 from .audio_io import load_audio_16k, load_audio_channels_16k
-from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_sample_args
+from .decoder import EOS_TOKEN_ID, IGNORE_INDEX, PAD_TOKEN_ID, check_beam_args, check_sample_args
 from .extract import read_slurp_split
 from .feature_extractor import SpeechT5FeatureExtractorMI355X
 from .lm import read_key_text
@@ -278,13 +281,17 @@ def utterance_record(line, tok, width=0):
     return rec
 
 
-def nbest_records(hyps, sums, tok, risk=None):
+def nbest_records(hyps, sums, tok, risk=None, beam_scores=None):
     """One utterance's "nbest": its hypotheses (1-D id tensors) by log-probability ``sums[h]``, best first, ties by hypothesis index;
-    ``risk``: per hypothesis its "mbr_risk"."""
+    ``risk``: per hypothesis its "mbr_risk".  ``beam_scores`` (--beams): the hypotheses stay in the search's order, best score first,
+    and every entry carries its "score"."""
     recs = []
-    for h in sorted(range(len(hyps)), key=lambda h: (-sums[h], h)):
+    for h in (range(len(hyps)) if beam_scores is not None else sorted(range(len(hyps)), key=lambda h: (-sums[h], h))):
         row = hyps[h].tolist()
-        rec = {"ids": row, "logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)}
+        rec = {"ids": row}
+        if beam_scores is not None:
+            rec["score"] = beam_scores[h]
+        rec.update({"logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)})
         if tok is not None:
             rec["text"] = tok.decode(strip_special(row))
         if risk is not None:
@@ -353,6 +360,18 @@ def check_args(args, ap):
         ap.error("--select needs --nbest: it chooses among the hypotheses of the n-best list")
     if args.ref is not None and args.ref_ids is not None:
         ap.error("give --ref or --ref-ids, not both")
+    sampling = (("--temperature", args.temperature != ap.get_default("temperature")), ("--top-k", args.top_k != ap.get_default("top_k")),
+                ("--top-p", args.top_p != ap.get_default("top_p")), ("--seed", args.seed is not None), ("--greedy-first", args.greedy_first))
+    if args.beams is not None:
+        for flag, given in sampling:
+            if given:
+                ap.error(f"{flag} does not go with --beams: beam search draws nothing")
+        if args.long:
+            ap.error("--beams does not go with --long")
+    else:
+        for flag, v in (("--length-penalty", args.length_penalty), ("--early-stopping", args.early_stopping)):
+            if v is not None:
+                ap.error(f"{flag} needs --beams")
     if args.long:
         return
     for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
@@ -368,11 +387,26 @@ def check_args(args, ap):
         raise SystemExit("--nbest needs --slots: the hypotheses are rows of the decoder pool")
     if args.nbest < 0:
         raise SystemExit("--nbest must be >= 0")
-    if args.nbest:
+    if args.beams is not None:
+        if not args.slots:
+            raise SystemExit("--beams needs --slots: the beams are rows of the decoder pool")
+        try:
+            k = check_beam_args(args.beams, args.nbest or 1, 1.0 if args.length_penalty is None else args.length_penalty,
+                                beam_early_stopping(args.early_stopping))[0]
+        except ValueError as e:
+            raise SystemExit(f"--beams / --nbest / --length-penalty / --early-stopping: {e}")
+        if args.slots < k:
+            raise SystemExit(f"--slots {args.slots} is below --beams {k}: an utterance's beams are rows of one pool")
+    elif args.nbest:
         try:
             args.seed = int(check_sample_args(args.nbest, args.temperature, args.top_k, args.top_p, args.seed)[1].seed)
         except ValueError as e:
             raise SystemExit(f"--nbest / --temperature / --top-k / --top-p / --seed: {e}")
+
+
+def beam_early_stopping(flag):
+    """--early-stopping false | true | never (None = false) as ``beam_search_many`` takes it."""
+    return {None: False, "false": False, "true": True, "never": "never"}[flag]
 
 
 def check_long_args(args, ap):
@@ -496,13 +530,33 @@ def sampled_window(run, feats, first_utterance):
     return [per[b] for per, b in zip(hyps, pick)], [mine[b] for mine, b in zip(sums, pick)], lists
 
 
+def beam_window(run, feats):
+    """--beams: (rows, their log-probability sums, per utterance its "nbest" or None) of one window's batches through
+    ``beam_search_many``.  The row is the best beam or, with --select mbr, the one of least risk within the --nbest list."""
+    args = run.args
+    hyps = run.model.beam_search_many(feats, num_beams=args.beams, num_return_sequences=args.nbest or 1,
+                                      length_penalty=1.0 if args.length_penalty is None else args.length_penalty,
+                                      early_stopping=beam_early_stopping(args.early_stopping), max_length=args.max_length, slots=args.slots,
+                                      pack=args.pack)
+    sums, scores = [t.tolist() for t in hyps.sequence_logprobs], [t.tolist() for t in hyps.sequence_scores]
+    pick, risks = [0] * len(hyps), [None] * len(hyps)
+    if args.select == "mbr":
+        sel = metrics.mbr_select(hyps)
+        pick = sel.best.cpu().tolist()
+        risks = [r.cpu().tolist() for r in sel.risk]
+    lists = [nbest_records(per, mine, run.tok, risk, sc) for per, mine, risk, sc in zip(hyps, sums, risks, scores)] if args.nbest else None
+    return [per[b] for per, b in zip(hyps, pick)], [mine[b] for mine, b in zip(sums, pick)], lists
+
+
 def window_lines(run, items, starts):
     """The Lines of the batches that begin at ``starts``, loaded, encoded and decoded in the pool as one window."""
     args = run.args
     chunks = [items[b0:b0 + args.batch_size] for b0 in starts]
     feats = [load_batch(chunk, b0, run.processor, run.device) for chunk, b0 in zip(chunks, starts)]
     lists = None
-    if args.nbest:
+    if args.beams is not None:
+        rows, sums, lists = beam_window(run, feats)
+    elif args.nbest:
         rows, sums, lists = sampled_window(run, feats, starts[0])
     else:
         rows, sums = greedy_window(run, feats)
@@ -570,6 +624,10 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=None, help="with --nbest: the random numbers' seed (default: drawn from torch's generator)")
     ap.add_argument("--greedy-first", action="store_true", help="with --nbest: hypothesis 0 is the greedy transcript, so the line's own fields are what they "
                     "are without --nbest")
+    ap.add_argument("--beams", type=int, default=None, metavar="K", help="with --slots >= K: beam search with K beams (1 .. 16) instead of greedy search; "
+                    "--nbest N (N <= K) then lists the N best beams with their \"score\"")
+    ap.add_argument("--length-penalty", type=float, default=None, help="with --beams: a hypothesis scores its log-probability over length ** this (default 1)")
+    ap.add_argument("--early-stopping", choices=["false", "true", "never"], default=None, help="with --beams: HF's early_stopping (default false)")
     ap.add_argument("--scores", action="store_true", help="also write \"logprob\" (sum over the generated tokens) and \"avg_logprob\" (per generated token)")
     ap.add_argument("--timestamps", action="store_true", help="also write \"token_times\": [start_s, end_s] of every generated token (cross-attention + DTW)")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
