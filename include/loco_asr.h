@@ -796,6 +796,69 @@ int loco_decoder_pool_read_beams(loco_encoder* enc, int32_t slots, int32_t T_cap
                                  int32_t* lengths, double* scores, double* sum_logprobs, float* token_logprobs, const void* workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* ---- n-gram language model over the decoder's ids, and its shallow fusion into beam search ------------------------------------------
+ * The rule (csrc/ngram.hip, one definition of the chain; this project's own, pinned by a numpy restatement in tests/ngram_ref.py and
+ * NOT validated against KenLM/SRILM binaries).
+ * Symbols: predicted symbols are the decoder ids 0 .. V - 1; a predicted id 2 is the model's </s>.  Contexts may also hold BOS = V (the
+ * model's <s>), which stands for the start token at index 0 of a row and is never predicted.
+ * Model: a backoff model of order n, 1 <= n <= 8: grams g = (c_1 .. c_j, w), 0 <= j <= n - 1, each with logp[g] and bo[g] as float64
+ * natural logarithms; a gram that never serves as a context has bo = 0; every w in 0 .. V - 1 has a unigram.  The one gram that ends in
+ * BOS is the unigram (BOS): it carries bo of the context <s> and is never looked up as a prediction.
+ * Next-token log-probability of w after a row of cur tokens: h_1 .. h_m = the row's last m = min(n - 1, cur) symbols, then
+ *     acc = 0
+ *     for j = m, m - 1, ..., 0:
+ *         ctx = the last j symbols of h
+ *         if gram (ctx, w) exists:      return acc + logp[(ctx, w)]
+ *         if j > 0 and gram ctx exists: acc = acc + bo[ctx]
+ * with every addition in double, in exactly this order: the device and the restatement give the same bits from the same table.
+ * Fusion: step 1 of the beam rule becomes s = (run[k] + (double)lp[k][v]) + bonus[k][v], bonus[k][v] = weight * lm[k][v] + token_bonus,
+ * every operation rounded once (no contraction); steps 2 - 7 are unchanged, so run, the finished sums and the finished scores carry
+ * fused values, while the per-token log-probabilities stay the acoustic model's fp32 log P.  Nothing is kept per beam for the model: a
+ * hypothesis' log-probabilities under it are a function of its tokens, computed afterwards by loco_op_ngram_score.
+ * Limits: V <= 127, order <= 8, at most 2^26 grams -- a gram packs into one 64-bit key, 7 bits per symbol (oldest lowest) and its length
+ * in bits 56 .. 59.  The table is an open-addressing hash (linear probing, load factor <= 0.5, 24 bytes per slot) in device memory.
+ *   loco_ngram_create     HOST arrays: lengths i32 [n], symbols i32 [n][8] (oldest first, the predicted symbol last; entries beyond a
+ *               gram's length are not read), logp f64 [n], backoff f64 [n].  Builds the table on the current device (synchronous) and
+ *               returns the handle in *out.  LOCO_E_INVALID naming the gram index: a length outside 1 .. order, a symbol outside
+ *               0 .. V, BOS in the predicted position of a gram of two or more symbols or anywhere but position 0 of a context, a
+ *               duplicate gram, a logp or backoff that is not finite; naming the symbol: an id without a unigram; naming the field:
+ *               vocab, order or n outside the limits, or no host memory for the build (28 bytes per slot, two slots per gram at least).
+ *   loco_ngram_destroy    frees the table; a pool it is attached to must have been re-initialised (loco_decoder_pool_init) before.
+ *   loco_op_ngram_logprobs  tokens i32 (DEVICE), row r at tokens + r * ld, ld >= S; cur i32 [R] (DEVICE): the tokens row r holds,
+ *               1 .. S, index 0 the start token (read as BOS whatever its id).  out f64 [R, V] (DEVICE): the rule for every w.  One
+ *               wave per row; a row's output depends on that row's tokens and the table alone.  A row whose cur is outside 1 .. S, or
+ *               that holds an id outside 0 .. V - 1 among the symbols read, is NaN.  Asynchronous; no atomics, no allocation.
+ *   loco_op_ngram_score   teacher-forced: tokens i32 [total] (DEVICE) hold B sequences, sequence b = tokens[starts[b] .. starts[b] +
+ *               lens[b]) (starts i64 [B], lens i32 [B], DEVICE); out f64 [total]: out[starts[b] + i] = the rule for token i after
+ *               tokens 0 .. i - 1 (token 0 read as BOS), 0 at i = 0.  A sequence that does not lie inside [0, total) is not touched.
+ *   loco_op_beam_select_fused   loco_op_beam_select with bonus f64 [G K, V] (DEVICE) or NULL; NULL is loco_op_beam_select, bit for bit.
+ *   loco_decoder_beam_fusion_workspace_bytes   loco_decoder_beam_workspace_bytes plus the bonus region, which comes after every region
+ *               of it (all of which keep their offsets).
+ *   loco_decoder_pool_attach_ngram   after loco_decoder_pool_init and before the pool's first loco_decoder_pool_admit_beams: the beam
+ *               pool in `workspace` (at least loco_decoder_beam_fusion_workspace_bytes) fuses `lm` with `weight` and `token_bonus`.
+ *               Kept by the handle per workspace address, as the beam config is, until loco_decoder_pool_init on that address.
+ *               loco_decoder_pool_step_beam then launches the n-gram kernel on the pool's token rows before the select kernel; a pool
+ *               with nothing attached enqueues exactly what it always did.  LOCO_E_INVALID: a model whose vocab is not the decoder's
+ *               or whose table is on another device than the handle, a weight or token_bonus that is not finite; LOCO_E_STATE: a pool that has admitted groups or has a model attached. */
+typedef struct loco_ngram loco_ngram;
+int loco_ngram_create(int32_t vocab, int32_t order, int64_t n, const int32_t* lengths, const int32_t* symbols, const double* logp,
+                      const double* backoff, loco_ngram** out);
+void loco_ngram_destroy(loco_ngram* lm);
+int32_t loco_ngram_vocab(const loco_ngram* lm);
+int32_t loco_ngram_order(const loco_ngram* lm);
+int loco_op_ngram_logprobs(const loco_ngram* lm, const int32_t* tokens, int64_t ld, int32_t S, const int32_t* cur, int32_t R, double* out,
+                           void* stream);
+int loco_op_ngram_score(const loco_ngram* lm, const int32_t* tokens, int64_t total, const int64_t* starts, const int32_t* lens, int32_t B,
+                        double* out, void* stream);
+int loco_op_beam_select_fused(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
+                              int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                              float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
+                              double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
+                              int32_t* counts, int32_t* poll, const double* bonus, void* stream);
+size_t loco_decoder_beam_fusion_workspace_bytes(const loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, int32_t num_beams);
+int loco_decoder_pool_attach_ngram(loco_encoder* enc, int32_t slots, int32_t T_cap, int32_t S_max, const loco_ngram* lm, double weight,
+                                   double token_bonus, void* workspace, size_t workspace_bytes);
+
 /* ---- decoder scores: log-probabilities of a transcript's tokens, per-sequence sums, the labels= loss --------------------------------
  * loco_decoder_score turns logits (loco_decoder_forward's [B, S, V], or a block of step logits) into what a transcript is judged by.
  * Stateless: no handle, no workspace.  Asynchronous, reads no host memory, two launches on `stream`; it can be captured like a step.

@@ -170,6 +170,15 @@ SIGNATURES = {
                                                 C.POINTER(_i32), _vp, _sz, _vp]),
     "loco_decoder_pool_step_beam": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "loco_decoder_pool_read_beams": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "loco_ngram_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "loco_ngram_destroy": (None, [_vp]),
+    "loco_ngram_vocab": (_i32, [_vp]),
+    "loco_ngram_order": (_i32, [_vp]),
+    "loco_op_ngram_logprobs": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "loco_op_ngram_score": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "loco_op_beam_select_fused": (C.c_int, [_vp, _i64, _i32, _i32, _i32, C.POINTER(BeamConfig)] + [_vp] * 24),
+    "loco_decoder_beam_fusion_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "loco_decoder_pool_attach_ngram": (C.c_int, [_vp, _i32, _i32, _i32, _vp, C.c_double, C.c_double, _vp, _sz]),
     "loco_decoder_score": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),

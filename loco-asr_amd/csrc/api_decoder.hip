@@ -481,8 +481,21 @@ void pool_beam_forget(loco_encoder* e, const void* ws) {
     for (size_t i = 0; i < v.size(); ++i)
         if (v[i].first == ws) {
             v.erase(v.begin() + i);
-            return;
+            break;
         }
+    auto& f = e->pool_fusion;
+    for (size_t i = 0; i < f.size(); ++i)
+        if (f[i].ws == ws) {
+            f.erase(f.begin() + i);
+            break;
+        }
+}
+
+// the n-gram model attached to the beam pool in `ws` (null: none)
+const loco_encoder::PoolFusion* pool_fusion(const loco_encoder* e, const void* ws) {
+    for (const auto& it : e->pool_fusion)
+        if (it.ws == ws) return &it;
+    return nullptr;
 }
 
 // the greedy and sampling entry points on a beam pool
@@ -725,7 +738,7 @@ struct BeamPlan {
     PoolPlan pool;
     int K, groups;
     size_t off_shadow, off_fin_tok, off_fin_tlp, off_fin_score, off_fin_sum, off_fin_len, off_run, off_alive, off_tlp, off_parent, off_count, off_den,
-        off_unsat, off_fin_n, off_tok_shadow, off_tlp_shadow, off_lp, total;
+        off_unsat, off_fin_n, off_tok_shadow, off_tlp_shadow, off_lp, total, off_bonus, total_fused;
 };
 
 void make_beam_plan(int layers, int slots, int T, int S, int K, BeamPlan& b) {
@@ -756,6 +769,8 @@ void make_beam_plan(int layers, int slots, int T, int S, int K, BeamPlan& b) {
     b.off_tlp_shadow = take((size_t)slots * S * f);
     b.off_lp = take((size_t)slots * 128 * f);  // the logits region's shape
     b.total = o;
+    b.off_bonus = take((size_t)slots * 128 * d);  // a pool with an n-gram model attached: the candidates' bonus, after everything else
+    b.total_fused = o;
 }
 
 BeamState beam_state(const BeamPlan& b, char* ws) {
@@ -814,6 +829,36 @@ size_t loco_decoder_beam_workspace_bytes(const loco_encoder* e, int32_t slots, i
     BeamPlan b;
     make_beam_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, num_beams, b);
     return b.total;
+}
+
+size_t loco_decoder_beam_fusion_workspace_bytes(const loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, int32_t num_beams) {
+    if (!loco_decoder_beam_workspace_bytes(e, slots, T_cap, S_max, num_beams)) return 0;
+    BeamPlan b;
+    make_beam_plan(decoder_layers_loaded(e, nullptr), slots, T_cap, S_max, num_beams, b);
+    return b.total_fused;
+}
+
+int loco_decoder_pool_attach_ngram(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, const loco_ngram* lm, double weight,
+                                   double token_bonus, void* workspace, size_t workspace_bytes) {
+    const char* fn = "loco_decoder_pool_attach_ngram";
+    LOCO_TRY(dec_handle_check(e, fn));
+    BeamPlan bp;
+    LOCO_TRY(beam_pool_check(e, fn, slots, T_cap, S_max, 1, workspace, workspace_bytes, bp));
+    if (workspace_bytes < bp.total_fused)
+        return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes (loco_decoder_beam_fusion_workspace_bytes)", fn, workspace_bytes, bp.total_fused);
+    if (!lm) return fail(LOCO_E_INVALID, "%s: null model", fn);
+    if (lm->device != e->device)
+        return fail(LOCO_E_INVALID, "%s: the model's table is on device %d, the decoder on device %d", fn, lm->device, e->device);
+    if (lm->table.V != e->dec.vocab)
+        return fail(LOCO_E_INVALID, "%s: the model's vocab = %d is not the decoder's %d", fn, lm->table.V, e->dec.vocab);
+    if (!std::isfinite(weight)) return fail(LOCO_E_INVALID, "%s: weight = %g must be finite", fn, weight);
+    if (!std::isfinite(token_bonus)) return fail(LOCO_E_INVALID, "%s: token_bonus = %g must be finite", fn, token_bonus);
+    if (pool_beam_config(e, workspace))
+        return fail(LOCO_E_STATE, "%s: the pool has admitted beam groups; attach after loco_decoder_pool_init and before the first admission", fn);
+    if (pool_sampled_slots(e, workspace)) return fail(LOCO_E_STATE, "%s: the pool holds slots admitted to sample", fn);
+    if (pool_fusion(e, workspace)) return fail(LOCO_E_STATE, "%s: the pool has a model attached; loco_decoder_pool_init comes first", fn);
+    e->pool_fusion.push_back({workspace, lm, weight, token_bonus});
+    return LOCO_OK;
 }
 
 int loco_decoder_pool_admit_beams(loco_encoder* e, int32_t slots, int32_t T_cap, int32_t S_max, const loco_beam_config* config, int32_t n,
@@ -898,8 +943,17 @@ int loco_decoder_pool_step_beam(loco_encoder* e, int32_t slots, int32_t T_cap, i
     const int V = e->dec.vocab;
     float* logits = step_logits ? step_logits : reinterpret_cast<float*>(ws + bp.pool.off_logits);
     float* lp = step_logprobs ? step_logprobs : reinterpret_cast<float*>(ws + bp.off_lp);
+    const loco_encoder::PoolFusion* fusion = pool_fusion(e, workspace);
+    if (fusion && workspace_bytes < bp.total_fused)
+        return fail(LOCO_E_WORKSPACE, "%s: workspace %zu < %zu bytes (loco_decoder_beam_fusion_workspace_bytes)", fn, workspace_bytes, bp.total_fused);
     LOCO_TRY(pool_step_walk(e, bp.pool, ws, st, max_pos, max_frames, logits, s));
-    HIP_TRY(launch_beam_select(st, bs, rule, logits, V, V, kDecEosToken, lp, s));
+    double* bonus = nullptr;
+    if (fusion) {
+        // weight * log P_lm(v | the slot's tokens) + token_bonus for every slot the embed kernel took as live (kv_row + 1 tokens)
+        bonus = reinterpret_cast<double*>(ws + bp.off_bonus);
+        HIP_TRY(launch_ngram_logprobs(fusion->lm->table, st.tokens, S_max, S_max, st.kv_row, 1, slots, true, fusion->weight, fusion->token_bonus, bonus, s));
+    }
+    HIP_TRY(launch_beam_select(st, bs, rule, logits, V, V, kDecEosToken, lp, s, bonus));
     if (step_parents) HIP_TRY(hipMemcpyAsync(step_parents, bs.parent, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     // rows 0 .. pos of the self cache, the token rows and their log-probabilities follow the parents
     HIP_TRY(launch_beam_reorder(ws + bp.pool.off_self, ws + bp.off_shadow, bp.pool.L, slots, S_max, 2 * kHidden, bs.parent, bs.count, st.status, rule.K,
@@ -935,12 +989,12 @@ int loco_decoder_pool_read_beams(loco_encoder* e, int32_t slots, int32_t T_cap, 
     return LOCO_OK;
 }
 
-int loco_op_beam_select(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
-                        int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
-                        float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
-                        double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
-                        int32_t* counts, int32_t* poll, void* stream) {
-    const char* fn = "loco_op_beam_select";
+namespace {
+int op_beam_select(const char* fn, const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config,
+                   const double* den, int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                   float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores, double* fin_sums,
+                   int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents, int32_t* counts, int32_t* poll,
+                   const double* bonus, void* stream) {
     BeamRule rule;
     LOCO_TRY(beam_config_check(config, fn, V, rule));
     if (!logits || !den || !status || !pos || !cap || !cur || !cnt || !lengths || !tokens || !token_logprobs || !run || !alive || !unsat || !fin_count ||
@@ -959,8 +1013,29 @@ int loco_op_beam_select(const float* logits, int64_t ld, int32_t G, int32_t V, i
     b.run = run, b.fin_score = fin_scores, b.fin_sum = fin_sums, b.den = den, b.tlp = token_logprobs, b.fin_tlp = fin_logprobs;
     b.alive = alive, b.parent = parents, b.count = counts, b.unsat = unsat, b.fin_n = fin_count, b.fin_len = fin_lengths, b.fin_tok = fin_tokens;
     b.groups = G, b.den_n = S_max;
-    HIP_TRY(launch_beam_select(p, b, rule, logits, (long)ld, V, kDecEosToken, logprobs, (hipStream_t)stream));
+    HIP_TRY(launch_beam_select(p, b, rule, logits, (long)ld, V, kDecEosToken, logprobs, (hipStream_t)stream, bonus));
     return LOCO_OK;
+}
+}  // namespace
+
+int loco_op_beam_select(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
+                        int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                        float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
+                        double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
+                        int32_t* counts, int32_t* poll, void* stream) {
+    return op_beam_select("loco_op_beam_select", logits, ld, G, V, S_max, config, den, status, pos, cap, cur, cnt, lengths, tokens, token_logprobs, run,
+                          alive, unsat, fin_count, fin_scores, fin_sums, fin_lengths, fin_tokens, fin_logprobs, logprobs, parents, counts, poll, nullptr,
+                          stream);
+}
+
+int loco_op_beam_select_fused(const float* logits, int64_t ld, int32_t G, int32_t V, int32_t S_max, const loco_beam_config* config, const double* den,
+                              int32_t* status, int32_t* pos, const int32_t* cap, int32_t* cur, int32_t* cnt, int32_t* lengths, int32_t* tokens,
+                              float* token_logprobs, double* run, int32_t* alive, int32_t* unsat, int32_t* fin_count, double* fin_scores,
+                              double* fin_sums, int32_t* fin_lengths, int32_t* fin_tokens, float* fin_logprobs, float* logprobs, int32_t* parents,
+                              int32_t* counts, int32_t* poll, const double* bonus, void* stream) {
+    return op_beam_select("loco_op_beam_select_fused", logits, ld, G, V, S_max, config, den, status, pos, cap, cur, cnt, lengths, tokens, token_logprobs,
+                          run, alive, unsat, fin_count, fin_scores, fin_sums, fin_lengths, fin_tokens, fin_logprobs, logprobs, parents, counts, poll,
+                          bonus, stream);
 }
 
 int loco_op_beam_reorder(void* buf, void* shadow, int32_t layers, int32_t slots, int32_t S_max, int64_t width, const int32_t* parents,

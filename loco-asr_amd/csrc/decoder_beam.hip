@@ -2,6 +2,7 @@
 // finished-hypothesis lists and the reordering of a group's rows by parent beam, on the device.
 //   pool_admit_beams_kernel  pool_admit_kernel for groups of K slots: beam 0 alive with score 0, the list empty
 //   beam_select_kernel       one wave per group: log-softmax of the K rows, the 2K best candidates, the list, the next beams
+//                            (<true>: with a per-candidate bonus, the n-gram fusion; ngram.hip computes it)
 //   beam_poll_kernel         poll[0] = slots open (the select kernel's groups run in separate workgroups)
 //   beam_copy_kernel         rows 0 .. count - 1 of a slot from its parent's into the shadow, then from the shadow back
 // The rule is HF's _beam_search with flags in place of its -1e9 sentinels and scores carried in double (include/loco_asr.h states it).
@@ -62,8 +63,11 @@ __global__ __launch_bounds__(64) void pool_admit_beams_kernel(PoolState p, BeamS
     if (i == 0) p.poll[0] = __popcll(open);
 }
 
+// FUSED: candidate (k, v) scores (run[k] + lp[k][v]) + bonus[k][v], bonus f64 [slots, V] (the n-gram fusion of include/loco_asr.h); the
+// sum is two roundings, never a contraction.  <false> never reads bonus: the rule's arithmetic as it was.
+template <bool FUSED>
 __global__ __launch_bounds__(64) void beam_select_kernel(PoolState p, BeamState b, BeamRule rule, const float* __restrict__ logits, long ld, int V,
-                                                         int eos, float* logprobs) {
+                                                         int eos, float* logprobs, const double* __restrict__ bonus) {
     __shared__ double run_s[kBeamMax], cand_s[2 * kBeamMax], m_s[2 * kBeamMax];
     __shared__ int alive_s[kBeamMax], cnt_s[kBeamMax], cand_i[2 * kBeamMax], m_src[2 * kBeamMax], next_c[kBeamMax], plan[4];
     const int lane = threadIdx.x, g = blockIdx.x;
@@ -103,7 +107,8 @@ __global__ __launch_bounds__(64) void beam_select_kernel(PoolState p, BeamState 
             const float* row = logprobs + (long)(base + k) * V;
             const double rk = run_s[k];
             for (int v = lane; v < V; v += 64) {
-                const double s = rk + (double)row[v];
+                double s = rk + (double)row[v];
+                if (FUSED) s = __dadd_rn(s, bonus[(long)(base + k) * V + v]);
                 const int c = k * V + v;
                 if (j > 0 && !beam_before(last_s, last_i, s, c)) continue;
                 if (bi == INT_MAX || beam_before(s, c, bs, bi)) bs = s, bi = c;
@@ -252,11 +257,14 @@ hipError_t launch_pool_admit_beams(const PoolState& p, const BeamState& b, const
 }
 
 hipError_t launch_beam_select(const PoolState& p, const BeamState& b, const BeamRule& rule, const float* logits, long ld, int V, int eos,
-                              float* logprobs, hipStream_t s) {
+                              float* logprobs, hipStream_t s, const double* bonus) {
     if (p.slots <= 0 || rule.K < 1 || rule.K > kBeamMax || b.groups < 1 || (long)b.groups * rule.K > p.slots || V < 2 * rule.K || V > (1 << 20) ||
         ld < V || p.S_max < 2 || b.den_n < 2 || !logits || !logprobs || (p.poll && p.slots > 64))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(beam_select_kernel, dim3(b.groups), dim3(64), 0, s, p, b, rule, logits, ld, V, eos, logprobs);
+    if (bonus)
+        hipLaunchKernelGGL(beam_select_kernel<true>, dim3(b.groups), dim3(64), 0, s, p, b, rule, logits, ld, V, eos, logprobs, bonus);
+    else
+        hipLaunchKernelGGL(beam_select_kernel<false>, dim3(b.groups), dim3(64), 0, s, p, b, rule, logits, ld, V, eos, logprobs, bonus);
     if (p.poll) hipLaunchKernelGGL(beam_poll_kernel, dim3(1), dim3(64), 0, s, p);
     return hipGetLastError();
 }

@@ -127,6 +127,15 @@ constexpr float kRangeLo = 0.015625f;  // 2^-6: a plane tensor whose LARGEST ele
 
 }  // namespace loco::host
 
+// An n-gram language model (loco_ngram_create, ngram_api.hip): the device table and what it was built from
+struct loco_ngram {
+    loco::NgramTable table{};
+    uint64_t* keys = nullptr;  // device, table.mask + 1 slots
+    double* vals = nullptr;    // device, [slots][2]
+    int64_t grams = 0;
+    int device = 0;
+};
+
 struct loco_encoder {
     loco_config cfg;
     int device = 0;
@@ -167,6 +176,13 @@ struct loco_encoder {
     std::vector<std::pair<const void*, unsigned long long>> pool_sampled;
     // decoder pools whose slots are beam groups: (workspace, the config of loco_decoder_pool_admit_beams), kept like pool_sampled
     std::vector<std::pair<const void*, loco_beam_config>> pool_beam;
+    // beam pools with an n-gram model attached (loco_decoder_pool_attach_ngram): kept per workspace address, forgotten with the config
+    struct PoolFusion {
+        const void* ws;
+        const loco_ngram* lm;
+        double weight, token_bonus;
+    };
+    std::vector<PoolFusion> pool_fusion;
     std::map<std::string, std::vector<int64_t>> dec_shapes;  // shapes of the decoder tensors as loaded (the vocabulary is theirs)
     // concurrency inside one forward: a batch may run as two half-batches on two streams (loco_set_streams).  The side stream and
     // its events are created on first use under side_mu; forwards in flight together serialise their second halves on it.

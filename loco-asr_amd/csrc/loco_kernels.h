@@ -431,13 +431,47 @@ struct BeamState {
 hipError_t launch_pool_admit_beams(const PoolState& p, const BeamState& b, const PoolAdmitSamples& a, const int32_t* frames, int start, hipStream_t s);
 // One step of the rule for every group whose first slot is open with kv_row >= 0 (the row the step wrote); logprobs f32 [slots, V] =
 // the log-softmax rows the rule used.  Rows of logits at logits + r * ld.  Ends with poll[0] = slots open.
+// bonus (optional) f64 [slots, V]: candidate (k, v) scores (run[k] + lp[k][v]) + bonus[k][v]; null is the rule without it, the same code
 hipError_t launch_beam_select(const PoolState& p, const BeamState& b, const BeamRule& rule, const float* logits, long ld, int V, int eos,
-                              float* logprobs, hipStream_t s);
+                              float* logprobs, hipStream_t s, const double* bonus = nullptr);
 // buf [layers][slots][S][W] of 4-byte words: rows 0 .. count[r] - 1 of slot r := those of slot parent[r] (clamped into r's group of K
 // slots), through shadow (same shape), for every r whose parent differs and, with open (optional, [slots]), whose open[r] is
 // kPoolOpen; max_count bounds the launches, not the copies
 hipError_t launch_beam_reorder(void* buf, void* shadow, int layers, int slots, int S, long W, const int32_t* parent, const int32_t* count,
                                const int32_t* open, int K, int max_count, hipStream_t s);
+
+// ---- n-gram language model over the decoder's ids (ngram.hip; the rule: include/loco_asr.h) ----
+constexpr int kNgramMaxOrder = 8, kNgramMaxVocab = 127;
+constexpr long kNgramMaxGrams = 1L << 26;
+// A gram of `len` symbols (oldest first, the predicted one last; a symbol is 0 .. V, V = <s>) as one key: 7 bits per symbol from bit 0
+// up, len in bits 56 .. 59.  Never 0, the mark of an empty slot.
+__host__ __device__ inline uint64_t ngram_key(uint64_t symbols, int len) { return symbols | ((uint64_t)len << 56); }
+// where a key's probe sequence starts (splitmix64's finaliser); host and device share it
+__host__ __device__ inline uint64_t ngram_mix(uint64_t x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+// The table on the device: open addressing with linear probing, mask + 1 slots (a power of two, at least twice the grams);
+// vals[slot] = (logp, backoff).  No key's probe sequence is longer than max_probe slots, so a lookup ends whatever memory holds.
+struct NgramTable {
+    const uint64_t* keys;
+    const double* vals;  // [mask + 1][2]
+    uint32_t mask;
+    int max_probe, V, order;
+};
+// out f64 [R, V]: row r = log P(v | the last min(order - 1, n) symbols of tokens[r * ld ..]), n = cur[r] + cur_offset the tokens the row
+// holds (index 0 counts as <s>).  fuse: out = weight * log P + token_bonus (each rounded once) and a row whose n is outside 1 .. S is
+// skipped; otherwise such a row, and a row with a context token outside 0 .. V - 1, is NaN.
+hipError_t launch_ngram_logprobs(const NgramTable& t, const int32_t* tokens, long ld, int S, const int32_t* cur, int cur_offset, int R, bool fuse,
+                                 double weight, double token_bonus, double* out, hipStream_t s);
+// out f64 [total]: sequence b = tokens[starts[b] .. starts[b] + lens[b]); out[starts[b] + i] = log P(token i | tokens 0 .. i - 1), 0 at i = 0;
+// a sequence that does not lie inside [0, total) is skipped
+hipError_t launch_ngram_score(const NgramTable& t, const int32_t* tokens, const int64_t* starts, const int32_t* lens, int B, int64_t total,
+                              double* out, hipStream_t s);
 
 // ---- decoder scores (decoder_score.hip) ----
 // logprob[m] = log_softmax(logits[m, :V])[target] with target = targets[m], or the row's argmax (decoder_common.h's rule) when targets is

@@ -189,13 +189,39 @@ class BeamSearchOutput:
     sequences_scores: Optional[torch.Tensor] = None
     token_logprobs: Optional[torch.Tensor] = None
     sequence_logprobs: Optional[torch.Tensor] = None
+    lm_logprobs: Optional[torch.Tensor] = None  # with lm=: float64 [B * N], the hypotheses' n-gram log-probabilities
 
 
 class BeamHypotheses(list):
     """``beam_search_many``'s hypotheses, ``hyps[u][h]`` best first; ``sequence_scores[u]`` f64 [N] are HF's ``sequences_scores`` and
-    ``sequence_logprobs[u]`` f64 [N] the sums of the tokens' log-probabilities."""
+    ``sequence_logprobs[u]`` f64 [N] the sums of the tokens' log-probabilities.  With ``lm=`` both are the FUSED values (every token's
+    log P plus ``lm_weight`` * its n-gram log P plus ``lm_bonus``) and ``lm_logprobs[u]`` f64 [N] are the hypotheses' n-gram
+    log-probabilities; without, ``lm_logprobs`` is None."""
     sequence_scores = None
     sequence_logprobs = None
+    lm_logprobs = None
+
+
+def check_fusion_args(lm, lm_weight=0.0, lm_bonus=0.0, vocab=None):
+    """None, or (lm, weight, bonus) of checked shallow-fusion arguments; ValueError naming the offender."""
+    if lm is None:
+        if float(lm_weight) != 0.0 or float(lm_bonus) != 0.0:
+            raise ValueError("lm_weight / lm_bonus need lm=, an ngram.NgramLM")
+        return None
+    if not (hasattr(lm, "vocab") and hasattr(lm, "next_logprobs")):
+        raise ValueError(f"lm must be an ngram.NgramLM, got {type(lm).__name__}")
+    if vocab is not None and int(lm.vocab) != int(vocab):
+        raise ValueError(f"lm: the model's vocab = {int(lm.vocab)} is not the decoder's {int(vocab)}")
+    out = []
+    for name, v in (("lm_weight", lm_weight), ("lm_bonus", lm_bonus)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a finite number, got {v!r}") from None
+        if f != f or f in (float("inf"), float("-inf")):
+            raise ValueError(f"{name} = {v} must be finite")
+        out.append(f)
+    return lm, out[0], out[1]
 
 
 def check_beam_args(num_beams, num_return_sequences=None, length_penalty=1.0, early_stopping=False, vocab=None):
@@ -501,11 +527,15 @@ class DecoderPool:
 
     ``beam`` (a _lib.BeamConfig, decoder.check_beam_args) makes it the beam pool: an item is one utterance and takes a group of
     ``num_beams`` slots (group g = slots g K .. g K + K - 1) through loco_decoder_pool_admit_beams, the pool is stepped through
-    loco_decoder_pool_step_beam and ``collect`` yields, per finished group, the group's list of hypotheses, best first."""
+    loco_decoder_pool_step_beam and ``collect`` yields, per finished group, the group's list of hypotheses, best first.  ``fusion``
+    (an ngram.NgramLM on the pool's device, weight, token_bonus) attaches the n-gram model to the beam pool: every step then scores
+    its candidates with ``weight * log P_lm + token_bonus`` added (loco_decoder_pool_attach_ngram); the pool keeps the model alive."""
 
     def __init__(self, encoder, slots: int, T_cap: int, S_max: int, device, poll_steps: int = 8, return_logits: bool = False,
-                 return_scores: bool = False, sample=None, beam=None, trace: bool = False):
+                 return_scores: bool = False, sample=None, beam=None, trace: bool = False, fusion=None):
         self.enc, self.lib = encoder, encoder._lib
+        self.fusion = fusion  # (an ngram.NgramLM on the device, weight, token_bonus) of a beam pool, or None
+        assert fusion is None or beam is not None
         self.sample = sample
         self.beam = beam
         self.K = int(beam.num_beams) if beam is not None else 1
@@ -517,7 +547,9 @@ class DecoderPool:
         self.return_logits = return_logits
         self.return_scores = return_scores  # collect() then yields 4-tuples: (..., log P of every generated token [len - 1])
         self.vocab = encoder._decoder_vocab
-        if beam is not None:
+        if fusion is not None:
+            need = int(self.lib.loco_decoder_beam_fusion_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max, self.K))
+        elif beam is not None:
             need = int(self.lib.loco_decoder_beam_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max, self.K))
         else:
             need = int(self.lib.loco_decoder_pool_workspace_bytes(encoder._handle, self.slots, self.T_cap, self.S_max))
@@ -525,6 +557,10 @@ class DecoderPool:
         self._shape = (self.slots, self.T_cap, self.S_max)
         # the limits are the library's: with need == 0 the call below names the one that was crossed
         _lib.check(self.lib.loco_decoder_pool_init(encoder._handle, *self._shape, self._ws(), need, self._stream()), "loco_decoder_pool_init")
+        if fusion is not None:  # before the first admission; the handle keeps it for this workspace until the next init
+            lm, weight, bonus = fusion
+            _lib.check(self.lib.loco_decoder_pool_attach_ngram(encoder._handle, *self._shape, lm.handle, float(weight), float(bonus), self._ws(), need),
+                       "loco_decoder_pool_attach_ngram")
         self.block = torch.zeros(4 + 2 * self.slots, dtype=torch.int32).pin_memory()
         self.tokens = torch.zeros((self.slots, self.S_max), dtype=torch.int32).pin_memory()
         self.entries = [None] * self.slots  # per slot: (item, step count at admission), None = free on the host's books

@@ -334,11 +334,12 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         return batches, total, caps
 
     def _decode_corpus(self, batches, caps, slots, pack, return_logits, return_scores, copies=1, sample=None, greedy_first=False, first_utterance=0,
-                       beam=None, trace=False):
+                       beam=None, trace=False, fusion=None):
         """The walk ``generate_many`` and ``sample_many`` share over checked arguments: encode ``pack`` batches at a time, decode in one
         pool.  {utterance * copies + hypothesis: [ids, logits or None, scores when asked for]}; ``sample`` (a _lib.SampleConfig) makes
         the pool draw ``copies`` hypotheses per utterance, of which hypothesis 0 is the argmax path with ``greedy_first``.  ``beam`` (a
-        _lib.BeamConfig) makes it the beam pool: {utterance: what DecoderPool.collect yields per group}."""
+        _lib.BeamConfig) makes it the beam pool: {utterance: what DecoderPool.collect yields per group}; ``fusion`` (lm, weight, bonus)
+        attaches an n-gram model to that pool."""
         total = len(caps)
         enc = self.speecht5.encoder
         lib = enc._lib
@@ -357,7 +358,8 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
                     if pool is None:  # after the first forward: the handle exists and carries the decoder's weights
                         rows = total * copies * (int(beam.num_beams) if beam is not None else 1)
                         pool = dec.DecoderPool(enc, min(int(slots), rows), T_cap, max(caps), device,
-                                               return_logits=return_logits, return_scores=return_scores, sample=sample, beam=beam, trace=trace)
+                                               return_logits=return_logits, return_scores=return_scores, sample=sample, beam=beam, trace=trace,
+                                               fusion=(fusion[0].to(device),) + tuple(fusion[1:]) if fusion is not None else None)
                     items = []
                     for b0, nb, t in spans:
                         for c in range(b0, b0 + nb):
@@ -413,7 +415,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
     @torch.no_grad()
     def beam_search_many(self, batches, num_beams: int = 4, num_return_sequences: Optional[int] = None, length_penalty: float = 1.0,
                          early_stopping=False, max_length=None, max_new_tokens: Optional[int] = None, slots: int = 64, pack: int = 8,
-                         return_scores: bool = False, return_step_logprobs: bool = False):
+                         return_scores: bool = False, return_step_logprobs: bool = False, lm=None, lm_weight: float = 0.0, lm_bonus: float = 0.0):
         """Beam search over a corpus, HF's ``generate(num_beams=K, num_return_sequences=N, length_penalty=, early_stopping=)``:
         ``batches``, ``max_length`` (an int or one per utterance), ``slots`` and ``pack`` are ``generate_many``'s.  An utterance takes a
         group of ``num_beams`` rows of the slot pool (``slots >= num_beams``; ``slots // num_beams`` utterances decode together); the
@@ -425,17 +427,29 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         ``hyps.sequence_scores[u]`` float64 [N] (HF's ``sequences_scores``) and ``hyps.sequence_logprobs[u]`` float64 [N].
         ``return_scores=True``: (hyps, scores) with ``scores[u][h]`` float32 [len - 1], the log-probability of every token.
         ``return_step_logprobs=True``: also ``hyps.step_logprobs[u]`` float32 [steps, num_beams, vocab] (host), the log-softmax rows
-        every step of the utterance chose from -- what a restatement of the rule needs to replay the search."""
+        every step of the utterance chose from -- what a restatement of the rule needs to replay the search.
+
+        Shallow fusion: ``lm`` (an ngram.NgramLM over the decoder's ids; None = the search as it always was) adds
+        ``lm_weight * log P_lm(token | hypothesis so far) + lm_bonus`` to every candidate's score on the device (include/loco_asr.h
+        states the rule).  ``sequence_scores`` and ``sequence_logprobs`` are then the FUSED values, ``scores`` / ``step_logprobs`` stay
+        the acoustic model's, and ``hyps.lm_logprobs[u]`` float64 [N] holds every hypothesis' n-gram log-probability, so that
+        ``sequence_logprobs = sum(scores) + lm_weight * lm_logprobs + lm_bonus * (len - 1)`` up to rounding."""
         self._require_decoder("beam_search_many()")
         k, n, config = dec.check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping,
                                            vocab=self.speecht5.encoder._decoder_vocab)
+        fusion = dec.check_fusion_args(lm, lm_weight, lm_bonus, vocab=self.speecht5.encoder._decoder_vocab)
         batches, total, caps = self._corpus_args("beam_search_many", batches, max_length, max_new_tokens, slots, pack)
         if int(slots) < k:
             raise ValueError(f"beam_search_many: slots = {slots} is below num_beams = {k}, the rows of one utterance")
-        results = self._decode_corpus(batches, caps, slots, pack, False, False, beam=config, trace=return_step_logprobs) if total else {}
+        results = self._decode_corpus(batches, caps, slots, pack, False, False, beam=config, trace=return_step_logprobs, fusion=fusion) if total else {}
         hyps = dec.BeamHypotheses([list(results[u][0][:n]) for u in range(total)])
         hyps.sequence_scores = [results[u][1][:n] for u in range(total)]
         hyps.sequence_logprobs = [results[u][2][:n] for u in range(total)]
+        if fusion is not None and total:  # one scoring launch over every hypothesis returned
+            flat = iter(fusion[0].token_logprobs([h for per in hyps for h in per]))
+            hyps.lm_logprobs = [torch.stack([next(flat).sum() for _ in per]) if len(per) else torch.zeros(0, dtype=torch.float64) for per in hyps]
+        elif fusion is not None:
+            hyps.lm_logprobs = []
         if return_step_logprobs:
             hyps.step_logprobs = [results[u][4] for u in range(total)]
         if not return_scores:
@@ -445,18 +459,20 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
     @torch.no_grad()
     def beam_search(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, num_beams: int = 4,
                     num_return_sequences: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False,
-                    max_length: Optional[int] = None, max_new_tokens: Optional[int] = None, slots: int = 64):
+                    max_length: Optional[int] = None, max_new_tokens: Optional[int] = None, slots: int = 64, lm=None, lm_weight: float = 0.0,
+                    lm_bonus: float = 0.0):
         """``beam_search_many`` for one batch, in HF's ``num_return_sequences`` layout: a decoder.BeamSearchOutput whose ``sequences``
         are LongTensor [B * N, S] on the inputs' device -- clip b's hypotheses, best first, in rows b * N .. b * N + N - 1, <pad> (1)
         after the end, S the longest row -- with ``sequences_scores`` float64 [B * N], ``token_logprobs`` [B * N, S - 1] (exactly 0 at
-        the <pad> columns) and ``sequence_logprobs`` float64 [B * N]."""
+        the <pad> columns) and ``sequence_logprobs`` float64 [B * N].  ``lm``, ``lm_weight``, ``lm_bonus``: ``beam_search_many``'s shallow
+        fusion; the scores are then the fused ones and ``lm_logprobs`` float64 [B * N] is filled."""
         self._require_decoder("beam_search()")
         if attention_mask is None:
             attention_mask = torch.ones(input_values.shape, dtype=torch.int32, device=input_values.device)
         hyps, scores = self.beam_search_many([dict(input_values=input_values, attention_mask=attention_mask)], num_beams=num_beams,
                                              num_return_sequences=num_return_sequences, length_penalty=length_penalty,
                                              early_stopping=early_stopping, max_length=dec.resolve_max_length(max_length, max_new_tokens),
-                                             slots=slots, pack=1, return_scores=True)
+                                             slots=slots, pack=1, return_scores=True, lm=lm, lm_weight=lm_weight, lm_bonus=lm_bonus)
         rows = [h for per in hyps for h in per]
         device = input_values.device
         S = max((int(r.shape[0]) for r in rows), default=1)
@@ -467,7 +483,8 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
             tlp[i, :l.shape[0]] = l
         cat = lambda per: torch.cat(list(per)) if len(rows) else torch.zeros(0, dtype=torch.float64)  # noqa: E731
         return dec.BeamSearchOutput(sequences=seqs.to(device), sequences_scores=cat(hyps.sequence_scores).to(device), token_logprobs=tlp.to(device),
-                                    sequence_logprobs=cat(hyps.sequence_logprobs).to(device))
+                                    sequence_logprobs=cat(hyps.sequence_logprobs).to(device),
+                                    lm_logprobs=cat(hyps.lm_logprobs).to(device) if hyps.lm_logprobs is not None else None)
 
     @torch.no_grad()
     def mbr_many(self, batches, num_return_sequences: int = 8, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
@@ -542,7 +559,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
     @torch.no_grad()
     def transcribe_long(self, waveform: torch.Tensor, vad=None, max_length: Optional[int] = None, slots: int = 64, pack: int = 8,
                         return_scores: bool = False, timestamps: bool = False, do_normalize: bool = False, num_beams: Optional[int] = None,
-                        length_penalty: float = 1.0, early_stopping=False):
+                        length_penalty: float = 1.0, early_stopping=False, lm=None, lm_weight: float = 0.0, lm_bonus: float = 0.0):
         """A transcript of a whole recording: ``waveform`` is a 1-D 16 kHz CUDA tensor of any length from one encoder frame on.  It is
         cut at pauses on the device (segment.segment; ``vad``: None, a segment.VadParams or a dict of its fields), and every segment is
         a batch of ONE clip -- ``input_values = waveform[s:e][None]``, mask all ones -- so its padded length is its own and GroupNorm
@@ -554,18 +571,20 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         ``token_logprobs`` (device), ``logprob`` and ``avg_logprob``, and with ``timestamps`` ``token_times`` [len - 1, 2] in
         recording time (``align_many``'s times plus ``start_s``).  ``do_normalize``: each segment is normalised on its own.
         ``num_beams`` (None: greedy, as ever): every segment's ids are the best beam of ``beam_search_many`` with ``length_penalty`` and
-        ``early_stopping``, its scores that beam's."""
+        ``early_stopping``, its scores that beam's.  ``lm``, ``lm_weight``, ``lm_bonus`` (with ``num_beams``) are ``beam_search_many``'s
+        shallow fusion; the segments' ``token_logprobs`` stay the acoustic model's."""
         def cut(params):
             segs = seg.segment(waveform, params)
             wave = waveform.to(torch.float32)
             return segs, [segs.start_samples, segs.end_samples], lambda s, e: wave[s:e]
         return self._transcribe_cut("transcribe_long()", cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize,
-                                    (num_beams, length_penalty, early_stopping))
+                                    (num_beams, length_penalty, early_stopping), (lm, lm_weight, lm_bonus))
 
     @torch.no_grad()
     def transcribe_channels(self, waveforms: torch.Tensor, crosstalk_db: float = seg.DEFAULT_CROSSTALK_DB, vad=None, max_length: Optional[int] = None,
                             slots: int = 64, pack: int = 8, return_scores: bool = False, timestamps: bool = False, do_normalize: bool = False,
-                            num_beams: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False):
+                            num_beams: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False, lm=None, lm_weight: float = 0.0,
+                            lm_bonus: float = 0.0):
         """``transcribe_long`` for a recording with one speaker per channel (a two-channel telephone call): ``waveforms`` is a
         [channels, samples] 16 kHz CUDA tensor.  Every channel is cut at its own pauses (segment.segment_channels; a frame in which
         another channel is louder by more than ``crosstalk_db`` is not speech), and every segment of every channel is a batch of ONE
@@ -580,9 +599,10 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
             return (segs, [segs.start_samples, segs.end_samples, segs.channel.to(torch.int64), segs.overlap_frames.to(torch.int64)],
                     lambda s, e, c, _: waves[c, s:e])
         return self._transcribe_cut("transcribe_channels()", cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize,
-                                    (num_beams, length_penalty, early_stopping))
+                                    (num_beams, length_penalty, early_stopping), (lm, lm_weight, lm_bonus))
 
-    def _transcribe_cut(self, what, cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize, beam=(None, 1.0, False)):
+    def _transcribe_cut(self, what, cut, vad, max_length, slots, pack, return_scores, timestamps, do_normalize, beam=(None, 1.0, False),
+                        fusion=(None, 0.0, 0.0)):
         """``transcribe_long`` and ``transcribe_channels`` (``what``) but for the cut itself.  ``cut(params)`` cuts the recording and
         returns (the Segments / ChannelSegments, the per-segment table as device columns -- start samples, end samples and, per channel,
         channel and overlap frames --, a callable that takes a row of that table to the segment's samples).  Everything else is here: the
@@ -591,6 +611,9 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
         self._require_decoder(what)
         if beam[0] is not None:  # refused before the recording is cut
             dec.check_beam_args(beam[0], 1, beam[1], beam[2], vocab=self.speecht5.encoder._decoder_vocab)
+            dec.check_fusion_args(*fusion, vocab=self.speecht5.encoder._decoder_vocab)
+        elif fusion[0] is not None:
+            raise ValueError(f"{what}: lm= needs num_beams=: shallow fusion is part of beam search")
         params = seg.resolve_params(vad)
         cap = dec.resolve_max_length(dec.MAX_TEXT_POSITIONS if max_length is None else max_length)
         segs, columns, clip = cut(params)
@@ -606,7 +629,7 @@ class SpeechT5ForSpeechToTextMI355X(nn.Module):
             ids, scores = rows if return_scores else (rows, None)
         else:
             hyps, per_token = self.beam_search_many(batches, num_beams=beam[0], length_penalty=beam[1], early_stopping=beam[2], max_length=cap,
-                                                    slots=slots, pack=pack, return_scores=True)
+                                                    slots=slots, pack=pack, return_scores=True, lm=fusion[0], lm_weight=fusion[1], lm_bonus=fusion[2])
             device = batches[0]["input_values"].device
             ids, scores = [per[0] for per in hyps], [per[0].to(device) for per in per_token] if return_scores else None
         out = []

@@ -13,7 +13,9 @@ with ``--greedy-first``, a sampled one otherwise; ``--select mbr`` makes them th
 list's others instead (metrics.mbr_select) and adds "mbr_risk" to every "nbest" entry.  ``--beams K`` (with ``--slots`` >= K) decodes by
 beam search instead (``beam_search_many``: ``--length-penalty``, ``--early-stopping false|true|never``): the line's own fields are the
 best beam, ``--nbest N`` (N <= K) then lists the N best beams in the search's order, each with "score" (HF's ``sequences_scores``) beside
-"logprob" and "avg_logprob", and ``--select mbr`` works on that list; the sampling flags do not go with it.  ``--ref FILE`` (Kaldi ``utt_id text``; needs a
+"logprob" and "avg_logprob", and ``--select mbr`` works on that list; the sampling flags do not go with it.  ``--ngram lm.arpa`` (with ``--beams``; ``--lm-weight W``, default 1, ``--lm-bonus B``,
+default 0) fuses a character n-gram model over the decoder's ids into the search (ngram.py): "logprob" and "score" are then the fused
+values, and ``--scores`` adds "lm_logprob" to the line and to every "nbest" entry.  ``--ref FILE`` (Kaldi ``utt_id text``; needs a
 tokenizer on disk) or ``--ref-ids FILE`` (``utt_id id id ...``) adds "errors": {"cer", "wer"?, "sub", "del", "ins", "ref_len"} to every
 line that has a reference and writes the corpus ``%CER`` / ``%WER`` lines to stderr.  No data parallelism.  Inputs, as extract.py takes them: a SLURP split (``--data-path slurp --split devel``: the
 same reader, headset recording first; .wav / .flac, other rates resampled on the device), audio files named on the command line, or
@@ -246,13 +248,15 @@ def load_references(args, tok):
 class Line:
     """One utterance on its way to --out.  ``ids``: its generated row without padding; ``logprob``: (the sum of the generated tokens'
     log-probabilities, how many the decode path counts as generated); ``times``: its "token_times"; ``nbest``: the records of its
-    hypotheses; ``errors``: its "errors".  A field that is None is not written."""
+    hypotheses; ``errors``: its "errors"; ``lm_logprob`` (--ngram with --scores): its n-gram log-probability.  A field that is None is not
+    written."""
     uid: str
     ids: list
     logprob: Optional[tuple] = None
     times: Optional[list] = None
     nbest: Optional[list] = None
     errors: Optional[dict] = None
+    lm_logprob: Optional[float] = None
 
 
 def token_fields(tok, ids, logprob=None, avg_logprob=None, times=None):
@@ -274,6 +278,8 @@ def utterance_record(line, tok, width=0):
     total, n = line.logprob if line.logprob is not None else (None, None)
     rec = {"id": line.uid}
     rec.update(token_fields(tok, line.ids + [PAD_TOKEN_ID] * (width - len(line.ids)), total, None if total is None else total / n, line.times))
+    if line.lm_logprob is not None:
+        rec["lm_logprob"] = line.lm_logprob
     if line.nbest is not None:
         rec["nbest"] = line.nbest
     if line.errors is not None:
@@ -281,10 +287,10 @@ def utterance_record(line, tok, width=0):
     return rec
 
 
-def nbest_records(hyps, sums, tok, risk=None, beam_scores=None):
+def nbest_records(hyps, sums, tok, risk=None, beam_scores=None, lm_sums=None):
     """One utterance's "nbest": its hypotheses (1-D id tensors) by log-probability ``sums[h]``, best first, ties by hypothesis index;
     ``risk``: per hypothesis its "mbr_risk".  ``beam_scores`` (--beams): the hypotheses stay in the search's order, best score first,
-    and every entry carries its "score"."""
+    and every entry carries its "score"; ``lm_sums`` (--ngram with --scores): per hypothesis its "lm_logprob"."""
     recs = []
     for h in (range(len(hyps)) if beam_scores is not None else sorted(range(len(hyps)), key=lambda h: (-sums[h], h))):
         row = hyps[h].tolist()
@@ -292,6 +298,8 @@ def nbest_records(hyps, sums, tok, risk=None, beam_scores=None):
         if beam_scores is not None:
             rec["score"] = beam_scores[h]
         rec.update({"logprob": sums[h], "avg_logprob": sums[h] / (len(row) - 1)})
+        if lm_sums is not None:
+            rec["lm_logprob"] = lm_sums[h]
         if tok is not None:
             rec["text"] = tok.decode(strip_special(row))
         if risk is not None:
@@ -369,9 +377,14 @@ def check_args(args, ap):
         if args.long:
             ap.error("--beams does not go with --long")
     else:
-        for flag, v in (("--length-penalty", args.length_penalty), ("--early-stopping", args.early_stopping)):
+        for flag, v in (("--length-penalty", args.length_penalty), ("--early-stopping", args.early_stopping), ("--ngram", args.ngram)):
             if v is not None:
                 ap.error(f"{flag} needs --beams")
+    for flag, v in (("--lm-weight", args.lm_weight), ("--lm-bonus", args.lm_bonus)):
+        if v is not None and args.ngram is None:
+            ap.error(f"{flag} needs --ngram")
+        if v is not None and not math.isfinite(v):
+            ap.error(f"{flag} {v} must be finite")
     if args.long:
         return
     for flag, v in (("--max-segment-s", args.max_segment_s), ("--min-silence-s", args.min_silence_s), ("--vad-margin-db", args.vad_margin_db),
@@ -458,6 +471,7 @@ class Run:
     model: Any
     processor: Any
     device: Any
+    ngram: Any = None  # --ngram: the model, read once (load_ngram)
 
 
 def span_sums(spans):
@@ -532,20 +546,37 @@ def sampled_window(run, feats, first_utterance):
 
 def beam_window(run, feats):
     """--beams: (rows, their log-probability sums, per utterance its "nbest" or None) of one window's batches through
-    ``beam_search_many``.  The row is the best beam or, with --select mbr, the one of least risk within the --nbest list."""
+    ``beam_search_many``.  The row is the best beam or, with --select mbr, the one of least risk within the --nbest list.  With --ngram
+    the sums are the fused ones and a fourth value, the rows' n-gram log-probabilities, follows (None without)."""
     args = run.args
+    fusion = {}
+    if args.ngram is not None:
+        fusion = dict(lm=load_ngram(run), lm_weight=1.0 if args.lm_weight is None else args.lm_weight, lm_bonus=args.lm_bonus or 0.0)
     hyps = run.model.beam_search_many(feats, num_beams=args.beams, num_return_sequences=args.nbest or 1,
                                       length_penalty=1.0 if args.length_penalty is None else args.length_penalty,
                                       early_stopping=beam_early_stopping(args.early_stopping), max_length=args.max_length, slots=args.slots,
-                                      pack=args.pack)
+                                      pack=args.pack, **fusion)
     sums, scores = [t.tolist() for t in hyps.sequence_logprobs], [t.tolist() for t in hyps.sequence_scores]
+    lm_sums = [t.tolist() for t in hyps.lm_logprobs] if fusion and args.scores else [None] * len(hyps)
     pick, risks = [0] * len(hyps), [None] * len(hyps)
     if args.select == "mbr":
         sel = metrics.mbr_select(hyps)
         pick = sel.best.cpu().tolist()
         risks = [r.cpu().tolist() for r in sel.risk]
-    lists = [nbest_records(per, mine, run.tok, risk, sc) for per, mine, risk, sc in zip(hyps, sums, risks, scores)] if args.nbest else None
-    return [per[b] for per, b in zip(hyps, pick)], [mine[b] for mine, b in zip(sums, pick)], lists
+    lists = [nbest_records(per, mine, run.tok, risk, sc, lm) for per, mine, risk, sc, lm in zip(hyps, sums, risks, scores, lm_sums)] if args.nbest else None
+    return [per[b] for per, b in zip(hyps, pick)], [mine[b] for mine, b in zip(sums, pick)], lists, [lm and lm[b] for lm, b in zip(lm_sums, pick)]
+
+
+def load_ngram(run):
+    """--ngram: the ARPA file over the decoder's ids, read once per run; SystemExit naming the flag and what the file lacks."""
+    if run.ngram is None:
+        from .ngram import NgramLM
+        vocab = run.model.speecht5.encoder._decoder_vocab
+        try:
+            run.ngram = NgramLM.from_arpa(run.args.ngram, vocab)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--ngram {run.args.ngram}: not an ARPA model over the decoder's {vocab} ids: {e}")
+    return run.ngram
 
 
 def window_lines(run, items, starts):
@@ -553,9 +584,9 @@ def window_lines(run, items, starts):
     args = run.args
     chunks = [items[b0:b0 + args.batch_size] for b0 in starts]
     feats = [load_batch(chunk, b0, run.processor, run.device) for chunk, b0 in zip(chunks, starts)]
-    lists = None
+    lists = lm_sums = None
     if args.beams is not None:
-        rows, sums, lists = beam_window(run, feats)
+        rows, sums, lists, lm_sums = beam_window(run, feats)
     elif args.nbest:
         rows, sums, lists = sampled_window(run, feats, starts[0])
     else:
@@ -568,7 +599,7 @@ def window_lines(run, items, starts):
         stamps = [rounded_pairs(zip(al.start_times.cpu().tolist(), al.end_times.cpu().tolist())) for al in als]
     uids = [uid for chunk in chunks for uid, _, _ in chunk]
     errs = line_errors(run, uids, ids)  # one pass per window
-    return [Line(*fields) for fields in zip(uids, ids, scores, stamps, lists or [None] * n, errs)]
+    return [Line(*fields) for fields in zip(uids, ids, scores, stamps, lists or [None] * n, errs, lm_sums or [None] * n)]
 
 
 def pool_lines(run, items):
@@ -628,6 +659,10 @@ def build_parser():
                     "--nbest N (N <= K) then lists the N best beams with their \"score\"")
     ap.add_argument("--length-penalty", type=float, default=None, help="with --beams: a hypothesis scores its log-probability over length ** this (default 1)")
     ap.add_argument("--early-stopping", choices=["false", "true", "never"], default=None, help="with --beams: HF's early_stopping (default false)")
+    ap.add_argument("--ngram", default=None, metavar="ARPA", help="with --beams: shallow fusion of a character n-gram model over the decoder's ids "
+                    "(python -m loco-asr_amd.ngram trains one); \"logprob\" and \"score\" are then the fused values and --scores adds \"lm_logprob\"")
+    ap.add_argument("--lm-weight", type=float, default=None, help="with --ngram: the weight of the model's log-probability (default 1)")
+    ap.add_argument("--lm-bonus", type=float, default=None, help="with --ngram: added per generated token (default 0)")
     ap.add_argument("--scores", action="store_true", help="also write \"logprob\" (sum over the generated tokens) and \"avg_logprob\" (per generated token)")
     ap.add_argument("--timestamps", action="store_true", help="also write \"token_times\": [start_s, end_s] of every generated token (cross-attention + DTW)")
     ap.add_argument("--tokenizer", default=None, help="spm_char.model file or a directory holding one; found on disk -> \"text\" is written too")
