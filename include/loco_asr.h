@@ -619,6 +619,27 @@ int loco_op_skinny_gemm(const float* A, int64_t lda, const float* W, int64_t ldw
 size_t loco_decoder_attention_scratch_bytes(int32_t B, int32_t Sq, int32_t Tk);
 int loco_op_decoder_attention(const float* q, const float* k, const float* v, const int32_t* key_counts, float* out, int32_t B, int32_t Sq,
                               int32_t Tk, int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream);
+/* The forms of those two kernels that only the decode step, the slot pool and the language model launch, as operators (per-element
+ * tests).  All strides are in floats.
+ *   loco_op_skinny_gemm_split: A W^T + bias (NULL: none) without an epilogue, columns [0, nsplit) to C[m ldc + n], columns [nsplit, N)
+ *     to C2.  c2_rows NULL (the decode step's q | k|v product): C2[m ldc2 + n - nsplit].  c2_rows [M] on the device (the slot pool's):
+ *     C2[m ldc2 + c2_rows[m] c2_row_stride + n - nsplit]; a row whose c2_rows[m] is negative writes nothing to C2.  0 <= nsplit <= N.
+ *   loco_op_decoder_attention_strided: loco_op_decoder_attention with every stride the caller's: row (b, i) of q at q + b sq + i ldq,
+ *     key j at k + b sk + j ldk, value j at v + b sv + j ldv, row (b, i) of out at out + b so + i ldo; head h at column 64 h of each.
+ *     A query without a visible key (key_counts[b] <= 0, or causal with i + causal_offset < 0) yields zeros; key_counts[b] > Tk means Tk.
+ *   loco_op_decoder_pool_attention: one query per slot (q, out [slots, 768], scale 1, not causal) over the slot's keys j < key_counts[b]
+ *     at k + b sk + j ldk and values at v + b sk + j ldk; Tk_bound >= every count that is to be seen in full.  A slot's output depends
+ *     on its own count and rows only, not on Tk_bound nor on the other slots.  scratch >= loco_decoder_pool_attention_scratch_bytes,
+ *     1 <= slots <= 64. */
+int loco_op_skinny_gemm_split(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, float* C2,
+                              int64_t ldc2, const int32_t* c2_rows, int64_t c2_row_stride, int32_t nsplit, int32_t M, int32_t N, int32_t K,
+                              void* stream);
+int loco_op_decoder_attention_strided(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
+                                      int64_t sv, const int32_t* key_counts, float* out, int64_t ldo, int64_t so, int32_t B, int32_t Sq, int32_t Tk,
+                                      int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream);
+size_t loco_decoder_pool_attention_scratch_bytes(int32_t slots, int32_t Tk_bound);
+int loco_op_decoder_pool_attention(const float* q, const float* k, int64_t ldk, int64_t sk, const float* v, const int32_t* key_counts, float* out,
+                                   int32_t slots, int32_t Tk_bound, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- decoder slot pool: greedy decoding of a corpus, finished rows refilled -------------------------------------------------------
  * loco_decoder_generate carries every row of one batch until the longest has ended.  A pool has `slots` decoder rows that each sit at

@@ -183,6 +183,11 @@ SIGNATURES = {
     "loco_op_skinny_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "loco_decoder_attention_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "loco_op_decoder_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _sz, _vp]),
+    "loco_op_skinny_gemm_split": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "loco_op_decoder_attention_strided": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32,
+                                                    _f, _vp, _sz, _vp]),
+    "loco_decoder_pool_attention_scratch_bytes": (_sz, [_i32, _i32]),
+    "loco_op_decoder_pool_attention": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "loco_decoder_forward_attn": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
     "loco_decoder_align_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "loco_decoder_align": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _sz, _vp]),

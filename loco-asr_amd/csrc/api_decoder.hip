@@ -1093,6 +1093,60 @@ int loco_op_decoder_attention(const float* q, const float* k, const float* v, co
     return LOCO_OK;
 }
 
+// ---- the decode step's and the slot pool's forms of the two kernels as operators (tests/test_gpu_decoder_contract.py) ----
+int loco_op_skinny_gemm_split(const float* A, int64_t lda, const float* Wt, int64_t ldw, const float* bias, float* C, int64_t ldc, float* C2,
+                              int64_t ldc2, const int32_t* c2_rows, int64_t c2_row_stride, int32_t nsplit, int32_t M, int32_t N, int32_t K,
+                              void* stream) {
+    const char* fn = "loco_op_skinny_gemm_split";
+    if (!A || !Wt || !C || !C2) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (M <= 0 || N <= 0 || K <= 0 || K % 256 != 0) return fail(LOCO_E_INVALID, "%s: M = %d, N = %d, K = %d: all positive, K a multiple of 256", fn, M, N, K);
+    if (M > kSkinnyMaxM) return fail(LOCO_E_INVALID, "%s: M = %d exceeds the limit of %d rows", fn, M, kSkinnyMaxM);
+    if (nsplit < 0 || nsplit > N) return fail(LOCO_E_INVALID, "%s: nsplit = %d is outside 0 .. N = %d", fn, nsplit, N);
+    if (lda < K || ldw < K || ((lda | ldw) & 3)) return fail(LOCO_E_INVALID, "%s: lda and ldw must be >= K and multiples of 4 floats", fn);
+    if (ldc < nsplit || (!c2_rows && ldc2 < N - nsplit) || (c2_rows && c2_row_stride < N - nsplit))
+        return fail(LOCO_E_INVALID, "%s: a destination row is shorter than its %d / %d columns", fn, nsplit, N - nsplit);
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Wt)) & 15) return fail(LOCO_E_INVALID, "%s: A and W must be 16-byte aligned", fn);
+    if (!c2_rows)
+        HIP_TRY(launch_skinny_gemm(A, (long)lda, Wt, (long)ldw, bias, nullptr, 0, C, (long)ldc, C2, (long)ldc2, nsplit, M, N, K, kEpiNone, (hipStream_t)stream));
+    else
+        HIP_TRY(launch_skinny_gemm_rows(A, (long)lda, Wt, (long)ldw, bias, C, (long)ldc, C2, (long)ldc2, c2_rows, (long)c2_row_stride, nsplit, M, N, K,
+                                        (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_decoder_attention_strided(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
+                                      int64_t sv, const int32_t* key_counts, float* out, int64_t ldo, int64_t so, int32_t B, int32_t Sq, int32_t Tk,
+                                      int32_t causal, int32_t causal_offset, float scale, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* fn = "loco_op_decoder_attention_strided";
+    if (!q || !k || !v || !out || B <= 0 || Sq <= 0 || Tk <= 0) return fail(LOCO_E_INVALID, "%s: null / non-positive argument", fn);
+    if (ldq < kHidden || ldk < kHidden || ldv < kHidden || ldo < kHidden || ((ldq | ldk | sq | sk) & 3))
+        return fail(LOCO_E_INVALID, "%s: row strides must be >= 768 floats, those of q and k and their clip strides multiples of 4 floats", fn);
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) return fail(LOCO_E_INVALID, "%s: q and k must be 16-byte aligned", fn);
+    if (scratch_bytes < dec_attention_scratch_bytes(B, Sq, Tk) || (!scratch && dec_attention_scratch_bytes(B, Sq, Tk) > 0))
+        return fail(LOCO_E_WORKSPACE, "%s: scratch %zu < %zu bytes", fn, scratch ? scratch_bytes : (size_t)0, dec_attention_scratch_bytes(B, Sq, Tk));
+    HIP_TRY(launch_dec_attention(q, (long)ldq, (long)sq, k, (long)ldk, (long)sk, v, (long)ldv, (long)sv, key_counts, out, (long)ldo, (long)so, B, Sq, Tk,
+                                 causal, causal_offset, scale, static_cast<float*>(scratch), (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+size_t loco_decoder_pool_attention_scratch_bytes(int32_t slots, int32_t Tk_bound) {
+    return slots > 0 && Tk_bound > 0 ? dec_pool_attention_scratch_bytes(slots, Tk_bound) : 0;
+}
+
+int loco_op_decoder_pool_attention(const float* q, const float* k, int64_t ldk, int64_t sk, const float* v, const int32_t* key_counts, float* out,
+                                   int32_t slots, int32_t Tk_bound, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* fn = "loco_op_decoder_pool_attention";
+    if (!q || !k || !v || !key_counts || !out || !scratch) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if (slots <= 0 || slots > kSkinnyMaxM || Tk_bound <= 0)
+        return fail(LOCO_E_INVALID, "%s: slots = %d must be 1 .. %d, Tk_bound = %d positive", fn, slots, kSkinnyMaxM, Tk_bound);
+    if (ldk < kHidden || ((ldk | sk) & 3)) return fail(LOCO_E_INVALID, "%s: ldk must be >= 768 floats, ldk and sk multiples of 4 floats", fn);
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) return fail(LOCO_E_INVALID, "%s: q and k must be 16-byte aligned", fn);
+    if (scratch_bytes < dec_pool_attention_scratch_bytes(slots, Tk_bound))
+        return fail(LOCO_E_WORKSPACE, "%s: scratch %zu < %zu bytes", fn, scratch_bytes, dec_pool_attention_scratch_bytes(slots, Tk_bound));
+    HIP_TRY(launch_dec_pool_attention(q, k, (long)ldk, (long)sk, v, key_counts, out, slots, Tk_bound, static_cast<float*>(scratch), (hipStream_t)stream));
+    return LOCO_OK;
+}
+
 // ---- decoder attention probabilities and the DTW as operators (decoder_probs.hip) ----
 int loco_op_decoder_attention_probs(const float* q, const float* k, const int32_t* key_counts, float* P, int32_t B, int32_t Sq, int32_t Tk,
                                     int32_t causal, int64_t ldq, int64_t sq, int64_t ldk, int64_t sk, float scale, void* stream) {

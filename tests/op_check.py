@@ -1,6 +1,7 @@
 """Per-element checks of single operators: guarded outputs, poisoned inputs, fp64 references and derived error bars.
 
-Used by tests/test_gpu_gemm_contract.py, tests/test_gpu_attention_contract.py and tests/test_gpu_attention_probs_contract.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
+Used by tests/test_gpu_gemm_contract.py, tests/test_gpu_attention_contract.py, tests/test_gpu_attention_probs_contract.py,
+tests/test_gpu_decoder_contract.py and (on the CPU) tests/test_decoder_contract_ref.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
 roundings times the forward-error scale of the element it applies to.
 
 Guards.  An output lives inside a larger allocation filled with a sentinel bit pattern (a NaN with a payload): before the first
@@ -81,6 +82,38 @@ first order in u throughout.  Each count is read off the kernel's instruction se
   5. The context made of these probabilities, sum_j P_ij v_jd in fp64: within sum_j bar_ij |v_jd| of the fp64 context, which is at most
      (2 max_j delta_ij + c_norm u) S[i,d] + n FLT_MIN max |v|, so within that plus the attention bar of what the attention kernel returns.
 Scores of +-inf or NaN are outside the contract (include/loco_asr.h): exp2(inf - inf) is NaN.
+
+Skinny GEMM (decoder.hip: skinny_gemm_kernel), skinny_count() below; S as for the GEMMs above.  ks = skinny_slices(N, K), which restates
+the launcher's skinny_gemm_slices in Python (a test that disagrees with the launcher about ks only moves the bar by a few counts; the values
+are checked either way).  A lane's partial sum is one chain of 4 FMAs per 256-element chunk over the chunks of its slice, ceil(K / 256 / ks)
+of them in slice 0, which holds the most; wave_sum adds 6 roundings (the butterfly, d = 32 ... 1), the merge of the slices in LDS ks - 1,
+the bias one and the residual one.  Every partial sum is a sum of a subset of the products, so each rounding is at most u S.
+Count = 4 ceil(K / 256 / ks) + 6 + (ks - 1) + 2.  The GELU epilogue is the erf form of the GEMMs above (the same gelu_erf): element_bar().
+
+Decoder attention (decoder.hip: dec_attention_kernel, dec_attention_combine; decoder_common.h: LOCO_DEC_LOAD_Q, LOCO_DEC_QK,
+LOCO_DEC_SOFTMAX_TILE), dec_attention_bar() below.  out[i,d] = sum_j w_ij v_jd, w = softmax_j(s_ij) over the keys visible to query i,
+s_ij = sum_c (scale q_c) k_c; S[i,d] = sum_j w_ij |v_jd| with the fp64 softmax w.  As for the encoder's attention, every error of an
+exponent's argument is an absolute error delta_ij of the score and a relative error of p_ij:
+  1. Score.  `q * scale`: one rounding per element of q, u A_ij in the sum, A_ij = sum_c |scale q_c| |k_c|.  LOCO_DEC_QK: four partial sums of
+     16 FMAs each, combined as (a0 + a1) + (a2 + a3): an element's product passes 16 + 2 roundings of at most u A_ij.  19 u A_ij.
+  2. `sc - m_new`: one rounding of the difference, u |s_ij - m| with m the running maximum of the tile, s_ij <= m <= m_i: at most
+     u (m_i - s_ij), m_i the row's maximum.
+  3. expf is OCML's, not v_exp_f32.  No HIP math document with ULP figures ships with this ROCm installation, so it is charged 2 ulp =
+     4 u relative.  (A cap, not a measurement: what this bar exists for -- a dropped or extra key, a wrong row, a lost chunk -- moves an
+     element by orders of magnitude more.)
+  4. Splits (nsplit > 1), dec_attention_combine: a split's sum and O are both multiplied by w = expf(ms - m).  It is the same register in
+     numerator and denominator, like corr below; it is charged all the same, as an error of the scores of the split's keys: the
+     difference's rounding, u |ms - m| <= u max_j (m_i - s_ij), and expf's 4 u.
+  5. Propagation, as in part 3 of the encoder's bar: 2 max_j delta_ij * S[i,d].
+  6. P V.  Per tile of 64 keys `o *= corr` and up to 64 FMAs: 65 roundings, each at most u S once divided by l (partial sums of |p v| / l never
+     exceed S); per split one FMA in the combine.  (65 ntiles + nsplit) u S, ntiles = ceil(n_i / 64) with n_i the visible keys of the
+     query: splits begin at multiples of 64, so the tiles of all splits together are the tiles of the row.
+  7. Normalisation.  l is a sum of positive terms, its error relative: per tile `s_run * corr` (1), the 6 additions of wave_sum(p) and the
+     sum (1); per split one FMA; the final division: (8 ntiles + nsplit + 1) u |ref|.
+Charged nothing: the running maximum and corr = expf(m_run - m_new).  o and s_run are multiplied by the ONE corr register, so whatever
+it holds scales numerator and denominator alike, and p, s_run and o all carry the factor exp(-m) for whatever m the wave holds.  What an
+inexact m costs is part 2.  A query without a visible key is outside the bar: its output is exactly 0.0 and is asserted as such.
+Bar = [2 max_j delta_ij + (65 ntiles + nsplit) u] S + (8 ntiles + nsplit + 1) u |ref|, nsplit = 0 in both brackets without splits.
 """
 import math
 
@@ -242,6 +275,42 @@ def attention_bar(kernel, ref, S, A_max, P_max, s_max, b_max, ntiles, table_form
     return bar
 
 
+def skinny_slices(N, K):
+    """skinny_gemm_slices of decoder.hip, restated: the k-slices a (N, K) product is launched with"""
+    chunks = K // 256
+    if chunks >= 8 or (N <= 128 and chunks >= 4):
+        return 4
+    return 2 if chunks >= 2 else 1
+
+
+def skinny_count(N, K, bias=True, residual=False):
+    ks = skinny_slices(N, K)
+    return 4 * math.ceil(K / 256 / ks) + 6 + (ks - 1) + int(bias) + int(residual)
+
+
+def dec_attention_splits(B, Sq, Tk):
+    """dec_attention_splits of decoder.hip, restated: (splits, keys per split) of a launch_dec_attention"""
+    rows = B * 12 * Sq
+    ns = max(1, min((4096 + rows - 1) // rows, (Tk + 255) // 256, 64))
+    return ns, ((Tk + ns - 1) // ns + 63) // 64 * 64
+
+
+def dec_pool_attention_splits(Tk_bound):
+    """dec_pool_attention_splits of decoder.hip, restated: splits of 256 keys"""
+    return 1 if Tk_bound <= 256 else (Tk_bound + 255) // 256
+
+
+def dec_attention_bar(ref, S, A_max, spread_max, nvis, nsplit):
+    """The decoder attention bar of the docstring.  ref, S [..., 64]; per query row [..., 1]: A_max = max_j sum_c |scale q_c| |k_c| and
+    spread_max = max_j (m_i - s_ij) over the visible keys, nvis their number; nsplit the launch's key splits (1: no combine)."""
+    ntiles = torch.ceil(nvis / 64)
+    split = nsplit if nsplit > 1 else 0
+    delta = (19 * A_max + spread_max + 4) * U
+    if split:
+        delta = delta + (spread_max + 4) * U
+    return (2 * delta + (65 * ntiles + split) * U) * S + (8 * ntiles + split + 1) * U * ref.abs()
+
+
 FLT_MIN = 2.0 ** -126
 PROBS_PRODUCT_COUNT = {"f32": 64, "x3": 29, "x2": 16}
 
@@ -283,6 +352,19 @@ def assert_elements(name, out, ref, S, bar, rel_l2_bar=None, **tags):
     if rel_l2_bar is not None:
         assert rl2 < rel_l2_bar, f"{name} {tags}: rel_l2 {rl2:.3e} >= {rel_l2_bar}"
     return ratio
+
+
+def assert_dec_attention(name, out, r, nsplit, **tags):
+    """out [B, 12, Sq, 64] against r, the dict of decoder_contract_cases.attn_reference: a query without a visible key holds exactly 0.0,
+    every other element is within dec_attention_bar of the fp64 reference"""
+    out = out.detach().cpu().reshape(r["ref"].shape)
+    has = r["has_keys"].expand_as(r["ref"])
+    empty = out[~has]
+    assert bool((empty == 0).all()), f"{name} {tags}: {int((empty != 0).sum())} elements of queries without a key are not 0.0 (NaN: {int(empty.isnan().sum())})"
+    if not bool(has.any()):
+        return 0.0
+    bar = dec_attention_bar(r["ref"], r["S"], r["A_max"], r["spread_max"], r["nvis"], nsplit)
+    return assert_elements(name, out[has], r["ref"][has], r["S"][has], bar[has], **tags)
 
 
 def same_bits(a, b):
