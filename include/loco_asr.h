@@ -1139,6 +1139,51 @@ int loco_op_edit_distance(const int32_t* symbols, int64_t n_symbols, const int32
 int loco_op_nbest_risk(const int32_t* counts, const int32_t* group_offsets, const double* weights, int32_t U, double* risk, int32_t* best,
                        void* stream);
 
+/* ---- embedding neighbours: row norms, fused top-k, group mean (neighbors.hip) ---------------------------------------------------
+ * Which rows of K [N, 768] are closest to each row of Q [M, 768], without an M x N matrix: the exact-fp32 MFMA product is walked in
+ * 128 x 128 tiles and every query keeps a sorted list of its k best keys.  All pointers are device pointers; dim must be 768.
+ *
+ * loco_op_row_norm2: norm2[r] = the squared norm of x's row r (row stride ldx floats), summed in double in one written order (lane l
+ * of a wave sums elements l, l + 64, ... ascending, then a butterfly) and rounded to fp32 once.
+ *
+ * loco_op_topk: values f32 [M][k] and indices i32 [M][k], best first, ties towards the LOWER key index.  Q and K are fp32 with row
+ * strides ldq / ldk (multiples of 4, >= 768, ldq < 2^23; both bases 16-byte aligned).  Metrics, s = the score, larger is better:
+ *     LOCO_TOPK_DOT      s = q.k
+ *     LOCO_TOPK_COSINE   s = ((q.k) * inv_q) * inv_k,  inv = 1 / max(sqrt(norm2), 1e-12)   (torch.nn.functional.normalize's eps; a zero
+ *                        vector scores 0)
+ *     LOCO_TOPK_L2       s = (2 (q.k) - norm2_k) - norm2_q   (the negated squared distance)
+ * q_norm2 [M] and k_norm2 [N] are loco_op_row_norm2's outputs (ignored, and may be NULL, for DOT).  exclude i32 [M] (or NULL) names
+ * one key index per query that is not a candidate, -1 for none (leave-one-out, self-similarity).  A NaN score is not a candidate.
+ * Where fewer than k candidates exist the remaining slots hold index -1 and value -inf.  k is 1 .. loco_topk_max_k() =
+ * LOCO_TOPK_MAX_K.  scratch holds one record of k pairs per (query, chunk of 1024 keys): loco_topk_scratch_bytes(M, N, k) =
+ * 8 M ceil(N / 1024) k bytes (0 outside the limits), 16-byte aligned; a caller bounds it by splitting M, which changes no result.
+ * Bits: a query's k results are a function of that query's 768 values, its norm, its exclude entry and the keys alone -- not of M, of
+ * the query's row, of the split of M or of the queries beside it: a score is one MFMA chain in the tile walk's k order, tiles and
+ * chunks start at multiples of 128 from key 0, and the chunk records are merged in ascending order by (value desc, index asc).
+ * Keys >= N and queries >= M are never read.
+ *
+ * loco_op_group_mean: out[g][:] = the mean of rows[index[j]][:] over j in [offsets[g], offsets[g + 1]) (offsets int64 [G + 1],
+ * ascending; index int32, or NULL for the contiguous run rows[j]).  Sums are in double in an order that depends on the group's size
+ * alone (row j goes to partial sum j mod 4 ascending; the four are added in order), divided and rounded to fp32 once.  count i32 [G]
+ * (or NULL) gets the group sizes.  An EMPTY group leaves out[g] untouched and sets count[g] = 0.  A row index outside [0, n_rows) is
+ * not read and makes its group's mean NaN.  It serves mean pooling of a ragged store and the k-means centre update (index = points
+ * stably sorted by label).  No floating-point atomics anywhere.
+ * LOCO_E_INVALID before any device work, naming the argument: a null pointer (the nullable ones excepted), dim != 768, k or metric out
+ * of range, M / N / G / rows outside 1 .. 2^31 - 1, a stride or an alignment as above; LOCO_E_WORKSPACE for a short scratch.  No
+ * allocation, no synchronisation; the caller's stream. */
+#define LOCO_TOPK_MAX_K 16
+#define LOCO_TOPK_DOT 0
+#define LOCO_TOPK_COSINE 1
+#define LOCO_TOPK_L2 2
+int32_t loco_topk_max_k(void);
+size_t loco_topk_scratch_bytes(int64_t M, int64_t N, int32_t k);
+int loco_op_row_norm2(const float* x, int64_t ldx, int64_t rows, int32_t dim, float* norm2, void* stream);
+int loco_op_topk(const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* q_norm2, const float* k_norm2, const int32_t* exclude,
+                 int64_t M, int64_t N, int32_t dim, int32_t k, int32_t metric, float* values, int32_t* indices, void* scratch,
+                 size_t scratch_bytes, void* stream);
+int loco_op_group_mean(const float* rows, int64_t ld, int64_t n_rows, const int32_t* index, const int64_t* offsets, int64_t G, int32_t dim,
+                       float* out, int64_t ldo, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ from . import lm  # noqa: F401
 from .lm import GPT2LMHeadModelMI355X  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import EditCounts, ErrorRate, MbrResult  # noqa: F401
+from . import neighbors  # noqa: F401
+from .neighbors import KMeansResult, TopK  # noqa: F401
 from . import segment  # noqa: F401
 from .segment import ChannelSegments, LongSegment, LongTranscript, Segments, VadParams  # noqa: F401
 from .speech_to_text import SpeechT5ForSpeechToTextMI355X  # noqa: F401
@@ -23,4 +25,5 @@ from .text_encoder import (SpeechT5EncoderWithTextPrenetMI355X, SpeechT5ForTextT
 __all__ = ["synth", "LIB_PATH", "LocoError", "BaseModelOutput", "Pack", "SpeechT5EncoderWithSpeechPrenetMI355X",
            "SpeechT5ForSpeechToTextMI355X", "sinusoid_table", "BatchFeature", "SpeechT5FeatureExtractorMI355X", "IntentClassifierMI355X",
            "SpeechT5EncoderWithTextPrenetMI355X", "SpeechT5ForTextToSpeechMI355X", "scaled_positional_table", "segment", "VadParams", "Segments",
-           "ChannelSegments", "LongSegment", "LongTranscript", "lm", "GPT2LMHeadModelMI355X", "metrics", "EditCounts", "ErrorRate", "MbrResult"]
+           "ChannelSegments", "LongSegment", "LongTranscript", "lm", "GPT2LMHeadModelMI355X", "metrics", "EditCounts", "ErrorRate", "MbrResult", "neighbors", "TopK",
+           "KMeansResult"]

@@ -225,6 +225,11 @@ SIGNATURES = {
     "loco_edit_max_len": (_i32, []),
     "loco_op_edit_distance": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp]),
     "loco_op_nbest_risk": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "loco_topk_max_k": (_i32, []),
+    "loco_topk_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "loco_op_row_norm2": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp]),
+    "loco_op_topk": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "loco_op_group_mean": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -426,4 +426,75 @@ int loco_op_nbest_risk(const int32_t* counts, const int32_t* group_offsets, cons
     return LOCO_OK;
 }
 
+// ---- embedding neighbours (neighbors.hip) ----
+static_assert(LOCO_TOPK_MAX_K == kTopkMaxK, "the header's cap is the kernel's");
+static_assert(LOCO_TOPK_DOT == kTopkDot && LOCO_TOPK_COSINE == kTopkCosine && LOCO_TOPK_L2 == kTopkL2, "the header's metrics are the kernel's");
+
+int32_t loco_topk_max_k(void) { return kTopkMaxK; }
+
+size_t loco_topk_scratch_bytes(int64_t M, int64_t N, int32_t k) { return topk_scratch_bytes((long)M, (long)N, (int)k); }
+
+int loco_op_row_norm2(const float* x, int64_t ldx, int64_t rows, int32_t dim, float* norm2, void* stream) {
+    const char* fn = "loco_op_row_norm2";
+    if (!x) return fail(LOCO_E_INVALID, "%s: x is null", fn);
+    if (!norm2) return fail(LOCO_E_INVALID, "%s: norm2 is null", fn);
+    if (dim != kHidden) return fail(LOCO_E_INVALID, "%s: dim = %d is not %d", fn, dim, kHidden);
+    if (rows < 1 || rows > INT32_MAX) return fail(LOCO_E_INVALID, "%s: rows = %lld is outside 1 .. 2^31 - 1", fn, (long long)rows);
+    if (ldx < kHidden) return fail(LOCO_E_INVALID, "%s: ldx = %lld is below %d", fn, (long long)ldx, kHidden);
+    if (misaligned(x, 4) || misaligned(norm2, 4)) return fail(LOCO_E_INVALID, "%s: x / norm2 is not 4-byte aligned", fn);
+    HIP_TRY(launch_row_norm2(x, (long)ldx, (long)rows, norm2, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_topk(const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* q_norm2, const float* k_norm2, const int32_t* exclude,
+                 int64_t M, int64_t N, int32_t dim, int32_t k, int32_t metric, float* values, int32_t* indices, void* scratch,
+                 size_t scratch_bytes, void* stream) {
+    const char* fn = "loco_op_topk";
+    if (!Q) return fail(LOCO_E_INVALID, "%s: Q is null", fn);
+    if (!K) return fail(LOCO_E_INVALID, "%s: K is null", fn);
+    if (!values) return fail(LOCO_E_INVALID, "%s: values is null", fn);
+    if (!indices) return fail(LOCO_E_INVALID, "%s: indices is null", fn);
+    if (!scratch) return fail(LOCO_E_INVALID, "%s: scratch is null", fn);
+    if (dim != kHidden) return fail(LOCO_E_INVALID, "%s: dim = %d is not %d", fn, dim, kHidden);
+    if (k < 1 || k > kTopkMaxK) return fail(LOCO_E_INVALID, "%s: k = %d is outside 1 .. %d", fn, k, kTopkMaxK);
+    if (metric != kTopkDot && metric != kTopkCosine && metric != kTopkL2) return fail(LOCO_E_INVALID, "%s: metric = %d is not dot, cosine or l2", fn, metric);
+    if (metric != kTopkDot && !q_norm2) return fail(LOCO_E_INVALID, "%s: q_norm2 is null (cosine and l2 need the squared norms)", fn);
+    if (metric != kTopkDot && !k_norm2) return fail(LOCO_E_INVALID, "%s: k_norm2 is null (cosine and l2 need the squared norms)", fn);
+    if (M < 1 || M > INT32_MAX) return fail(LOCO_E_INVALID, "%s: M = %lld is outside 1 .. 2^31 - 1", fn, (long long)M);
+    if (N < 1 || N > INT32_MAX) return fail(LOCO_E_INVALID, "%s: N = %lld is outside 1 .. 2^31 - 1", fn, (long long)N);
+    if ((M + 127) / 128 * topk_chunks((long)N) > INT32_MAX)
+        return fail(LOCO_E_INVALID, "%s: M = %lld by N = %lld is more than 2^31 - 1 workgroups; split M", fn, (long long)M, (long long)N);
+    if (ldq < kHidden || (ldq & 3) || ldq >= (1LL << 23)) return fail(LOCO_E_INVALID, "%s: ldq = %lld is not a multiple of 4 in 768 .. 2^23 - 1", fn, (long long)ldq);
+    if (ldk < kHidden || (ldk & 3)) return fail(LOCO_E_INVALID, "%s: ldk = %lld is not a multiple of 4 of at least 768", fn, (long long)ldk);
+    if (misaligned(Q, 16)) return fail(LOCO_E_INVALID, "%s: Q is not 16-byte aligned", fn);
+    if (misaligned(K, 16)) return fail(LOCO_E_INVALID, "%s: K is not 16-byte aligned", fn);
+    if (misaligned(scratch, 16)) return fail(LOCO_E_INVALID, "%s: scratch is not 16-byte aligned", fn);
+    if (misaligned(values, 4) || misaligned(indices, 4) || misaligned(q_norm2, 4) || misaligned(k_norm2, 4) || misaligned(exclude, 4))
+        return fail(LOCO_E_INVALID, "%s: values / indices / q_norm2 / k_norm2 / exclude is not 4-byte aligned", fn);
+    const size_t need = topk_scratch_bytes((long)M, (long)N, (int)k);
+    if (scratch_bytes < need) return fail(LOCO_E_WORKSPACE, "%s: scratch %zu < %zu bytes", fn, scratch_bytes, need);
+    HIP_TRY(launch_topk(Q, (long)ldq, K, (long)ldk, q_norm2, k_norm2, exclude, (long)M, (long)N, (int)k, (int)metric, values, indices, scratch,
+                        (hipStream_t)stream));
+    return LOCO_OK;
+}
+
+int loco_op_group_mean(const float* rows, int64_t ld, int64_t n_rows, const int32_t* index, const int64_t* offsets, int64_t G, int32_t dim,
+                       float* out, int64_t ldo, int32_t* count, void* stream) {
+    const char* fn = "loco_op_group_mean";
+    if (!rows) return fail(LOCO_E_INVALID, "%s: rows is null", fn);
+    if (!offsets) return fail(LOCO_E_INVALID, "%s: offsets is null", fn);
+    if (!out) return fail(LOCO_E_INVALID, "%s: out is null", fn);
+    if (dim != kHidden) return fail(LOCO_E_INVALID, "%s: dim = %d is not %d", fn, dim, kHidden);
+    if (G < 1 || G > INT32_MAX) return fail(LOCO_E_INVALID, "%s: G = %lld is outside 1 .. 2^31 - 1", fn, (long long)G);
+    if (n_rows < 1) return fail(LOCO_E_INVALID, "%s: n_rows = %lld is below 1", fn, (long long)n_rows);
+    if (ld < kHidden || (ld & 3)) return fail(LOCO_E_INVALID, "%s: ld = %lld is not a multiple of 4 of at least 768", fn, (long long)ld);
+    if (ldo < kHidden || (ldo & 3)) return fail(LOCO_E_INVALID, "%s: ldo = %lld is not a multiple of 4 of at least 768", fn, (long long)ldo);
+    if (misaligned(rows, 16)) return fail(LOCO_E_INVALID, "%s: rows is not 16-byte aligned", fn);
+    if (misaligned(out, 16)) return fail(LOCO_E_INVALID, "%s: out is not 16-byte aligned", fn);
+    if (misaligned(offsets, 8)) return fail(LOCO_E_INVALID, "%s: offsets is not 8-byte aligned", fn);
+    if (misaligned(index, 4) || misaligned(count, 4)) return fail(LOCO_E_INVALID, "%s: index / count is not 4-byte aligned", fn);
+    HIP_TRY(launch_group_mean(rows, (long)ld, (long)n_rows, index, offsets, (long)G, out, (long)ldo, count, (hipStream_t)stream));
+    return LOCO_OK;
+}
+
 }  // extern "C"

@@ -579,6 +579,26 @@ hipError_t launch_edit_distance(const int32_t* symbols, long n_symbols, const in
 hipError_t launch_nbest_risk(const int32_t* counts, const int32_t* group_offsets, const double* weights, int U, double* risk, int32_t* best,
                              hipStream_t s);
 
+// ---- embedding neighbours (neighbors.hip) ----
+constexpr int kTopkMaxK = 16;      // entries of a query's list: the lists of a 128-query workgroup take 16 KiB of LDS
+constexpr int kTopkChunk = 1024;   // keys of one topk workgroup: fixed, part of the merge order
+constexpr int kTopkDot = 0, kTopkCosine = 1, kTopkL2 = 2;
+long topk_chunks(long N);
+size_t topk_scratch_bytes(long M, long N, int k);  // 0 outside the limits
+// n2[r] = the squared norm of x's row r (768 values, row stride ldx), summed in double in one order, rounded to fp32 once
+hipError_t launch_row_norm2(const float* x, long ldx, long rows, float* n2, hipStream_t s);
+// The k best keys of every query, best first, ties towards the lower key index: values f32 [M, k], indices i32 [M, k]; (-inf, -1) where
+// fewer than k candidates exist.  dot: q.k; cosine: ((q.k) / max(|q|, 1e-12)) / max(|k|, 1e-12); l2: (2 q.k - |k|^2) - |q|^2.  qn2 / kn2
+// (launch_row_norm2; unused for dot) are the squared norms; exclude (nullable) names one key per query that is no candidate (-1: none);
+// a NaN score is no candidate.  scratch >= topk_scratch_bytes(M, N, k).  A query's result does not depend on M or on the query's row.
+hipError_t launch_topk(const float* Q, long ldq, const float* K, long ldk, const float* qn2, const float* kn2, const int32_t* exclude, long M,
+                       long N, int k, int metric, float* values, int32_t* indices, void* scratch, hipStream_t s);
+// out[g, :] = the mean of rows[index[j], :] (index null: rows[j, :]) over j in [offsets[g], offsets[g + 1]), sums in double in an order
+// that depends on the group's size alone, rounded to fp32 once; count[g] (nullable) = the group's size.  An empty group leaves out[g]
+// as it is; a row index outside [0, n_rows) is not read and makes its group's mean NaN.
+hipError_t launch_group_mean(const float* rows, long ld, long n_rows, const int32_t* index, const int64_t* offsets, long G, float* out, long ldo,
+                             int32_t* count, hipStream_t s);
+
 // the C ABI's error string (loco_last_error) for translation units other than loco_api.hip
 int api_fail(int code, const char* fmt, ...);
 

@@ -137,6 +137,20 @@ class EmbeddingStore:
             at += n
         return rows
 
+    # ---- pooling ----------------------------------------------------------------------------------------------
+    def pooled(self, how: str = "average") -> torch.Tensor:
+        """f32 [n_items, 768] on the device: the mean of each clip's stored frames -- padded frames included, as the notebooks'
+        ``torch.mean(dim=1)`` includes them -- summed in double and rounded once (``loco_op_group_mean`` over the store's own
+        offsets; nothing leaves the device).  There is no CPU path."""
+        if how != "average":
+            raise ValueError(f"how = {how!r}: only 'average' pooling is implemented")
+        if self.device.type != "cuda":
+            raise ValueError(f"pooled: the store is on {self.device}; there is no CPU path (loco_op_group_mean runs on the device)")
+        from . import neighbors
+        ends = torch.from_numpy(np.append(self.offsets_host, np.int64(self.n_rows))).to(self.device)
+        out, _ = neighbors.group_mean(self.rows, ends)
+        return out
+
     # ---- batches ----------------------------------------------------------------------------------------------
     def _check_indices(self, ind: np.ndarray):
         if ind.ndim != 1 or ind.size == 0:
