@@ -364,6 +364,18 @@ size_t loco_conv0_scratch_bytes(int32_t B);
 int loco_op_conv0_gn_gelu(const float* wav, int32_t B, int64_t L, const float* w, const float* gn_w, const float* gn_b,
                           float* out, void* scratch, void* stream);
 
+/* The same layer with every output form the forward uses.  Exactly one of `out` (fp32 [B, T0, 512]) and the pair out_hi / out_lo
+ * (fp16 planes [B, T0, 512], hi = fp16(v), lo = fp16(v - hi)) is non-null, else LOCO_E_INVALID; with `out` the result has the bits of
+ * loco_op_conv0_gn_gelu.  range_slot (may be NULL, read only with planes): 8 fp32 words, word i raised -- never lowered -- to
+ * max |v| over the 64-frame blocks i, i + 8, ... of every clip, as an unsigned maximum of the bit patterns.
+ * t0_clip (device int32 [B], may be NULL; 1 <= t0_clip[b] <= T0): the packed forward's promise.  Clip b's GroupNorm statistics run
+ * over its first t0_clip[b] conv frames only, summed in the order a launch of that clip alone, at a length whose T0 is t0_clip[b],
+ * would sum them: frames t < t0_clip[b] have that launch's bits.  Frames t >= t0_clip[b] are written as +0.0 (zero bits in both
+ * planes) and enter the range words as 0. */
+int loco_op_conv0_gn_gelu_ex(const float* wav, int32_t B, int64_t L, const float* w, const float* gn_w, const float* gn_b,
+                             float* out, void* out_hi, void* out_lo, float* range_slot, const int32_t* t0_clip, void* scratch,
+                             void* stream);
+
 /* frames[b] = loco_output_frames(sum(mask[b,:])); mask NULL -> loco_output_frames(L). (modeling:569-598) */
 int loco_op_frame_counts(const int32_t* mask, int32_t B, int64_t L, int32_t* frames, void* stream);
 

@@ -111,6 +111,7 @@ SIGNATURES = {
                                _i64, _i64, _i64, _i64, _vp]),
     "loco_conv0_scratch_bytes": (_sz, [_i32]),
     "loco_op_conv0_gn_gelu": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "loco_op_conv0_gn_gelu_ex": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "loco_op_frame_counts": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "loco_op_pos_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "loco_op_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),

@@ -43,6 +43,17 @@ int loco_op_conv0_gn_gelu(const float* wav, int32_t B, int64_t L, const float* w
     return LOCO_OK;
 }
 
+int loco_op_conv0_gn_gelu_ex(const float* wav, int32_t B, int64_t L, const float* w, const float* gn_w, const float* gn_b, float* out,
+                             void* out_hi, void* out_lo, float* range_slot, const int32_t* t0_clip, void* scratch, void* stream) {
+    const char* fn = "loco_op_conv0_gn_gelu_ex";
+    if (!wav || !w || !gn_w || !gn_b || !scratch) return fail(LOCO_E_INVALID, "%s: null argument", fn);
+    if ((out_hi == nullptr) != (out_lo == nullptr)) return fail(LOCO_E_INVALID, "%s: out_hi and out_lo go together", fn);
+    if ((out != nullptr) == (out_hi != nullptr)) return fail(LOCO_E_INVALID, "%s: exactly one of out and the plane pair", fn);
+    if (L < 10) return fail(LOCO_E_INVALID, "%s: L < 10", fn);
+    HIP_TRY(launch_conv0_gn_gelu(wav, B, L, w, gn_w, gn_b, out, scratch, 1e-5f, (hipStream_t)stream, out_hi, out_lo, range_slot, t0_clip));
+    return LOCO_OK;
+}
+
 int loco_op_frame_counts(const int32_t* mask, int32_t B, int64_t L, int32_t* frames, void* stream) {
     if (!frames || B <= 0) return fail(LOCO_E_INVALID, "loco_op_frame_counts: invalid argument");
     HIP_TRY(launch_frame_counts(mask, B, L, frames, (hipStream_t)stream));

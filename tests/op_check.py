@@ -1,7 +1,8 @@
 """Per-element checks of single operators: guarded outputs, poisoned inputs, fp64 references and derived error bars.
 
 Used by tests/test_gpu_gemm_contract.py, tests/test_gpu_attention_contract.py, tests/test_gpu_attention_probs_contract.py,
-tests/test_gpu_decoder_contract.py and (on the CPU) tests/test_decoder_contract_ref.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
+tests/test_gpu_decoder_contract.py, tests/test_gpu_frontend_contract.py and (on the CPU) tests/test_decoder_contract_ref.py and
+tests/test_frontend_ref.py.  Nothing here is fitted to a kernel's output: every bar below is a worst-case count of
 roundings times the forward-error scale of the element it applies to.
 
 Guards.  An output lives inside a larger allocation filled with a sentinel bit pattern (a NaN with a payload): before the first
@@ -114,6 +115,41 @@ Charged nothing: the running maximum and corr = expf(m_run - m_new).  o and s_ru
 it holds scales numerator and denominator alike, and p, s_run and o all carry the factor exp(-m) for whatever m the wave holds.  What an
 inexact m costs is part 2.  A query without a visible key is outside the bar: its output is exactly 0.0 and is asserted as such.
 Bar = [2 max_j delta_ij + (65 ntiles + nsplit) u] S + (8 ntiles + nsplit + 1) u |ref|, nsplit = 0 in both brackets without splits.
+
+The waveform front end (tests/frontend_cases.py, tests/test_gpu_frontend_contract.py); e = 2^-53.
+Normaliser (norm_misc.hip: wav_moments_kernel, wav_norm_coeffs_kernel, wav_norm_apply_kernel), normalize_bar() below.
+out = (x - mean) * rstd for i < n, the padding value's bits for i >= n.
+  1. `(float) mean`: one rounding, u |mean|; `xb[i] - mean`: one, u |x - mean|; both are then multiplied by rstd.
+  2. `(float)(1.0 / sqrt(var + 1e-7))` and the product: one rounding each, 2 u |ref|.
+  3. rstd's own error, relative, from var = q / n - mean^2 in fp64.  A sample's square or the sample passes `depth` roundings on its way
+     into q or s: the product v * v (1), a thread's chain of ceil(chunk / 256) additions (chunk = ceil(n / 128) rounded up to 4), the 8
+     levels of the shared-memory tree and the 128 parts in sequence.  q is a sum of positive terms: relative error depth e, one more
+     for / n.  s: depth e sum |x|, one more for / n, and |mean| and mean |x| are both at most sqrt(q / n), so mean^2 moves by at most
+     (2 (depth + 1) + 1) e q / n; the subtraction adds one.  |d var| <= (3 depth + 5) e q / n.  rstd = (var + 1e-7)^-1/2 halves the
+     relative error; sqrt and the division add one rounding each: c = (3 depth + 5) / 2 + 2, charged as c e (q / n) / (var + 1e-7) |ref|.
+     The clamp var > 0 only moves var towards its true value.
+conv0 + GroupNorm + GELU (conv0_gn_gelu.hip), conv0_bar() below.  h = fma(y - mu, sc, be), y the chain of 10 fmaf, Y = sum_k |w_k| |x_k|.
+  1. y: 10 roundings of at most u Y; `(float) mean`: u |mu|; `y - mu`: u |y - mu|; all times |sc|.
+  2. `(float)(gn_w / sqrt(var + eps))`: u |sc| |y - mu|; the fma: u |h|.
+  3. sc's error from var = E[y^2] - mean^2 in fp64.  The kernel never sums y^2: it forms w^T M w from 55 second moments of the strided
+     waveform, whose terms have both signs, so the scale of its roundings is not E[y^2] but sum_kk' |w_k| |w_k'| |M_kk'| <= E[Y^2].
+     A moment passes depth = 1 (the product) + ceil(per / 256) (a thread's chain, per = ceil(T0 / 64)) + 6 (butterfly) + 2 (the four
+     waves) + 64 (the parts in sequence) + 1 (/ T0) roundings; the quadratic form adds 2 for the products w_k w_k' M and 55 for its
+     chain: (depth + 57) e E[Y^2].  mean: (depth + 11) e E[Y], |mean| <= E[Y] <= sqrt(E[Y^2]), so mean^2 moves by (2 (depth + 11) + 1) e
+     E[Y^2]; the subtraction one more.  |d var| <= (3 depth + 81) e E[Y^2]; halved by the root, plus sqrt and the division:
+     c = (3 depth + 81) / 2 + 2, charged as c e E[Y^2] / (var + eps) |sc| |y - mu|.  (The issue's sketch charged E[y^2]; E[Y^2] is
+     what the instruction sequence supports.)
+  4. erf GELU as in element_bar: 1.13 * bar + 4 u |ref|.  The u |h| of part 2 matters here: for x < 0 gelu_erf's own error is up to
+     1.0 u |x| absolute (value_domain_cases.RESTATED_NEG_ABS_PER_X), more than 4 u |ref| in the tail, but |gelu'| <= 0.13 there, so
+     0.13 bar + u |h| <= 1.13 bar.  Planes: + max(2^-21 |ref|, 2^-25), planes_bar(): lo is an fp16 number, subnormal below 2^-14
+     with spacing 2^-24, so hi + lo misses a small value by up to 2^-25 absolute.  (The planes themselves are held to the bits of the
+     fp32 form's split; this bar only says what hi + lo is worth.)
+  The statistics run over the launch's whole T0 (zero tail included), or over t0_clip[b] frames; frames at and beyond t0_clip[b] are +0.0.
+Positional conv, fp32 (pos_conv.hip), pos_conv_count below.  ONE accumulator per element takes all K = 128 x 48 = 6144 products, four per
+v_mfma_f32_16x16x4_f32 (one per lane quarter), never folded: one rounding per product as in the fp32 GEMM's count, K of them, each at
+most u S, S = sum |h| |w| + |bias|; `acc + bv` one more, and two spare for the order inside an MFMA: K + 3.  Then the erf GELU rule
+and the two additions `hv + gelu + table`: 2 u (|h| + |gelu| + |table|).  Per product the bar is loose (S / 6144 at K + 3 roundings of
+u S), per tap it is not (S / 128): frontend_cases' one-hot weights make the conv a single exact product, and the bar a few u.
 """
 import math
 
@@ -254,6 +290,54 @@ def element_bar(ref, pre, S, count, epilogue=0, planes=False):
     if planes:
         bar = bar + 2.0 ** -21 * ref.abs()
     return bar
+
+
+EPS64 = 2.0 ** -53
+
+
+def normalize_cancel_count(n):
+    """c of the normaliser's part 3 for a row of n samples"""
+    chunk = (math.ceil(n / 128) + 3) // 4 * 4
+    depth = 1 + math.ceil(chunk / 256) + 8 + 128
+    return (3 * depth + 5) / 2 + 2
+
+
+def normalize_bar(x, ref, mean, var, q_over_n, rstd, n):
+    """The normaliser's bar of the docstring for one row's samples x (fp64), ref = (x - mean) rstd; mean, var, q_over_n, rstd fp64 scalars"""
+    bar = rstd * U * (abs(mean) + (x - mean).abs()) + 2 * U * ref.abs()
+    return bar + normalize_cancel_count(n) * EPS64 * q_over_n / (var + 1e-7) * ref.abs()
+
+
+def conv0_cancel_count(T0):
+    """c of conv0's part 3 for statistics over T0 frames"""
+    depth = 1 + math.ceil(math.ceil(T0 / 64) / 256) + 6 + 2 + 64 + 1
+    return (3 * depth + 81) / 2 + 2
+
+
+def planes_bar(bar, ref):
+    """a bar for hi + lo of a value written as fp16 planes: the + 2^-21 |ref| of the docstring, levelling off at 2^-25 where lo is a
+    subnormal fp16 number (spacing 2^-24 whatever |ref| is: value_domain_cases.split_bound) -- conv0's GELU output has such elements"""
+    return bar + (2.0 ** -21 * ref.abs()).clamp_min(2.0 ** -25)
+
+
+def conv0_bar(ref, h, y, Y, mu, sc, var, EY2, T0, eps=1e-5):
+    """conv0's bar of the docstring.  ref, h, y, Y [..., T, 512]; mu, sc, var, EY2 = E[Y^2] broadcastable per (clip, channel); T0 the
+    frames the statistics ran over (a number or a tensor broadcastable like mu).  Planes: planes_bar() of this."""
+    d = (y - mu).abs()
+    c = conv0_cancel_count(T0) if not torch.is_tensor(T0) else torch.as_tensor(
+        [conv0_cancel_count(int(t)) for t in T0.reshape(-1)], dtype=torch.float64).reshape(T0.shape)
+    rel_sc = U + c * EPS64 * EY2 / (var + eps)
+    pre = sc.abs() * U * (10 * Y + mu.abs() + d) + rel_sc * sc.abs() * d + U * h.abs()
+    return 1.13 * pre + 4 * U * ref.abs()
+
+
+POS_CONV_K = 128 * 48
+pos_conv_count = POS_CONV_K + 3
+
+
+def pos_conv_bar(g, pre, S, h, tab, count=pos_conv_count):
+    """The fp32 positional conv's bar: g = gelu(pre), S the conv's scale, h and tab the two addends, all fp64 of one shape"""
+    return element_bar(g, pre, S, count, 1) + 2 * U * (h.abs() + g.abs() + tab.abs())
 
 
 def attention_bar(kernel, ref, S, A_max, P_max, s_max, b_max, ntiles, table_formed, planes=False):
